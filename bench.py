@@ -2,7 +2,12 @@
 no-grad metrics the reference logs every step, remfx/models.py:217-256) of a RemFX
 removal network on a batch of synthetic white-noise clips (B, 1, 262144) @ 48 kHz.
 
-    python bench.py --gpus N --steps K --warmup W [--workload demucs|tcn] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--workload demucs|tcn] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, preheats and warms up, times the K steps and prints the result line.  `--full` adds everything else the
+benchmark measures: the per-kernel roofline passes, the `also` block (other arithmetic modes, sub-metrics, parity against
+the CPU oracle), the CPU baseline and the full record file.  `--dump-outputs DIR` writes what the last timed step computed
+as DIR/<name>.npy (see dump_outputs).
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
@@ -14,6 +19,7 @@ Prints ONE JSON line (rank 0).  metric = audio-seconds processed per second (who
 import argparse
 import json
 import os
+import random
 
 os.environ.setdefault("RFX_STRICT_NATIVE", "1")     # an op without a HIP kernel raises instead of running through torch-ROCm
 import sys
@@ -35,6 +41,8 @@ PEAK_F32_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md: fp32 MFMA
 PEAK_BF16_TFLOPS = 2500.0    # dense bf16 MFMA; the bf16x3 mode issues 3 bf16 MFMA flops per algorithmic flop
 DTYPES = {"f32": "f32", "bf16x3": "f32 via bf16x3 split MFMA (fp32 accumulate)", "bf16": "bf16 (fp32 accumulate)"}
 PEAK_HBM_GBS = 8000.0
+PREHEAT_SETTLE_S = 5.0       # the preheat waits at most this long past --preheat-seconds for the step time to settle: a plain run's
+                             # set-up, preheat and warm-up stay within half a minute
 
 
 # ---- output: the FULL record goes to a file (and stderr on request); stdout carries ONE compact JSON line (< 4 KB) ---------------
@@ -63,11 +71,12 @@ def step_roofline(workload, gemm, batch, sec_per_step, peak_tflops, pmc_total_by
     return r
 
 
-def emit(out, tag):
-    """Write the full record to gpurun_out/ (scratch on the GPU box; falls back to profiles/) and print the compact line."""
+def emit(out, tag, record=True):
+    """Print the compact line; with `record` (bench.py --full) also write the full record to a file (RFX_BENCH_FULL_DIR, else
+    the output folder beside bench.py, else profiles/)."""
     full_path = None
     for d in (os.environ.get("RFX_BENCH_FULL_DIR"), os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")):
-        if not d:
+        if not d or not record:
             continue
         try:
             os.makedirs(d, exist_ok=True)
@@ -148,6 +157,36 @@ def synthetic_batch(batch, rank, device, clip=CLIP):
     y = torch.randn(batch, 1, clip, generator=g) * 0.1
     lab = torch.zeros(batch, 5)
     return tuple(t.to(device) for t in (x, y, lab, lab.clone()))
+
+
+DUMP_SAMPLE = 1 << 21                  # elements kept of a larger output: 8 MB in float32, at most 4 sampled arrays per dump
+
+
+def _dump_array(t):
+    """Float32 / float64 numpy copy of a tensor (or number); above DUMP_SAMPLE elements a fixed seeded sample of it: the same
+    element positions in every run and every build, and in every array of the same size (parameters and gradients line up)."""
+    import numpy as np
+    if not torch.is_tensor(t):
+        return np.asarray(t, dtype=np.float64)
+    t = t.detach()
+    if t.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: arrays {name: tensor} -> d/<name>.npy (float32 / float64; sampled as _dump_array says)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), _dump_array(t))
+
+
+def _logged(model):
+    """The per-step values the model logged (self.log): {name: tensor}."""
+    return {k: v for k, v in getattr(model, "logged", {}).items() if torch.is_tensor(v) or isinstance(v, (int, float))}
 
 
 def variant_name(code, prec):
@@ -439,7 +478,8 @@ def bench_chain(args, rank, world, device):
     data = synthetic_batch(batch, rank, device)
     from remfx_amd import ops
     timer = KernelTimer(ops.PREC_NAMES[args.gemm])
-    timer.install()
+    if args.full:
+        timer.install()
 
     def fence():
         if world > 1:
@@ -452,7 +492,7 @@ def bench_chain(args, rank, world, device):
         timer.enabled = True
         t0 = time.time()
         for i in range(args.steps):
-            chain.test_step(data, i)
+            loss = chain.test_step(data, i)
         fence()
     dt = time.time() - t0
     timer.enabled = False
@@ -462,7 +502,18 @@ def bench_chain(args, rank, world, device):
     if rank != 0:
         return
     dt = float(t)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(loss=loss, labels=chain.last_labels, **_logged(chain)))
     napplied = float(chain.last_labels.sum())
+    line = {"metric": "audio-seconds/sec chain inference (whole job)", "value": round(world * batch * CLIP / SR * args.steps / dt, 3),
+            "unit": "audio-seconds/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": DTYPES[args.gemm],
+            "data": "synthetic", "config": {"workload": "RemFX-detect chain inference (+exp=remfx_detect), inference only",
+                                            "clips_per_gpu": batch, "clip_samples": CLIP, "sample_rate": SR,
+                                            "removal_model_applications_per_step": napplied, "parallelism": f"dp{world}"}}
+    if not args.full:
+        return emit(line, f"chain_{args.gemm}_b{batch}_n{world}", record=False)
     # roofline of the dominant gather-GEMM instantiation of the chain (detector at fp32 parity = bf16x3 inside at_least_fp32_parity,
     # removal networks in the session mode): algorithmic flops / bytes per launch over its event-timed duration
     import glob
@@ -487,20 +538,13 @@ def bench_chain(args, rank, world, device):
     cpu = None
     if not args.no_cpu_baseline:
         cpu = cpu_baseline_chain(chain.last_labels.detach().cpu(), order)
-    emit({"roofline": roof, "cpu_baseline": cpu,
-        "metric": "audio-seconds/sec chain inference (whole job)", "value": round(world * batch * CLIP / SR * args.steps / dt, 3),
-        "unit": "audio-seconds/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
-        "vs_baseline": None, "dtype": DTYPES[args.gemm],
-        "data": "synthetic", "config": {"workload": "RemFX-detect chain inference (+exp=remfx_detect), inference only",
-                                        "clips_per_gpu": batch, "clip_samples": CLIP, "sample_rate": SR,
-                                        "removal_model_applications_per_step": napplied, "parallelism": f"dp{world}"}},
-         f"chain_{args.gemm}_b{batch}_n{world}")
+    emit({"roofline": roof, "cpu_baseline": cpu, **line}, f"chain_{args.gemm}_b{batch}_n{world}")
 
 
-def measure_demucs_fwd(model, x, steps, warmup, gemm, world=1):
+def measure_demucs_fwd(model, x, steps, warmup, gemm, world=1, stage_passes=True):
     """STFT + Hybrid Demucs FORWARD (DemucsModel.sample: _spec, both U-Net branches, _ispec) on the clips `x`, no loss /
-    backward: seconds per pass (max over ranks), output rms, and HIP-event times of the two HBM-bound end stages."""
+    backward: seconds per pass (max over ranks), output rms, the output of the last timed pass, and (`stage_passes`: 4 more passes)
+    HIP-event times of the two HBM-bound end stages."""
     from remfx_amd import stft as stft_mod
     ev = {"stft": [], "istft": []}
     orig = {"stft": stft_mod.stft, "istft": stft_mod.istft}
@@ -536,19 +580,20 @@ def measure_demucs_fwd(model, x, steps, warmup, gemm, world=1):
                 out = model.model.sample(x)
             fence()
             dt = time.time() - t0
-            # the two end stages are priced like the dominant kernel: on passes with the time branch on the compute stream, so that an
-            # event bracket holds the FFT launch alone (beside the time branch's kernels it reads 1.6x longer)
-            two, _hd.TWO_STREAMS = _hd.TWO_STREAMS, False
-            try:
-                model.model.sample(x)
-                fence()
-                state["on"] = True
-                for _ in range(3):
+            if stage_passes:
+                # the two end stages are priced like the dominant kernel: on passes with the time branch on the compute stream, so that
+                # an event bracket holds the FFT launch alone (beside the time branch's kernels it reads 1.6x longer)
+                two, _hd.TWO_STREAMS = _hd.TWO_STREAMS, False
+                try:
                     model.model.sample(x)
-                fence()
-                state["on"] = False
-            finally:
-                _hd.TWO_STREAMS = two
+                    fence()
+                    state["on"] = True
+                    for _ in range(3):
+                        model.model.sample(x)
+                    fence()
+                    state["on"] = False
+                finally:
+                    _hd.TWO_STREAMS = two
     finally:
         stft_mod.stft, stft_mod.istft = orig["stft"], orig["istft"]
         model.train(was_training)
@@ -577,7 +622,8 @@ def measure_demucs_fwd(model, x, steps, warmup, gemm, world=1):
                       "frac_mfma": round(batch * 117.2e9 / (unet_ms * 1e-3) / 1e12 / mfma_peak, 4)}
     stages["source"] = "event brackets on 3 one-stream passes after the timed ones"
     return {"seconds": dt, "flops": flops, "bytes": nbytes, "frac_hbm": f_hbm, "frac_hbm_fp32_bytes": f_hbm32, "frac_mfma": f_mfma, "mfma_peak": mfma_peak,
-            "stages": stages, "output_rms": float(out.float().pow(2).mean().sqrt())}
+            "stages": stages if stage_passes else None, "output_rms": float(out.float().pow(2).mean().sqrt()),
+            "output": out}
 
 
 def bench_demucs_fwd(args, rank, world, device):
@@ -587,9 +633,11 @@ def bench_demucs_fwd(args, rank, world, device):
     batch = args.batch or 64
     model = build_model("demucs", device).eval()
     x = synthetic_batch(batch, rank, device)[0]
-    m = measure_demucs_fwd(model, x, args.steps, args.warmup, args.gemm, world)
+    m = measure_demucs_fwd(model, x, args.steps, args.warmup, args.gemm, world, stage_passes=args.full)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"output": m["output"]})
     dt, f_hbm, f_mfma = m["seconds"], m["frac_hbm"], m["frac_mfma"]
     bound = "hbm" if f_hbm >= f_mfma else "mfma"
     emit({
@@ -605,7 +653,7 @@ def bench_demucs_fwd(args, rank, world, device):
                      "frac": round(max(f_hbm, f_mfma), 4), "frac_hbm": round(f_hbm, 4), "frac_mfma": round(f_mfma, 4),
                      "frac_hbm_fp32_bytes": round(m["frac_hbm_fp32_bytes"], 4),
                      "algorithmic_bytes_per_pass": m["bytes"], "algorithmic_flops_per_pass": m["flops"], "traffic": None,
-                     "stages": m["stages"]}}, f"demucs_fwd_{args.gemm}_b{batch}_n{world}")
+                     "stages": m["stages"]}}, f"demucs_fwd_{args.gemm}_b{batch}_n{world}", record=args.full)
 
 
 def also_block(args, model, opt, sched, sync, data, device, step):
@@ -717,6 +765,14 @@ def main():
                     help="skip the 3 instrumented and the 3 one-stream steps behind the timed region (the per-kernel table and the dominant "
                          "kernel's price): profiler runs then contain exactly preheat + W + K steps")
     ap.add_argument("--dump-launches", default="", help="write the per-launch plan / algorithmic work / event time list of the timed steps (JSON)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; arrays "
+                         "above 2^21 elements as a fixed seeded sample): the loss, the logged metrics, the parameters and gradients "
+                         "(training workloads), the detected labels (chain), the output (demucs_fwd)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure as well: the per-kernel roofline passes (3 instrumented + 3 "
+                         "one-stream steps), the `also` block, the CPU baseline, the full record file; --no-also / --no-exclusive / "
+                         "--no-cpu-baseline switch parts of it off again")
     ap.add_argument("--union-ranks", type=int, default=0,
                     help="single process only: train on the concatenation of the synthetic batches ranks 0..N-1 would "
                          "get (N x --batch clips) -- the reference point of the data-parallel equivalence test")
@@ -727,6 +783,10 @@ def main():
                          "of the fp32 oracle) for the fp32 configs (TCN config 2, DCUNet config 4, Open-Unmix, chain inference); "
                          "f32: exact fp32 MFMA")
     args = ap.parse_args()
+    if not args.full:                           # a plain run: set up, warm up, the timed steps, the outputs, the result line
+        args.no_cpu_baseline = args.no_also = args.no_exclusive = True
+        if args.dump_launches:
+            raise SystemExit("--dump-launches lists the instrumented steps of --full")
     if args.gemm is None:
         args.gemm = "bf16" if args.workload in ("demucs", "demucs_fwd") else "bf16x3"
     if args.workload == "tcn" and args.warmup < 2:
@@ -794,7 +854,8 @@ def main():
     if not args.no_priority_stream:
         ops.enter_compute_stream(device)             # compute stream high priority, weight-gradient side stream normal (as Trainer.fit)
     timer = KernelTimer(ops.PREC_NAMES[args.gemm])
-    timer.install()
+    if args.full:
+        timer.install()
 
     # as Trainer.fit: Python's cyclic collector stays out of the enqueue loop (ops.StepGC: a full collection every 50 steps, between
     # two steps; RFX_STEP_GC=0 is the A/B -- 32 - 36 ms against a steady 31 ms at 8 clips)
@@ -821,13 +882,22 @@ def main():
     # back to back on one fresh box: 151.7 / 144.1 / 143.7 ms; with 60 untimed steps in front, the first process reads 144.8 ms) --
     # too long for W = 5 warm-up steps and invisible to a "step time has stopped falling" test.  So: at least `--preheat` steps AND
     # `--preheat-seconds` of wall time, then until the last three synchronised steps are within 1.5 % of the fastest one seen (bounded
-    # by `--preheat-max` steps).  `--preheat 0` disables all of it.  The count is reported as `preheat_steps`; none of it is timed.
+    # by `--preheat-max` steps and PREHEAT_SETTLE_S).  `--preheat 0` disables all of it.  The count is reported as `preheat_steps`; none of
+    # it is timed.
+    # The preheat's step count depends on the box, so the training state from before it is put back after it: the W + K steps start
+    # from the freshly built model in every run, and the last timed step sees the same inputs every time (--dump-outputs).
+    snap = None
+    if args.preheat > 0:
+        snap = ([t.clone() for t in (opt.flat.data, opt.m, opt.v)], [b.clone() for b in model.buffers()], opt.step_count,
+                sched.last_epoch, opt.param_groups[0]["lr"], torch.get_rng_state(), torch.cuda.get_rng_state(device), random.getstate())
     pre_t, n_pre, pre_t0 = [], 0, time.time()
     n_max = args.preheat_max if args.preheat > 0 else 0
     while True:
         if n_pre >= args.preheat:
             stable = len(pre_t) >= 4 and max(pre_t[-3:]) <= 1.015 * min(pre_t[1:])
-            more = torch.tensor([float(n_pre < n_max and (time.time() - pre_t0 < args.preheat_seconds or not stable))], device=device)
+            el = time.time() - pre_t0
+            settle = not stable and el < args.preheat_seconds + PREHEAT_SETTLE_S
+            more = torch.tensor([float(n_pre < n_max and (el < args.preheat_seconds or settle))], device=device)
             if world > 1:                            # every rank takes the same decision
                 torch.distributed.all_reduce(more, op=torch.distributed.ReduceOp.MAX)
             if float(more) == 0.0:
@@ -839,6 +909,18 @@ def main():
         pre_t.append(time.time() - t0)
         n_pre += 1
     args.preheat = n_pre
+    if snap is not None:
+        (data0, m0, v0), bufs0, opt.step_count, sched.last_epoch, opt.param_groups[0]["lr"], rng_cpu, rng_dev, rng_py = snap
+        for dst, src in zip((opt.flat.data, opt.m, opt.v), (data0, m0, v0)):
+            dst.copy_(src)
+        for b, b0 in zip(model.buffers(), bufs0):
+            b.copy_(b0)
+        torch.set_rng_state(rng_cpu)
+        torch.cuda.set_rng_state(rng_dev, device)
+        random.setstate(rng_py)
+        ops.weights_changed()                    # parameters written in place: cached weight packs are stale
+        torch.cuda.synchronize()
+        del snap, data0, m0, v0, bufs0
     PHASES["preheat"] = round(time.time() - pre_t0, 2)
     t_w0 = time.time()
     for i in range(args.warmup):
@@ -855,6 +937,10 @@ def main():
     fence()
     dt = time.time() - t0
     PHASES["timed"] = round(dt, 2)
+    if args.dump_outputs and rank == 0:
+        t_d0 = time.time()
+        dump_outputs(args.dump_outputs, dict(loss=loss, params=opt.flat.data, grads=opt.flat.grad, **_logged(model)))
+        PHASES["dump_outputs"] = round(time.time() - t_d0, 2)
     OBS = 0 if args.no_exclusive else 3       # profiler runs (--no-exclusive) execute exactly preheat + W + K steps
     timer.enabled = True
     for i in range(OBS):
@@ -880,7 +966,7 @@ def main():
     # The timed region runs weight-gradient GEMMs on a second stream (ops.GradSink), so a forward-family launch shares the machine
     # with them and its event-timed duration is a CONCURRENT one.  For the kernel's own efficiency, time a few extra steps with
     # everything on the compute stream (not part of `value`): roofline.exclusive.
-    param_abs_sum = float(opt.flat.data.double().abs().sum())     # state after exactly W + K + OBS (+ preheat) steps: the 2-rank test compares it
+    param_abs_sum = float(opt.flat.data.double().abs().sum())     # state after exactly W + K + OBS steps: the 2-rank test compares it
     excl = None
     t_x0 = time.time()
     sink = getattr(opt.flat, "sink", None)
@@ -1014,6 +1100,8 @@ def main():
                      "family": dict(fam, kernel=fam_name, traffic=fam_traffic, share_of_step=round((kms / max(OBS, 1)) / (dt / args.steps * 1e3), 3)),
                      "by_bound": {"mfma": _price(*cls["mfma"]), "hbm": _price(*cls["hbm"])}},
     }
+    if not args.full:
+        del out["roofline"]                     # per-kernel figures: the instrumented steps of --full
     if args.workload == "demucs" and world == 1 and not args.no_also:
         t_a0 = time.time()
         out["also"] = also_block(args, model, opt, sched, sync, data, device, step)
@@ -1051,7 +1139,7 @@ def main():
     if cands:
         tot_traffic = json.load(open(cands[-1])).get("total_bytes_per_step")
     out["step_roofline"] = dict(step_roofline(args.workload, args.gemm, batch, dt / args.steps, peak, tot_traffic), traffic_source=pmc_file)
-    emit(out, f"{args.workload}_{args.gemm}_b{batch}_n{world}")
+    emit(out, f"{args.workload}_{args.gemm}_b{batch}_n{world}", record=args.full)
 
 
 if __name__ == "__main__":

@@ -32,12 +32,12 @@ cp $OUT/${R}_demucs_b8_bf16_pmc_traffic.json profiles/${R}_demucs_b8_pmc_traffic
 for t in tcn_b32_bf16x3 dcunet_b4_bf16x3 chain_b16_bf16x3 demucs_b8_bf16; do
   python scripts/prof_summary.py $OUT/${R}_${t}_kernel_stats.csv 3 25 $OUT/${R}_${t}_pmc_traffic.json > $OUT/${R}_${t}_summary.md 2>/dev/null
 done
-python bench.py --workload tcn --steps 2 --warmup 2 2>> $OUT/cfg.err | tail -1 > $OUT/bench_tcn_bf16x3.json
-python bench.py --workload dcunet 2>> $OUT/cfg.err | tail -1 > $OUT/bench_dcunet_bf16x3.json
-python bench.py --workload chain 2>> $OUT/cfg.err | tail -1 > $OUT/bench_chain_bf16x3.json
-python bench.py --workload umx 2>> $OUT/cfg.err | tail -1 > $OUT/bench_umx_bf16x3.json
-python bench.py --workload demucs --batch 8 --steps 20 --warmup 5 --no-also 2>> $OUT/cfg.err | tail -1 > $OUT/bench_demucs_bf16_b8.json
+python bench.py --full --workload tcn --steps 2 --warmup 2 2>> $OUT/cfg.err | tail -1 > $OUT/bench_tcn_bf16x3.json
+python bench.py --full --workload dcunet 2>> $OUT/cfg.err | tail -1 > $OUT/bench_dcunet_bf16x3.json
+python bench.py --full --workload chain 2>> $OUT/cfg.err | tail -1 > $OUT/bench_chain_bf16x3.json
+python bench.py --full --workload umx 2>> $OUT/cfg.err | tail -1 > $OUT/bench_umx_bf16x3.json
+python bench.py --full --workload demucs --batch 8 --steps 20 --warmup 5 --no-also 2>> $OUT/cfg.err | tail -1 > $OUT/bench_demucs_bf16_b8.json
 grep -ho '"ms_per_step": [0-9.]*' $OUT/bench_tcn_bf16x3.json $OUT/bench_dcunet_bf16x3.json $OUT/bench_chain_bf16x3.json $OUT/bench_demucs_bf16_b8.json | tr '\n' ' '
 # the per-rank shares of config 3 at 4 / 2 GPUs (16 / 32 clips): the projected-scaling table of DESIGN.md section 7
-python bench.py --workload demucs --batch 16 --steps 20 --warmup 5 --no-also --no-cpu-baseline 2>> $OUT/cfg.err | tail -1 > $OUT/bench_demucs_bf16_b16.json
-python bench.py --workload demucs --batch 32 --steps 20 --warmup 5 --no-also --no-cpu-baseline 2>> $OUT/cfg.err | tail -1 > $OUT/bench_demucs_bf16_b32.json
+python bench.py --full --workload demucs --batch 16 --steps 20 --warmup 5 --no-also --no-cpu-baseline 2>> $OUT/cfg.err | tail -1 > $OUT/bench_demucs_bf16_b16.json
+python bench.py --full --workload demucs --batch 32 --steps 20 --warmup 5 --no-also --no-cpu-baseline 2>> $OUT/cfg.err | tail -1 > $OUT/bench_demucs_bf16_b32.json

@@ -25,9 +25,9 @@ python scripts/collect_pmc.py $OUT/pmc_FETCH_SIZE.csv $OUT/pmc_WRITE_SIZE.csv $O
 rm -f $OUT/pmc_FETCH_SIZE.csv $OUT/pmc_WRITE_SIZE.csv
 python scripts/prof_summary.py $OUT/${R}_demucs_b64_kernel_stats_$MODE.csv 6 40 $OUT/${R}_demucs_b64_pmc_traffic_$MODE.json > $OUT/${R}_demucs_b64_summary_$MODE.md
 cp $OUT/${R}_demucs_b64_pmc_traffic_$MODE.json profiles/ 2>/dev/null    # bench.py joins its per-kernel table with the newest PMC pass
-python bench.py --steps 20 --warmup 5 --gemm $MODE > $OUT/bench_demucs_$MODE.json 2> $OUT/bench_demucs_$MODE.err
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-also --sink main --gemm $MODE 2>> $OUT/bench_demucs_$MODE.err | tail -1 > $OUT/bench_demucs_${MODE}_sinkmain.json
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-also --sink off --no-fused-dconv --gemm $MODE 2>> $OUT/bench_demucs_$MODE.err | tail -1 > $OUT/bench_demucs_${MODE}_r02path.json
-python bench.py --workload demucs_fwd --gemm $MODE > $OUT/bench_demucs_fwd_$MODE.json 2>> $OUT/bench_demucs_$MODE.err
+python bench.py --full --steps 20 --warmup 5 --gemm $MODE > $OUT/bench_demucs_$MODE.json 2> $OUT/bench_demucs_$MODE.err
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-also --sink main --gemm $MODE 2>> $OUT/bench_demucs_$MODE.err | tail -1 > $OUT/bench_demucs_${MODE}_sinkmain.json
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-also --sink off --no-fused-dconv --gemm $MODE 2>> $OUT/bench_demucs_$MODE.err | tail -1 > $OUT/bench_demucs_${MODE}_r02path.json
+python bench.py --full --workload demucs_fwd --gemm $MODE > $OUT/bench_demucs_fwd_$MODE.json 2>> $OUT/bench_demucs_$MODE.err
 # (TCN / DCUNet / Open-Unmix / chain / the 8-clip batch: scripts/measure_configs.sh, with their own kernel stats, PMC passes and cpu_baseline)
 grep -ho '"ms_per_step": [0-9.]*' $OUT/bench_*_$MODE.json | tr '\n' ' '

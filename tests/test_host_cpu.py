@@ -352,20 +352,6 @@ def test_bench_final_line_is_compact(tmp_path, monkeypatch, capsys):
     assert len(full["roofline"]["by_kernel"]) == 80
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/cfg"), reason="reference tree only exists in the build container")
-def test_composer_reproduces_fixture_from_reference_tree():
-    from remfx_amd import config
-    for name, rec in _composed().items():
-        cfg = config.compose("/root/reference/cfg", "config.yaml", rec["argv"])
-        a, b = dict(cfg), dict(rec["cfg"])
-        for d in (a, b):                                   # ${now:...} stamps differ between runs
-            d.get("callbacks", {}).get("model_checkpoint", {}).pop("dirpath", None)
-            if isinstance(d.get("logger"), dict):
-                d["logger"] = {k: v for k, v in d["logger"].items() if k != "version"}
-        import json
-        assert json.loads(json.dumps(a)) == b, name
-
-
 def test_effect_label_order_and_alias():
     import remfx.effects as alias
     from remfx_amd import effects, models
