@@ -405,6 +405,28 @@ int rfx_fx_reverb(const float* x, float* y, int32_t B, int64_t T, int32_t sample
 int rfx_fx_loudness(const float* x, int32_t B, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
                     double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs, float* gain, void* stream);
 int rfx_fx_scale(const float* x, float* y, int32_t B, int64_t T, const float* gain, void* stream);
+/* The same measurement for B clips of C channels, x: (B, C, T): pyloudnorm's joint multichannel loudness (block power = sum of the
+ * channels' mean squares).  hop_ws: B * C * nhop doubles; lufs[B], gain[B]. */
+int rfx_fx_loudness_joint(const float* x, int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
+                          double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs, float* gain,
+                          void* stream);
+/* The rest of remfx/effects.py: RandomPedalboardLimiter (:468-494), RandomParametricEQ (:37-214), RandomStereoWidener (:217-252),
+ * RandomVolumeAutomation (:255-294), RandomPedalboardPhaser (:418-465).  Parameters per row unless stated.
+ * limiter: ws = 2 * B * T floats; params = 9 x B floats on the device, rows thr1 ratio1 c_attack1 c_release1 (stage 1),
+ *          thr2 ratio2 c_attack2 c_release2 (stage 2, linear thresholds and ballistics coefficients as for rfx_fx_compressor), make-up.
+ * eq: nsec = 2..8 biquads; coef on the device, per row nsec x {b0 b1 b2 a1 a2} (a0 = 1) then the (2 nsec)^2 zero-input state
+ *     transition of `chunk` samples, row-major; chunk * 64 >= T.
+ * widener: B (2, T) clips, x: (B, 2, T); g_mid = 2 (1 - width), g_side = 2 width per clip.
+ * volume: IN PLACE; S segments per row: seg_end (cumulative end sample, non-decreasing), dB at the segment's start and end; S <= 64.
+ * phaser: ws = rfx_fx_phaser_ws_floats(B, T) floats. */
+int rfx_fx_limiter(const float* x, float* y, float* ws, int32_t B, int64_t T, const float* params, void* stream);
+int rfx_fx_eq(const float* x, float* y, int32_t B, int64_t T, int32_t nsec, int32_t chunk, const double* coef, void* stream);
+int rfx_fx_widener(const float* x, float* y, int32_t B, int64_t T, const float* g_mid, const float* g_side, void* stream);
+int rfx_fx_volume(float* x, int32_t B, int64_t T, int32_t S, const int32_t* seg_end, const float* db_start, const float* db_end,
+                  void* stream);
+int64_t rfx_fx_phaser_ws_floats(int32_t B, int64_t T);
+int rfx_fx_phaser(const float* x, float* y, float* ws, int32_t B, int64_t T, float sample_rate, const float* rate_hz, const float* depth,
+                  const float* centre_hz, const float* feedback, const float* mix, void* stream);
 
 /* ---- fused DConv depth-layer of the Hybrid Demucs frequency branch (bf16 arithmetic) ---------------------------------------
  * torchaudio HDemucs `_DConv` layer (reached from remfx/models.py:319): x_out = x + scale * GLU(GN(conv1x1(GELU(GN(conv3_dil(x))))))

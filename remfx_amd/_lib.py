@@ -200,6 +200,13 @@ SIGNATURES = {
     "rfx_fx_reverb": [_P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P],
     "rfx_fx_loudness": [_P, _I32, _I64, _I32, _I32, _I32, _I32, C.c_double, _P, C.c_float, _P, _P, _P, _P],
     "rfx_fx_scale": [_P, _P, _I32, _I64, _P, _P],
+    "rfx_fx_loudness_joint": [_P, _I32, _I32, _I64, _I32, _I32, _I32, _I32, C.c_double, _P, C.c_float, _P, _P, _P, _P],
+    "rfx_fx_limiter": [_P, _P, _P, _I32, _I64, _P, _P],
+    "rfx_fx_eq": [_P, _P, _I32, _I64, _I32, _I32, _P, _P],
+    "rfx_fx_widener": [_P, _P, _I32, _I64, _P, _P, _P],
+    "rfx_fx_volume": [_P, _I32, _I64, _I32, _P, _P, _P, _P],
+    "rfx_fx_phaser_ws_floats": [_I32, _I64],
+    "rfx_fx_phaser": [_P, _P, _P, _I32, _I64, C.c_float, _P, _P, _P, _P, _P, _P],
     "rfx_localstate_gen_fwd": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
     "rfx_localstate_gen_bwd": [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "rfx_mha_fwd": [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
@@ -244,7 +251,8 @@ SIGNATURES = {
     "rfx_cl_dconv_bwd": [_P, _P, _P],
 }
 
-_RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws"}
+_RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",
+          "rfx_fx_phaser_ws_floats"}
 _lib = None
 
 

@@ -139,6 +139,8 @@ __global__ __launch_bounds__(64) void fx_comp_env_kernel(const float* __restrict
     er[n] = yv;
   }
 }
+// the static gain computer, shared by the compressor and the limiter's output pass
+__device__ __forceinline__ float fx_comp_gain(float e, float th, float ti, float ex) { return e < th ? 1.0f : powf(e * ti, ex); }
 __global__ __launch_bounds__(256) void fx_comp_gain_kernel(const float* __restrict__ x, const float* __restrict__ env,
                                                            float* __restrict__ y, int64_t T, const float* __restrict__ thr,
                                                            const float* __restrict__ ratio) {
@@ -148,9 +150,28 @@ __global__ __launch_bounds__(256) void fx_comp_gain_kernel(const float* __restri
   const float* er = env + (int64_t)b * T;
   float* yr = y + (int64_t)b * T;
   for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < T; n += (int64_t)gridDim.x * 256) {
-    const float e = er[n];
-    const float g = e < th ? 1.0f : powf(e * ti, ex);
+    const float g = fx_comp_gain(er[n], th, ti, ex);
     yr[n] = g * xr[n];
+  }
+}
+
+// ---- limiter: JUCE dsp::Limiter (pedalboard.Limiter) = two Compressors in series, make-up gain, hard clip to [-1, 1] --------
+//   stage 1: -10 dB, ratio 4, attack 2 ms, release 200 ms;  stage 2: threshold_db, ratio 1000, attack 0.001 ms, release_ms
+//   make-up = min(10^(10 (1 - 1/4) / 40), 10^(-threshold_db / 20))
+// Stage 1 is the compressor's two kernels as they are; stage 2's envelope walks stage 1's output with the same lane kernel, and one
+// coalesced pass applies stage 2's gain, the make-up gain and the clip.  Two lane walks of ~5 instructions per sample each: the
+// gain computer's powf stays off the serial lanes.
+__global__ __launch_bounds__(256) void fx_limit_out_kernel(const float* __restrict__ x, const float* __restrict__ env,
+                                                           float* __restrict__ y, int64_t T, const float* __restrict__ thr,
+                                                           const float* __restrict__ ratio, const float* __restrict__ makeup) {
+  const int b = blockIdx.y;
+  const float th = thr[b], ti = 1.0f / th, ex = 1.0f / ratio[b] - 1.0f, mk = makeup[b];
+  const float* xr = x + (int64_t)b * T;
+  const float* er = env + (int64_t)b * T;
+  float* yr = y + (int64_t)b * T;
+  for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < T; n += (int64_t)gridDim.x * 256) {
+    const float v = (fx_comp_gain(er[n], th, ti, ex) * xr[n]) * mk;
+    yr[n] = fminf(fmaxf(v, -1.0f), 1.0f);
   }
 }
 
@@ -306,16 +327,23 @@ __global__ __launch_bounds__(64) void fx_kweight_kernel(const FxLoudArgs a) {
   }
   if (hi > lo && h < a.nhop) atomicAdd(hp + h, acc);
 }
-// gating on the hop sums; gain[b] = 10^(clamp(target - L, -120, 40) / 20).  One thread per clip.
-__global__ void fx_loud_gate_kernel(const double* __restrict__ hop, int B, int nhop, int nblk, double inv_block, float target,
+// gating on the hop sums; gain[b] = 10^(clamp(target - L, -120, 40) / 20).  One thread per clip.  A clip of C channels owns C
+// consecutive rows of hop sums: pyloudnorm's multichannel block power is the sum of the channels' mean squares (weight 1 for L, R).
+__device__ __forceinline__ double fx_hop_sum(const double* hp, int nhop, int C, int j) {
+  double h = hp[j];
+  for (int c = 1; c < C; ++c) h += hp[(int64_t)c * nhop + j];
+  return h;
+}
+__global__ void fx_loud_gate_kernel(const double* __restrict__ hop, int B, int C, int nhop, int nblk, double inv_block, float target,
                                     float* __restrict__ lufs, float* __restrict__ gain) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const double* hp = hop + (int64_t)b * nhop;
+  const double* hp = hop + (int64_t)b * C * nhop;
   // block j = hops j .. j + 3 (400 ms at 75 % overlap)
   double s1 = 0.0; int n1 = 0;
   for (int j = 0; j < nblk; ++j) {
-    const double z = (hp[j] + hp[j + 1] + hp[j + 2] + hp[j + 3]) * inv_block;
+    const double z = (fx_hop_sum(hp, nhop, C, j) + fx_hop_sum(hp, nhop, C, j + 1) + fx_hop_sum(hp, nhop, C, j + 2) +
+                      fx_hop_sum(hp, nhop, C, j + 3)) * inv_block;
     const double l = -0.691 + 10.0 * log10(z);
     if (l >= -70.0) { s1 += z; ++n1; }
   }
@@ -325,7 +353,8 @@ __global__ void fx_loud_gate_kernel(const double* __restrict__ hop, int B, int n
     const double gamma_r = -0.691 + 10.0 * log10(s1 / n1) - 10.0;
     double s2 = 0.0; int n2 = 0;
     for (int j = 0; j < nblk; ++j) {
-      const double z = (hp[j] + hp[j + 1] + hp[j + 2] + hp[j + 3]) * inv_block;
+      const double z = (fx_hop_sum(hp, nhop, C, j) + fx_hop_sum(hp, nhop, C, j + 1) + fx_hop_sum(hp, nhop, C, j + 2) +
+                        fx_hop_sum(hp, nhop, C, j + 3)) * inv_block;
       const double l = -0.691 + 10.0 * log10(z);
       if (l > gamma_r && l > -70.0) { s2 += z; ++n2; }
     }
@@ -343,6 +372,210 @@ __global__ __launch_bounds__(256) void fx_scale_kernel(const float* __restrict__
   const float* xr = x + (int64_t)b * T;
   float* yr = y + (int64_t)b * T;
   for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < T; n += (int64_t)gridDim.x * 256) yr[n] = g * xr[n];
+}
+
+// ---- parametric EQ (reference parametric_eq: low shelf -> N peaking bands -> high shelf, RBJ biquads, lfilter in fp64) ------
+// A cascade of NS = N + 2 biquads in transposed direct form II, fp64, rounded to fp32 at the end: an order-2 NS linear recurrence,
+// blocked like fx_kweight_kernel.  64 chunks per row, one lane each: pass 1 filters every chunk from a zero state; the true start
+// state of every chunk follows from s_k = M s_(k-1) + z_k with the row's own M = A^chunk (2 NS x 2 NS, from the host), one lane per
+// state component; pass 2 re-filters from the right state and stores.  Only the last non-empty chunk can be short, and its end
+// state is never used.  coef per row: NS x {b0, b1, b2, a1, a2} (a0 = 1), then M row-major.
+#define FX_EQ_MAX_NS 8
+__device__ __forceinline__ double fx_biquad5(const double* c, double x, double& s0, double& s1) {
+  const double y = c[0] * x + s0;
+  s0 = c[1] * x - c[3] * y + s1;
+  s1 = c[2] * x - c[4] * y;
+  return y;
+}
+template <int NS>
+__global__ __launch_bounds__(64) void fx_eq_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t T, int chunk,
+                                                   const double* __restrict__ coef) {
+  constexpr int D = 2 * NS, CS = 5 * NS + D * D;
+  __shared__ double st[64][D];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const double* cr = coef + (int64_t)row * CS;
+  double c[5 * NS];
+#pragma unroll
+  for (int i = 0; i < 5 * NS; ++i) c[i] = cr[i];
+  const float* xr = x + (int64_t)row * T;
+  float* yr = y + (int64_t)row * T;
+  const int64_t lo = (int64_t)lane * chunk, hi = lo + chunk < T ? lo + chunk : T;
+  double s[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) s[i] = 0.0;
+  for (int64_t n = lo; n < hi; ++n) {
+    double v = (double)xr[n];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) v = fx_biquad5(c + 5 * k, v, s[2 * k], s[2 * k + 1]);
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i) st[lane][i] = s[i];
+  __syncthreads();
+  {
+    // lane i < D carries component i of the running state; lanes >= D shadow lane 0 and store nothing
+    const int i = lane < D ? lane : 0;
+    double m[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) m[j] = cr[5 * NS + i * D + j];
+    double cur = 0.0;
+    for (int k = 0; k < 64; ++k) {
+      double acc = st[k][i];
+      if (lane < D) st[k][i] = cur;
+#pragma unroll
+      for (int j = 0; j < D; ++j) acc += m[j] * __shfl(cur, j, 64);
+      cur = acc;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < D; ++i) s[i] = st[lane][i];
+  for (int64_t n = lo; n < hi; ++n) {
+    double v = (double)xr[n];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) v = fx_biquad5(c + 5 * k, v, s[2 * k], s[2 * k + 1]);
+    yr[n] = (float)v;
+  }
+}
+
+// ---- stereo widener (reference stereo_widener, fp32 torch) on (2, T) clips ---------------------------------------------------
+//   mid = (l + r) / sqrt2;  side = (l - r) / sqrt2;  mid *= 2 (1 - w);  side *= 2 w;  l' = (mid + side) / sqrt2;  r' = (mid - side) / sqrt2
+// The reference's operation order and roundings: correctly rounded divisions by fp32(sqrt2), every product rounded before the
+// following add.  -ffp-contract=fast fuses across a `fp contract(off)` pragma and the _rn intrinsics alike (mid * gm + side
+// became one fma: 1-ulp differences that the cancellation in mid - side grew to thousands of ulps), so the products pass through
+// fx_rounded, an empty asm the combiner cannot look through.  16-byte vectors.
+__device__ __forceinline__ float fx_rounded(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ void fx_widen(float l, float r, float gm, float gs, float& ol, float& orr) {
+  const float r2 = 1.41421356237309515f;
+  const float mid = fx_rounded(((l + r) / r2) * gm), side = fx_rounded(((l - r) / r2) * gs);
+  ol = (mid + side) / r2;
+  orr = (mid - side) / r2;
+}
+__global__ __launch_bounds__(256) void fx_widener_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t T,
+                                                         const float* __restrict__ g_mid, const float* __restrict__ g_side) {
+  const int b = blockIdx.y;
+  const float gm = g_mid[b], gs = g_side[b];
+  const float* xl = x + (int64_t)b * 2 * T;
+  const float* xr = xl + T;
+  float* yl = y + (int64_t)b * 2 * T;
+  float* yr = yl + T;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < T; i += (int64_t)gridDim.x * 1024) {
+    if (i + 3 < T) {
+      const f32x4 l = rfx_ld4(xl + i), r = rfx_ld4(xr + i);
+      f32x4 ol, orr;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float a, c;
+        fx_widen(l[j], r[j], gm, gs, a, c);
+        ol[j] = a;
+        orr[j] = c;
+      }
+      rfx_st4(yl + i, ol);
+      rfx_st4(yr + i, orr);
+    } else {
+      for (int64_t k = i; k < T; ++k) fx_widen(xl[k], xr[k], gm, gs, yl[k], yr[k]);
+    }
+  }
+}
+
+// ---- volume automation (reference RandomVolumeAutomation): piecewise-linear dB ramps, applied IN PLACE -------------------------
+// Per row a table of S segments (end sample, start dB, end dB), contiguous from sample 0; samples past the last end keep 0 dB
+// (gain 1: left untouched).  The dB value of a sample follows torch.linspace's fp32 formula, step = (end - start) / (steps - 1),
+// start + step i in the first half and end - step (steps - 1 - i) in the second; then x *= 10^(dB / 20).
+#define FX_VOL_MAXSEG 64
+__global__ __launch_bounds__(256) void fx_volume_kernel(float* __restrict__ x, int64_t T, int S, const int32_t* __restrict__ seg_end,
+                                                        const float* __restrict__ db_start, const float* __restrict__ db_end) {
+  __shared__ int64_t se[FX_VOL_MAXSEG];
+  __shared__ float sa[FX_VOL_MAXSEG], sb[FX_VOL_MAXSEG];
+  const int b = blockIdx.y;
+  if (threadIdx.x < S) {
+    se[threadIdx.x] = seg_end[b * S + threadIdx.x];
+    sa[threadIdx.x] = db_start[b * S + threadIdx.x];
+    sb[threadIdx.x] = db_end[b * S + threadIdx.x];
+  }
+  __syncthreads();
+  const int64_t filled = se[S - 1] < T ? se[S - 1] : T;
+  float* xr = x + (int64_t)b * T;
+  for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < filled; n += (int64_t)gridDim.x * 256) {
+    int s = 0;
+    while (n >= se[s]) ++s;                 // n < se[S - 1]: ends at s <= S - 1; zero-length segments are skipped
+    const int64_t lo = s ? se[s - 1] : 0, steps = se[s] - lo, i = n - lo;
+    const float st = sa[s], en = sb[s];
+    float v = st;
+    if (steps > 1) {
+      const float step = (en - st) / (float)(steps - 1);
+      v = i < steps / 2 ? st + step * (float)i : en - step * (float)(steps - i - 1);     // fused: within an ulp of torch's dB
+    }
+    xr[n] = xr[n] * powf(10.0f, v / 20.0f);
+  }
+}
+
+// ---- phaser: JUCE dsp::Phaser (pedalboard.Phaser) ------------------------------------------------------------------------------
+//   every 4th sample (m = n / 4): lfo = sin(2 pi rate m / (sr / 4) - pi) depth / 2;  f = mapToLog10(clamp(lfo + normCentre, 0, 1),
+//   20, fmax), fmax = min(20000, 0.49 sr);  G = g / (1 + g), g = tan(pi f / sr)
+//   u = x[n] - fb out[n - 1];  6 first-order TPT all-passes: v = G (u - s), y = v + s, s = y + v, u = 2 y - u;  out = u
+//   y[n] = (1 - mix) x[n] + mix out
+// Pass 1 (coalesced): the coefficient stream G[m] of every row, evaluated in fp64 and rounded to fp32.  Pass 2: one LANE per row
+// walks the one-sample feedback loop (a linear but time-varying recurrence); like the compressor envelope, the loads of 32
+// samples and their 8 coefficients are issued ahead of the chain.  Rows are padded to a multiple of 8 coefficients.
+__global__ __launch_bounds__(256) void fx_phaser_coef_kernel(float* __restrict__ G, int64_t M, int64_t Mpad, float sr,
+                                                             const float* __restrict__ rate, const float* __restrict__ depth,
+                                                             const float* __restrict__ centre) {
+  const int b = blockIdx.y;
+  const double pi = 3.14159265358979323846;
+  const double fhi = fmin(20000.0, 0.49 * (double)sr), lmin = log10(20.0), lmax = log10(fhi);
+  const double nc = (log10((double)centre[b]) - lmin) / (lmax - lmin);
+  const double winc = 2.0 * pi * (double)rate[b] / ((double)sr / 4.0), dep = 0.5 * (double)depth[b];
+  float* gr = G + (int64_t)b * Mpad;
+  for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
+    double ph = winc * (double)m;
+    ph -= floor(ph * (0.5 / pi)) * (2.0 * pi);
+    const double v = fmin(fmax(sin(ph - pi) * dep + nc, 0.0), 1.0);
+    const double g = tan(pi * (20.0 * pow(fhi / 20.0, v)) / (double)sr);
+    gr[m] = (float)(g / (1.0 + g));
+  }
+}
+__device__ __forceinline__ float fx_phaser_step(float xv, float g, float (&s)[6], float& last, float fb, float mix, float dry) {
+  float u = xv - last;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const float v = g * (u - s[k]);
+    const float yk = v + s[k];
+    s[k] = yk + v;
+    u = 2.0f * yk - u;
+  }
+  last = u * fb;
+  return u * mix + xv * dry;
+}
+__global__ __launch_bounds__(64) void fx_phaser_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ G,
+                                                       int B, int64_t T, int64_t Mpad, const float* __restrict__ fb,
+                                                       const float* __restrict__ mix) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const float f = fb[b], m = mix[b], dry = 1.0f - m;
+  const float* xr = x + (int64_t)b * T;
+  const float* gr = G + (int64_t)b * Mpad;
+  float* yr = y + (int64_t)b * T;
+  float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float last = 0.f;
+  int64_t n = 0;
+  for (; n + 32 <= T; n += 32) {
+    f32x4 v[8], g[2];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = rfx_ld4(xr + n + 4 * q);
+    g[0] = rfx_ld4(gr + n / 4);
+    g[1] = rfx_ld4(gr + n / 4 + 4);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = fx_phaser_step(v[q][j], g[q >> 2][q & 3], s, last, f, m, dry);
+      rfx_st4(yr + n + 4 * q, o);
+    }
+  }
+  for (; n < T; ++n) yr[n] = fx_phaser_step(xr[n], gr[n / 4], s, last, f, m, dry);
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------
@@ -416,19 +649,85 @@ extern "C" int rfx_fx_reverb(const float* x, float* y, int32_t B, int64_t T, int
   RFX_CHECK_LAUNCH();
   return 0;
 }
-extern "C" int rfx_fx_loudness(const float* x, int32_t B, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
-                               double inv_block, const double* coef /* b1[3] a1[3] b2[3] a2[3] M[16] on the HOST */,
-                               float target_lufs, double* hop_ws, float* lufs, float* gain, void* stream) {
-  if (!x || !coef || !hop_ws || !lufs || !gain || B <= 0 || T <= 0 || chunk <= 0 || hop_len <= 0 || nhop < 4 || nblk < 1 ||
-      nblk + 3 > nhop || (int64_t)chunk * 64 < T) return -1;
+// B clips of C channels: the K-weighting runs over all B * C rows, the gate sums each clip's C rows of hop sums
+static int fx_loudness(const float* x, int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
+                       double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs, float* gain,
+                       void* stream) {
+  if (!x || !coef || !hop_ws || !lufs || !gain || B <= 0 || C <= 0 || (int64_t)B * C > 65535 || T <= 0 || chunk <= 0 ||
+      hop_len <= 0 || nhop < 4 || nblk < 1 || nblk + 3 > nhop || (int64_t)chunk * 64 < T) return -1;
   FxLoudArgs a{};
   a.x = x; a.hop = hop_ws; a.T = T; a.chunk = chunk; a.nhop = nhop; a.hop_len = hop_len; a.hop_of = nullptr;
   for (int i = 0; i < 3; ++i) { a.b1[i] = coef[i]; a.a1[i] = coef[3 + i]; a.b2[i] = coef[6 + i]; a.a2[i] = coef[9 + i]; }
   for (int i = 0; i < 16; ++i) a.M[i] = coef[12 + i];
-  if (hipMemsetAsync(hop_ws, 0, sizeof(double) * (size_t)B * nhop, (hipStream_t)stream) != hipSuccess) return -3;
-  hipLaunchKernelGGL(fx_kweight_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(fx_loud_gate_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, hop_ws, B, nhop, nblk, inv_block,
+  const int rows = B * C;
+  if (hipMemsetAsync(hop_ws, 0, sizeof(double) * (size_t)rows * nhop, (hipStream_t)stream) != hipSuccess) return -3;
+  hipLaunchKernelGGL(fx_kweight_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(fx_loud_gate_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, hop_ws, B, C, nhop, nblk, inv_block,
                      target_lufs, lufs, gain);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_fx_loudness(const float* x, int32_t B, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
+                               double inv_block, const double* coef /* b1[3] a1[3] b2[3] a2[3] M[16] on the HOST */,
+                               float target_lufs, double* hop_ws, float* lufs, float* gain, void* stream) {
+  return fx_loudness(x, B, 1, T, chunk, hop_len, nhop, nblk, inv_block, coef, target_lufs, hop_ws, lufs, gain, stream);
+}
+extern "C" int rfx_fx_loudness_joint(const float* x, int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop,
+                                     int32_t nblk, double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs,
+                                     float* gain, void* stream) {
+  return fx_loudness(x, B, C, T, chunk, hop_len, nhop, nblk, inv_block, coef, target_lufs, hop_ws, lufs, gain, stream);
+}
+extern "C" int rfx_fx_limiter(const float* x, float* y, float* ws, int32_t B, int64_t T, const float* params, void* stream) {
+  if (!fx_ok(x, y, B, T) || !ws || !params) return -1;
+  const float* p[9];
+  for (int i = 0; i < 9; ++i) p[i] = params + (size_t)i * B;   // thr1 ratio1 ca1 cr1 thr2 ratio2 ca2 cr2 makeup
+  float* env = ws;
+  float* y1 = ws + (size_t)B * T;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(fx_comp_env_kernel, dim3((B + 63) / 64), dim3(64), 0, s, x, env, B, T, p[2], p[3]);
+  hipLaunchKernelGGL(fx_comp_gain_kernel, fx_grid(T, B, 256), dim3(256), 0, s, x, env, y1, T, p[0], p[1]);
+  hipLaunchKernelGGL(fx_comp_env_kernel, dim3((B + 63) / 64), dim3(64), 0, s, y1, env, B, T, p[6], p[7]);
+  hipLaunchKernelGGL(fx_limit_out_kernel, fx_grid(T, B, 256), dim3(256), 0, s, y1, env, y, T, p[4], p[5], p[8]);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_fx_eq(const float* x, float* y, int32_t B, int64_t T, int32_t nsec, int32_t chunk, const double* coef, void* stream) {
+  if (!fx_ok(x, y, B, T) || !coef || chunk <= 0 || (int64_t)chunk * 64 < T) return -1;
+  const hipStream_t s = (hipStream_t)stream;
+  switch (nsec) {
+    case 2: hipLaunchKernelGGL(fx_eq_kernel<2>, dim3(B), dim3(64), 0, s, x, y, T, chunk, coef); break;
+    case 3: hipLaunchKernelGGL(fx_eq_kernel<3>, dim3(B), dim3(64), 0, s, x, y, T, chunk, coef); break;
+    case 4: hipLaunchKernelGGL(fx_eq_kernel<4>, dim3(B), dim3(64), 0, s, x, y, T, chunk, coef); break;
+    case 5: hipLaunchKernelGGL(fx_eq_kernel<5>, dim3(B), dim3(64), 0, s, x, y, T, chunk, coef); break;
+    case 6: hipLaunchKernelGGL(fx_eq_kernel<6>, dim3(B), dim3(64), 0, s, x, y, T, chunk, coef); break;
+    case 7: hipLaunchKernelGGL(fx_eq_kernel<7>, dim3(B), dim3(64), 0, s, x, y, T, chunk, coef); break;
+    case FX_EQ_MAX_NS: hipLaunchKernelGGL(fx_eq_kernel<FX_EQ_MAX_NS>, dim3(B), dim3(64), 0, s, x, y, T, chunk, coef); break;
+    default: return -1;
+  }
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_fx_widener(const float* x, float* y, int32_t B, int64_t T, const float* g_mid, const float* g_side, void* stream) {
+  if (!fx_ok(x, y, B, T) || !g_mid || !g_side) return -1;
+  hipLaunchKernelGGL(fx_widener_kernel, fx_grid(T, B, 1024), dim3(256), 0, (hipStream_t)stream, x, y, T, g_mid, g_side);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_fx_volume(float* x, int32_t B, int64_t T, int32_t S, const int32_t* seg_end, const float* db_start,
+                             const float* db_end, void* stream) {
+  if (!fx_ok(x, x, B, T) || !seg_end || !db_start || !db_end || S < 1 || S > FX_VOL_MAXSEG) return -1;
+  hipLaunchKernelGGL(fx_volume_kernel, fx_grid(T, B, 256), dim3(256), 0, (hipStream_t)stream, x, T, S, seg_end, db_start, db_end);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int64_t rfx_fx_phaser_ws_floats(int32_t B, int64_t T) { return (int64_t)B * ((((T + 3) / 4) + 7) / 8 * 8); }
+extern "C" int rfx_fx_phaser(const float* x, float* y, float* ws, int32_t B, int64_t T, float sample_rate, const float* rate_hz,
+                             const float* depth, const float* centre_hz, const float* feedback, const float* mix, void* stream) {
+  if (!fx_ok(x, y, B, T) || !ws || !rate_hz || !depth || !centre_hz || !feedback || !mix || sample_rate <= 0.f) return -1;
+  const int64_t M = (T + 3) / 4, Mpad = (M + 7) / 8 * 8;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(fx_phaser_coef_kernel, fx_grid(M, B, 256), dim3(256), 0, s, ws, M, Mpad, sample_rate, rate_hz, depth, centre_hz);
+  hipLaunchKernelGGL(fx_phaser_kernel, dim3((B + 63) / 64), dim3(64), 0, s, x, y, ws, B, T, Mpad, feedback, mix);
   RFX_CHECK_LAUNCH();
   return 0;
 }

@@ -165,6 +165,11 @@ class RandomPedalboardDistortion(_RandomEffect):
         return y
 
 
+def _ballistics_cte(ms, sample_rate):
+    """juce::dsp::BallisticsFilter coefficient of an attack / release time."""
+    return 0.0 if ms < 1e-3 else math.exp(-2.0 * math.pi * 1000.0 / float(sample_rate) / ms)
+
+
 class RandomPedalboardCompressor(_RandomEffect):
     defaults = dict(min_threshold_db=-42.0, max_threshold_db=-6.0, min_ratio=1.5, max_ratio=4.0, min_attack_ms=1.0,
                     max_attack_ms=50.0, min_release_ms=10.0, max_release_ms=250.0)
@@ -175,8 +180,7 @@ class RandomPedalboardCompressor(_RandomEffect):
 
     def render(self, clips, params):
         dev = clips.device
-        ef = -2.0 * math.pi * 1000.0 / float(self.sample_rate)                       # juce::dsp::BallisticsFilter
-        cte = lambda ms: 0.0 if ms < 1e-3 else math.exp(ef / ms)
+        cte = lambda ms: _ballistics_cte(ms, self.sample_rate)
         thr = _vec([10.0 ** (p["threshold_db"] / 20.0) for p in params], dev)
         ratio = _vec([p["ratio"] for p in params], dev)
         ca, cr = _vec([cte(p["attack_ms"]) for p in params], dev), _vec([cte(p["release_ms"]) for p in params], dev)
@@ -205,19 +209,29 @@ def _k_weighting(rate):
     return coef(4.0, 1.0 / np.sqrt(2.0), 1500.0, True), coef(0.0, 0.5, 38.0, False)
 
 
-def _transition(b1, a1, b2, a2, steps):
-    """Zero-input state transition over `steps` samples of the two cascaded biquads in transposed direct form II
-    (states s1a, s1b, s2a, s2b): y1 = s1a, s1a' = -a1[1] y1 + s1b, s1b' = -a1[2] y1; y2 = b2[0] y1 + s2a, ..."""
-    A = np.zeros((4, 4))
-    A[0, 0], A[0, 1], A[1, 0] = -a1[1], 1.0, -a1[2]
-    # y2 = b2[0] * s1a + s2a
-    A[2, 0], A[2, 2], A[2, 3] = b2[1] - a2[1] * b2[0], -a2[1], 1.0
-    A[3, 0], A[3, 2] = b2[2] - a2[2] * b2[0], -a2[2]
+def _transition(sections, steps):
+    """Zero-input state transition over `steps` samples of biquads (b, a) in series, transposed direct form II, states
+    (s_0a, s_0b, s_1a, ...): y_k = b_k[0] y_(k-1) + s_ka, s_ka' = b_k[1] y_(k-1) - a_k[1] y_k + s_kb, s_kb' = b_k[2] y_(k-1) - a_k[2] y_k
+    with y_(-1) = 0 (no input).  Every y_k is carried as a row of coefficients over the states."""
+    D = 2 * len(sections)
+    A = np.zeros((D, D))
+    y = np.zeros(D)
+    for k, (b, a) in enumerate(sections):
+        ea, eb = np.zeros(D), np.zeros(D)
+        ea[2 * k], eb[2 * k + 1] = 1.0, 1.0
+        yk = b[0] * y + ea
+        A[2 * k] = b[1] * y - a[1] * yk + eb
+        A[2 * k + 1] = b[2] * y - a[2] * yk
+        y = yk
     return np.linalg.matrix_power(A, int(steps))
 
 
 class LoudnessNormalize(torch.nn.Module):
-    """effects.py:619-629: scale to `target_lufs_db` by the BS.1770 integrated loudness (pyloudnorm.Meter)."""
+    """effects.py:619-629: scale to `target_lufs_db` by the BS.1770 integrated loudness (pyloudnorm.Meter).
+
+    A ``(C, T)`` clip with C > 1 is measured jointly, as pyloudnorm measures a multichannel clip (block power = sum of the
+    channels' mean squares) and scaled by one gain.  Known difference: a ``(B, C, T)`` batch is measured and scaled row by
+    row, every channel on its own."""
 
     def __init__(self, sample_rate: float, target_lufs_db: float = -32.0) -> None:
         super().__init__()
@@ -238,7 +252,7 @@ class LoudnessNormalize(torch.nn.Module):
                     raise NotImplementedError(f"loudness blocks are not multiples of a 100 ms hop at {rate} Hz")
             chunk = -(-T // 64)
             (b1, a1), (b2, a2) = _k_weighting(rate)
-            M = _transition(b1, a1, b2, a2, chunk)
+            M = _transition([(b1, a1), (b2, a2)], chunk)
             coef = np.concatenate([b1, a1, b2, a2, M.reshape(-1)]).astype(np.float64)
             p = dict(nblk=nblk, hop=hop, nhop=nblk + 3, chunk=chunk, coef=coef, inv=1.0 / (T_g * rate))
             self._cache[T] = p
@@ -257,14 +271,318 @@ class LoudnessNormalize(torch.nn.Module):
                                          _ptr(gain), _stream()), "rfx_fx_loudness")
         return lufs, gain
 
+    def measure_joint(self, clips):
+        """(B, C, T) device clips -> (lufs (B,), gain (B,)): every clip's C channels measured together."""
+        B, Ch, T = clips.shape
+        p = self._plan(T)
+        hop_ws = torch.empty((B * Ch, p["nhop"]), device=clips.device, dtype=torch.float64)
+        lufs = torch.empty(B, device=clips.device, dtype=torch.float32)
+        gain = torch.empty_like(lufs)
+        check(_lib.lib().rfx_fx_loudness_joint(_ptr(clips), B, Ch, T, p["chunk"], p["hop"], p["nhop"], p["nblk"], p["inv"],
+                                               p["coef"].ctypes.data_as(C.c_void_p), float(self.target_lufs_db), _ptr(hop_ws),
+                                               _ptr(lufs), _ptr(gain), _stream()), "rfx_fx_loudness_joint")
+        return lufs, gain
+
     def forward(self, x: torch.Tensor):
         clips, restore = _as_clips(x)
         if x.dim() == 2 and x.shape[0] != 1:
-            raise NotImplementedError("LoudnessNormalize: mono clips (the reference sums to mono before its effects)")
-        _, gain = self.measure(clips)
+            _, gain = self.measure_joint(clips.view(1, *clips.shape))
+            gain = gain.expand(clips.shape[0]).contiguous()
+        else:
+            _, gain = self.measure(clips)
         y = torch.empty_like(clips)
         check(_lib.lib().rfx_fx_scale(_ptr(clips), _ptr(y), clips.shape[0], clips.shape[1], _ptr(gain), _stream()), "rfx_fx_scale")
         return restore(y)
+
+
+_RBJ = {    # RBJ cookbook biquads as (b0, b1, b2, a0, a1, a2) of (A, cos w0, alpha, sqrt A)
+    "high_shelf": lambda A, c, al, sA: (A * ((A + 1) + (A - 1) * c + 2 * sA * al), -2 * A * ((A - 1) + (A + 1) * c),
+                                        A * ((A + 1) + (A - 1) * c - 2 * sA * al), (A + 1) - (A - 1) * c + 2 * sA * al,
+                                        2 * ((A - 1) - (A + 1) * c), (A + 1) - (A - 1) * c - 2 * sA * al),
+    "low_shelf": lambda A, c, al, sA: (A * ((A + 1) - (A - 1) * c + 2 * sA * al), 2 * A * ((A - 1) - (A + 1) * c),
+                                       A * ((A + 1) - (A - 1) * c - 2 * sA * al), (A + 1) + (A - 1) * c + 2 * sA * al,
+                                       -2 * ((A - 1) + (A + 1) * c), (A + 1) + (A - 1) * c - 2 * sA * al),
+    "peaking": lambda A, c, al, sA: (1 + al * A, -2 * c, 1 - al * A, 1 + al / A, -2 * c, 1 - al / A),
+}
+
+
+def biqaud(gain_db: float, cutoff_freq: float, q_factor: float, sample_rate: float, filter_type: str):
+    """effects.py:37-91 (the reference's spelling): (b, a) float64 coefficients, normalised by a0, of a "low_shelf",
+    "high_shelf" or "peaking" biquad."""
+    A = 10 ** (gain_db / 40.0)
+    w0 = 2.0 * np.pi * (cutoff_freq / sample_rate)
+    alpha = np.sin(w0) / (2.0 * q_factor)
+    b0, b1, b2, a0, a1, a2 = _RBJ[filter_type](A, np.cos(w0), alpha, np.sqrt(A))
+    return np.array([b0, b1, b2]) / a0, np.array([a0, a1, a2]) / a0
+
+
+def _eq_sections(p, sample_rate):
+    """The biquads of one parametric_eq parameter set, in the reference's order: low shelf, bands, high shelf."""
+    secs = [biqaud(p["low_shelf_gain_db"], p["low_shelf_cutoff_freq"], p["low_shelf_q_factor"], sample_rate, "low_shelf")]
+    secs += [biqaud(g, f, q, sample_rate, "peaking")
+             for g, f, q in zip(p["band_gains_db"], p["band_cutoff_freqs"], p["band_q_factors"])]
+    secs.append(biqaud(p["high_shelf_gain_db"], p["high_shelf_cutoff_freq"], p["high_shelf_q_factor"], sample_rate, "high_shelf"))
+    return secs
+
+
+def _eq_render(clips, params, sample_rate):
+    """(N, T) device clips, one parametric_eq parameter set per row -> (N, T): rfx_fx_eq with the per-row transition."""
+    N, T = clips.shape
+    chunk = -(-T // 64)
+    rows, done = [], {}
+    for p in params:
+        if id(p) not in done:
+            secs = _eq_sections(p, sample_rate)
+            if not 2 <= len(secs) <= 8:
+                raise ValueError(f"parametric EQ: 0 to 6 bands, got {len(secs) - 2}")
+            coef = [np.array([b[0], b[1], b[2], a[1], a[2]]) for b, a in secs]
+            done[id(p)] = (len(secs), np.concatenate(coef + [_transition(secs, chunk).reshape(-1)]))
+        rows.append(done[id(p)])
+    nsec = rows[0][0]
+    if any(n != nsec for n, _ in rows):
+        raise ValueError("parametric EQ: every clip of one launch needs the same number of bands")
+    coef = torch.from_numpy(np.stack([r for _, r in rows])).to(clips.device)
+    y = torch.empty_like(clips)
+    check(_lib.lib().rfx_fx_eq(_ptr(clips), _ptr(y), N, T, nsec, chunk, _ptr(coef), _stream()), "rfx_fx_eq")
+    return y
+
+
+def parametric_eq(x, sample_rate: float, low_shelf_gain_db: float = 0.0, low_shelf_cutoff_freq: float = 80.0,
+                  low_shelf_q_factor: float = 0.707, band_gains_db=(0.0,), band_cutoff_freqs=(300.0,), band_q_factors=(0.707,),
+                  high_shelf_gain_db: float = 0.0, high_shelf_cutoff_freq: float = 1000.0, high_shelf_q_factor: float = 0.707,
+                  dtype=np.float32):
+    """effects.py:94-150: low shelf -> bands -> high shelf along the last axis, rendered on the device in fp64.  A numpy array
+    (read as fp32) gives a numpy array of `dtype`; a CUDA tensor gives a CUDA fp32 tensor."""
+    assert len(band_gains_db) == len(band_cutoff_freqs) == len(band_q_factors)
+    p = dict(low_shelf_gain_db=low_shelf_gain_db, low_shelf_cutoff_freq=low_shelf_cutoff_freq, low_shelf_q_factor=low_shelf_q_factor,
+             band_gains_db=list(band_gains_db), band_cutoff_freqs=list(band_cutoff_freqs), band_q_factors=list(band_q_factors),
+             high_shelf_gain_db=high_shelf_gain_db, high_shelf_cutoff_freq=high_shelf_cutoff_freq,
+             high_shelf_q_factor=high_shelf_q_factor)
+    is_np = isinstance(x, np.ndarray)
+    t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda() if is_np else x
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise ValueError("remfx_amd.effects render on the GPU: pass a CUDA tensor or a numpy array (there is no CPU path)")
+    flat = t.reshape(-1, t.shape[-1]).to(torch.float32).contiguous()
+    y = _eq_render(flat, [p] * flat.shape[0], sample_rate).view(t.shape)
+    return y.cpu().numpy().astype(dtype) if is_np else y
+
+
+class RandomParametricEQ(_RandomEffect):
+    defaults = dict(num_bands=3, min_gain_db=-6.0, max_gain_db=6.0, min_cutoff_freq=1000.0, max_cutoff_freq=10000.0,
+                    min_q_factor=0.1, max_q_factor=4.0)
+
+    def draw(self):                                    # effects.py:182-198
+        p = dict(low_shelf_gain_db=rand(self.min_gain_db, self.max_gain_db), low_shelf_cutoff_freq=loguniform(20.0, 200.0),
+                 low_shelf_q_factor=rand(self.min_q_factor, self.max_q_factor))
+        p.update(high_shelf_gain_db=rand(self.min_gain_db, self.max_gain_db), high_shelf_cutoff_freq=loguniform(8000.0, 16000.0),
+                 high_shelf_q_factor=rand(self.min_q_factor, self.max_q_factor))
+        p.update(band_gains_db=[], band_cutoff_freqs=[], band_q_factors=[])
+        for _ in range(self.num_bands):
+            p["band_gains_db"].append(rand(self.min_gain_db, self.max_gain_db))
+            p["band_cutoff_freqs"].append(loguniform(self.min_cutoff_freq, self.max_cutoff_freq))
+            p["band_q_factors"].append(rand(self.min_q_factor, self.max_q_factor))
+        return p
+
+    def render(self, clips, params):
+        return _eq_render(clips, params, self.sample_rate)
+
+
+def _widener_gains(width):
+    """stereo_widener's mid / side factors, evaluated in the type of `width` like the reference's scalars."""
+    return 2 * (1 - width), 2 * width
+
+
+def _check_stereo(x):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        raise ValueError("remfx_amd.effects render on the GPU: pass a CUDA tensor (there is no CPU path)")
+    if x.dim() not in (2, 3) or x.shape[-2] != 2:
+        raise ValueError(f"the stereo widener takes (2, samples) or (batch, 2, samples), got {tuple(x.shape)}")
+
+
+def stereo_widener(x: torch.Tensor, width):
+    """effects.py:217-235 on the device: x (2, T) or (B, 2, T) CUDA, width a number or one per clip.  Returns a new tensor."""
+    _check_stereo(x)
+    flat = x.reshape(-1, x.shape[-1]).to(torch.float32).contiguous()
+    widths = list(width) if isinstance(width, (list, tuple)) else [width] * (flat.shape[0] // 2)
+    return _widener_render(flat, widths).view(x.shape)
+
+
+def _widener_render(rows, widths):
+    g = [_widener_gains(w) for w in widths]
+    gm, gs = _vec([a for a, _ in g], rows.device), _vec([b for _, b in g], rows.device)
+    y = torch.empty_like(rows)
+    check(_lib.lib().rfx_fx_widener(_ptr(rows), _ptr(y), rows.shape[0] // 2, rows.shape[1], _ptr(gm), _ptr(gs), _stream()),
+          "rfx_fx_widener")
+    return y
+
+
+class RandomStereoWidener(_RandomEffect):
+    """effects.py:238-252.  Stereo only: any other channel count raises ValueError (upstream: IndexError for mono, channels
+    beyond two silently dropped)."""
+    defaults = dict(min_width=0.0, max_width=1.0)
+
+    def draw(self):                                    # effects.py:251
+        return dict(width=rand(self.min_width, self.max_width))
+
+    def render(self, clips, params):
+        """clips: (2 N, T), rows 2i and 2i + 1 = left and right of clip i."""
+        if clips.shape[0] % 2:
+            raise ValueError("the stereo widener renders (left, right) row pairs")
+        return _widener_render(clips, [p["width"] for p in params[::2]])
+
+    def forward(self, x: torch.Tensor):
+        _check_stereo(x)
+        return super().forward(x)
+
+
+class RandomVolumeAutomation(_RandomEffect):
+    """effects.py:255-294: piecewise-linear dB ramps over Dirichlet-drawn segments.  Like upstream, ``forward`` scales ``x`` IN
+    PLACE and returns it."""
+    defaults = dict(min_segments=1, max_segments=3, min_gain_db=-6.0, max_gain_db=6.0)
+
+    def draw(self, T):                                 # effects.py:274-291
+        n = randint(self.min_segments, self.max_segments)
+        lengths = (T * np.random.dirichlet([rand(0, 10) for _ in range(n)], 1)).astype("int")[0]
+        gains = [rand(self.min_gain_db, self.max_gain_db) for _ in range(n)]
+        return dict(num_segments=int(n), segment_lengths=[int(v) for v in lengths], end_gains_db=gains)
+
+    def render(self, clips, params):
+        """Scales the (N, T) fp32 clips in place and returns them."""
+        S = max(p["num_segments"] for p in params)
+        if S > 64:
+            raise ValueError("volume automation: at most 64 segments")
+        ends, d0, d1 = [], [], []
+        for p in params:
+            e = np.cumsum(p["segment_lengths"]).tolist()
+            g = list(p["end_gains_db"])
+            pad = S - len(e)                           # zero-length segments after the last one
+            ends += e + [e[-1]] * pad
+            d0 += [0.0] + g[:-1] + [0.0] * pad
+            d1 += g + [0.0] * pad
+        dev = clips.device
+        # held until the launch is queued: a freed block would be handed to the next _vec
+        ends, d0, d1 = _vec(ends, dev, torch.int32), _vec(d0, dev), _vec(d1, dev)
+        check(_lib.lib().rfx_fx_volume(_ptr(clips), clips.shape[0], clips.shape[1], S, _ptr(ends), _ptr(d0), _ptr(d1), _stream()),
+              "rfx_fx_volume")
+        return clips
+
+    def forward(self, x: torch.Tensor):
+        clips, _ = _as_clips(x)
+        nsets = x.shape[0] if x.dim() == 3 else 1
+        sets = [self.draw(x.shape[-1]) for _ in range(nsets)]
+        per = clips.shape[0] // nsets
+        self.last_params = sets
+        self.render(clips, [s for s in sets for _ in range(per)])
+        if clips.data_ptr() != x.data_ptr():
+            x.copy_(clips.view(x.shape))
+        return x
+
+
+class RandomPedalboardPhaser(_RandomEffect):
+    defaults = dict(min_rate_hz=0.25, max_rate_hz=5.0, min_depth=0.1, max_depth=0.6, min_centre_frequency_hz=200.0,
+                    max_centre_frequency_hz=600.0, min_feedback=0.1, max_feedback=0.6, min_mix=0.1, max_mix=0.7)
+
+    def draw(self):                                    # effects.py:448-454; the centre draw spans (min, min) upstream
+        return dict(rate_hz=rand(self.min_rate_hz, self.max_rate_hz), depth=rand(self.min_depth, self.max_depth),
+                    centre_frequency_hz=rand(self.min_centre_frequency_hz, self.min_centre_frequency_hz),
+                    feedback=rand(self.min_feedback, self.max_feedback), mix=rand(self.min_mix, self.max_mix))
+
+    def render(self, clips, params):
+        dev = clips.device
+        N, T = clips.shape
+        v = {k: _vec([p[k] for p in params], dev) for k in ("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix")}
+        L = _lib.lib()
+        ws = torch.empty(int(L.rfx_fx_phaser_ws_floats(N, T)), device=dev, dtype=torch.float32)
+        y = torch.empty_like(clips)
+        check(L.rfx_fx_phaser(_ptr(clips), _ptr(y), _ptr(ws), N, T, float(self.sample_rate), _ptr(v["rate_hz"]), _ptr(v["depth"]),
+                              _ptr(v["centre_frequency_hz"]), _ptr(v["feedback"]), _ptr(v["mix"]), _stream()), "rfx_fx_phaser")
+        return y
+
+
+class RandomPedalboardLimiter(_RandomEffect):
+    defaults = dict(min_threshold_db=-32.0, max_threshold_db=-6.0, min_release_ms=10.0, max_release_ms=300.0)
+
+    def draw(self):                                    # effects.py:486-487
+        return dict(threshold_db=rand(self.min_threshold_db, self.max_threshold_db),
+                    release_ms=rand(self.min_release_ms, self.max_release_ms))
+
+    def stages(self, p):
+        """juce::dsp::Limiter::update: the two compressor stages' parameters and the make-up gain of one draw."""
+        makeup = min(10.0 ** (10.0 * (1.0 - 1.0 / 4.0) / 40.0), 10.0 ** (-p["threshold_db"] / 20.0))
+        return (dict(threshold_db=-10.0, ratio=4.0, attack_ms=2.0, release_ms=200.0),
+                dict(threshold_db=p["threshold_db"], ratio=1000.0, attack_ms=0.001, release_ms=p["release_ms"]), makeup)
+
+    def render(self, clips, params):
+        N, T = clips.shape
+        cols = []
+        for p in params:
+            s1, s2, makeup = self.stages(p)
+            col = []
+            for s in (s1, s2):
+                col += [10.0 ** (s["threshold_db"] / 20.0), s["ratio"], _ballistics_cte(s["attack_ms"], self.sample_rate),
+                        _ballistics_cte(s["release_ms"], self.sample_rate)]
+            cols.append(col + [makeup])
+        prm = _vec(np.asarray(cols).T.copy(), clips.device)
+        ws = torch.empty((2, N, T), device=clips.device, dtype=torch.float32)
+        y = torch.empty_like(clips)
+        check(_lib.lib().rfx_fx_limiter(_ptr(clips), _ptr(y), _ptr(ws), N, T, _ptr(prm), _stream()), "rfx_fx_limiter")
+        return y
+
+
+class RandomAudioEffectsChannel(torch.nn.Module):
+    """effects.py:632-696: the reference's augmentation chain on stereo clips -- ten stages, each applied with its probability
+    (torchvision RandomApply: skipped when p < torch.rand(1)), then LoudnessNormalize measured jointly over both channels.
+
+    ``forward`` takes ``(2, T)`` or ``(B, 2, T)`` CUDA tensors and returns a new tensor.  Draws go clip by clip, so a batch equals
+    B successive single-clip calls under the same seed; each stage then renders in ONE launch over the clips that drew it."""
+
+    def __init__(self, sample_rate: float, parametric_eq_prob: float = 0.7, distortion_prob: float = 0.01, delay_prob: float = 0.1,
+                 chorus_prob: float = 0.01, phaser_prob: float = 0.01, compressor_prob: float = 0.4, reverb_prob: float = 0.2,
+                 stereo_widener_prob: float = 0.3, limiter_prob: float = 0.3, vol_automation_prob: float = 0.7,
+                 target_lufs_db: float = -32.0) -> None:
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.stages = [(RandomParametricEQ(sample_rate), parametric_eq_prob), (RandomPedalboardDistortion(sample_rate), distortion_prob),
+                       (RandomPedalboardDelay(sample_rate), delay_prob), (RandomPedalboardChorus(sample_rate), chorus_prob),
+                       (RandomPedalboardPhaser(sample_rate), phaser_prob), (RandomPedalboardCompressor(sample_rate), compressor_prob),
+                       (RandomPedalboardReverb(sample_rate), reverb_prob), (RandomStereoWidener(sample_rate), stereo_widener_prob),
+                       (RandomPedalboardLimiter(sample_rate), limiter_prob), (RandomVolumeAutomation(sample_rate), vol_automation_prob)]
+        self.normalize = LoudnessNormalize(sample_rate, target_lufs_db=target_lufs_db)
+
+    def plan(self, B, T):
+        """The host-side draws of B clips of T samples: per clip, the (stage class name, parameters) that fire, in order."""
+        out = []
+        for _ in range(B):
+            fired = []
+            for fx, p in self.stages:
+                if p < torch.rand(1):
+                    continue
+                fired.append((type(fx).__name__, fx.draw(T) if isinstance(fx, RandomVolumeAutomation) else fx.draw()))
+            out.append(fired)
+        return out
+
+    def forward(self, x: torch.Tensor):
+        _check_stereo(x)
+        B, Ch, T = (1,) + tuple(x.shape) if x.dim() == 2 else tuple(x.shape)
+        plan = self.plan(B, T)
+        self.last_plan = plan
+        y = x.reshape(B * Ch, T).to(torch.float32).clone()
+        for fx, _ in self.stages:
+            name = type(fx).__name__
+            sel = [(b, prm) for b, fired in enumerate(plan) for n, prm in fired if n == name]
+            if not sel:
+                continue
+            params = [prm for _, prm in sel for _ in range(Ch)]
+            if len(sel) == B:
+                y = fx.render(y, params)
+            else:
+                idx = torch.tensor([b * Ch + c for b, _ in sel for c in range(Ch)], device=y.device)
+                y.index_copy_(0, idx, fx.render(y.index_select(0, idx), params))
+        _, gain = self.normalize.measure_joint(y.view(B, Ch, T))
+        gain = gain.repeat_interleave(Ch)
+        out = torch.empty_like(y)
+        check(_lib.lib().rfx_fx_scale(_ptr(y), _ptr(out), B * Ch, T, _ptr(gain), _stream()), "rfx_fx_scale")
+        return out.view(x.shape)
 
 
 # label order: column k of dry / wet label tensors (effects.py:699-707)
