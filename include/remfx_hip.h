@@ -427,6 +427,18 @@ int rfx_fx_volume(float* x, int32_t B, int64_t T, int32_t S, const int32_t* seg_
 int64_t rfx_fx_phaser_ws_floats(int32_t B, int64_t T);
 int rfx_fx_phaser(const float* x, float* y, float* ws, int32_t B, int64_t T, float sample_rate, const float* rate_hz, const float* depth,
                   const float* centre_hz, const float* feedback, const float* mix, void* stream);
+/* RandomSoxReverb.forward `effects.py:516-572`: SoX `reverb ... --wet-only` (two Freeverb banks per input channel, offsets 0 and
+ * stereo depth, geometry scaled by the room) and the wet / dry mix.  x: (B, Cin, T), Cin = 1 or 2; y: (B, 2, T), y != x;
+ * ws: rfx_fx_sox_reverb_ws_floats(B, Cin, T) floats.  One row per BANK, bank ((b Cin + c) 2 + w) = wet channel w of input channel c
+ * of clip b, all on the device:
+ *   geom: 16 int32 = pre-delay in samples, 8 comb lengths, 4 all-pass lengths (SoX's order), the row of x the bank reads
+ *         ((b Cin + c) here), 2 unused;
+ *   coef: 4 floats = comb feedback, damping, bank gain, wet_dry (read from the clip's first bank).
+ * lds_floats: the largest sum of a bank's twelve lengths (<= 40960: 160 KB of LDS), -1 beyond; a bank whose lengths exceed it or
+ * are below 1 renders NaN.  Banks with a length below 64 run in blocks of that length. */
+int64_t rfx_fx_sox_reverb_ws_floats(int32_t B, int32_t Cin, int64_t T);
+int rfx_fx_sox_reverb(const float* x, float* y, float* ws, int32_t B, int32_t Cin, int64_t T, const int32_t* geom, const float* coef,
+                      int32_t lds_floats, void* stream);
 
 /* ---- fused DConv depth-layer of the Hybrid Demucs frequency branch (bf16 arithmetic) ---------------------------------------
  * torchaudio HDemucs `_DConv` layer (reached from remfx/models.py:319): x_out = x + scale * GLU(GN(conv1x1(GELU(GN(conv3_dil(x))))))

@@ -254,6 +254,120 @@ __global__ __launch_bounds__(64) void fx_reverb_kernel(const FxReverbArgs a) {
   }
 }
 
+// ---- SoX `reverb` (RandomSoxReverb, effects.py:516-572): Freeverb banks with PER-BANK geometry, wet only, mono or stereo in, stereo out
+//   bank(in) = gain * allpass_0(allpass_1(allpass_2(allpass_3( sum_{j = 7..0} comb_j(in) ))));   in[n] = clip(x[n - delay], -1, 1)
+//   comb:    o = buf[p]; store = o + (store - o) damp; buf[p] = in + store * feedback; return o
+//   allpass: o = buf[p]; buf[p] = in + 0.5 o; return o - in
+//   wet[w] = clip(mean over the input channels of bank_w(channel));   y[w] = x[min(w, Cin - 1)] (1 - wet_dry) + wet[w] wet_dry
+// Room scale, stereo depth and pre-delay are drawn per clip, so the twelve lengths, the pre-delay and the input row of a bank come
+// from device memory (geom), as do feedback, damp, gain and wet_dry (coef).  One workgroup of one wave owns ONE bank (<= 55 KB of LDS
+// at 48 kHz): the 2 Cin banks of a clip run side by side and leave their wet signal in a workspace; fx_sox_mix_kernel then averages
+// the channels, clips, mixes with the dry signal and stores every output sample once.  The scheme inside a bank is fx_reverb_kernel's;
+// the block is narrowed to the bank's shortest lag where that is below 64 samples.  The pre-delay reads x[n - delay] from global memory.
+#define FX_SOX_GEOM 16       // int32 per bank: pre-delay, 8 comb lengths, 4 all-pass lengths, input row of x, 2 spare
+#define FX_SOX_COEF 4        // float per bank: feedback, damp, gain, wet_dry
+__global__ __launch_bounds__(64) void fx_sox_bank_kernel(const float* __restrict__ x, float* __restrict__ ws, int64_t T,
+                                                         const int32_t* __restrict__ geom, const float* __restrict__ coef,
+                                                         int lds_floats, int64_t x_rows) {
+  extern __shared__ float sox_arena[];
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int32_t* g = geom + (int64_t)r * FX_SOX_GEOM;
+  const float* cf = coef + (int64_t)r * FX_SOX_COEF;
+  float* wr = ws + (int64_t)r * T;
+  const int64_t delay = g[0], row = g[1 + FX_RV_NC + FX_RV_NA];
+  int clen[FX_RV_NC], alen[FX_RV_NA], coff[FX_RV_NC], aoff[FX_RV_NA];
+  int off = 0, blk = 64;
+  bool ok = delay >= 0 && row >= 0 && row < x_rows;
+#pragma unroll
+  for (int j = 0; j < FX_RV_NC; ++j) {
+    clen[j] = g[1 + j]; coff[j] = off;
+    ok = ok && clen[j] >= 1 && clen[j] <= lds_floats;        // bounded before it is summed: `off` cannot overflow
+    off += ok ? clen[j] : 0;
+    blk = clen[j] < blk ? clen[j] : blk;
+  }
+#pragma unroll
+  for (int j = 0; j < FX_RV_NA; ++j) {
+    alen[j] = g[1 + FX_RV_NC + j]; aoff[j] = off;
+    ok = ok && alen[j] >= 1 && alen[j] <= lds_floats;
+    off += ok ? alen[j] : 0;
+    blk = alen[j] < blk ? alen[j] : blk;
+  }
+  if (!ok || off > lds_floats) {                 // a plan the launch cannot hold: a loud result, never an access outside the arena
+    for (int64_t n = lane; n < T; n += 64) wr[n] = __builtin_nanf("");
+    return;
+  }
+  const float* xr = x + row * T;
+  const float fbk = cf[0], damp = cf[1], gain = cf[2];
+  for (int i = lane; i < off; i += 64) sox_arena[i] = 0.f;
+  float last[FX_RV_NC];
+  int cpos[FX_RV_NC], apos[FX_RV_NA];
+#pragma unroll
+  for (int j = 0; j < FX_RV_NC; ++j) { last[j] = 0.f; cpos[j] = 0; }
+#pragma unroll
+  for (int j = 0; j < FX_RV_NA; ++j) apos[j] = 0;
+  float dpw[6];
+  dpw[0] = damp;
+#pragma unroll
+  for (int s = 1; s < 6; ++s) dpw[s] = dpw[s - 1] * dpw[s - 1];
+  const float dl1 = powf(damp, (float)(lane + 1));
+  const bool in_blk = lane < blk;
+  __syncthreads();
+  for (int64_t n0 = 0; n0 < T; n0 += blk) {
+    const int64_t n = n0 + lane;
+    const bool act = in_blk && n < T;
+    const float in = act && n >= delay ? fminf(fmaxf(xr[n - delay], -1.0f), 1.0f) : 0.f;
+    float out = 0.f;
+#pragma unroll
+    for (int j = FX_RV_NC - 1; j >= 0; --j) {
+      float* buf = sox_arena + coff[j];
+      int idx = cpos[j] + lane;
+      idx -= idx >= clen[j] ? clen[j] : 0;
+      const float o = in_blk ? buf[idx] : 0.f;
+      // store[i] = (1 - damp) o[i] + damp store[i - 1]: inclusive weighted scan; lanes beyond the block hold zeros and feed no lane below
+      float v = (1.0f - damp) * o;
+#pragma unroll
+      for (int s = 0; s < 6; ++s) {
+        const float u = __shfl_up(v, 1 << s, 64);
+        if (lane >= (1 << s)) v = fmaf(dpw[s], u, v);
+      }
+      v = fmaf(dl1, last[j], v);
+      if (in_blk) buf[idx] = in + v * fbk;     // lanes beyond T store values (in = 0) that no sample below T reads back
+      last[j] = __shfl(v, blk - 1, 64);
+      cpos[j] += blk;
+      cpos[j] -= cpos[j] >= clen[j] ? clen[j] : 0;
+      out += o;
+    }
+#pragma unroll
+    for (int j = FX_RV_NA - 1; j >= 0; --j) {
+      float* buf = sox_arena + aoff[j];
+      int idx = apos[j] + lane;
+      idx -= idx >= alen[j] ? alen[j] : 0;
+      const float o = in_blk ? buf[idx] : 0.f;
+      if (in_blk) buf[idx] = out + 0.5f * o;
+      out = o - out;
+      apos[j] += blk;
+      apos[j] -= apos[j] >= alen[j] ? alen[j] : 0;
+    }
+    if (act) wr[n] = out * gain;
+  }
+}
+// y: (B, 2, T).  The banks of clip b are workspace rows ((b Cin + c) 2 + w); wet_dry is read from the clip's first bank.
+__global__ __launch_bounds__(256) void fx_sox_mix_kernel(const float* __restrict__ x, const float* __restrict__ ws, float* __restrict__ y,
+                                                         int Cin, int64_t T, const float* __restrict__ coef) {
+  const int b = blockIdx.y >> 1, w = blockIdx.y & 1;
+  const float wd = coef[(int64_t)b * Cin * 2 * FX_SOX_COEF + 3], dry = 1.0f - wd;
+  const float* xr = x + ((int64_t)b * Cin + (w < Cin ? w : Cin - 1)) * T;
+  const float* w0 = ws + ((int64_t)b * Cin * 2 + w) * T;
+  const float* w1 = w0 + 2 * T;
+  float* yr = y + ((int64_t)b * 2 + w) * T;
+  for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < T; n += (int64_t)gridDim.x * 256) {
+    float wet = w0[n];
+    if (Cin == 2) wet = 0.5f * (wet + w1[n]);
+    wet = wet > 1.0f ? 1.0f : (wet < -1.0f ? -1.0f : wet);            // a NaN (refused plan) stays a NaN
+    yr[n] = xr[n] * dry + wet * wd;
+  }
+}
+
 // ---- BS.1770 integrated loudness (pyloudnorm.Meter.integrated_loudness) + gain --------------------------------------
 // K-weighting = two biquads in series evaluated in fp64 (scipy.signal.lfilter on float64).  A 4th-order LINEAR recurrence:
 // the clip is cut into 64 chunks, one lane each.  Pass 1: every lane filters its chunk from a ZERO state and keeps the
@@ -646,6 +760,21 @@ extern "C" int rfx_fx_reverb(const float* x, float* y, int32_t B, int64_t T, int
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(fx_reverb_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
       hipSuccess) return -3;
   hipLaunchKernelGGL(fx_reverb_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, a);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int64_t rfx_fx_sox_reverb_ws_floats(int32_t B, int32_t Cin, int64_t T) { return (int64_t)B * Cin * 2 * T; }
+extern "C" int rfx_fx_sox_reverb(const float* x, float* y, float* ws, int32_t B, int32_t Cin, int64_t T, const int32_t* geom,
+                                 const float* coef, int32_t lds_floats, void* stream) {
+  if (!fx_ok(x, y, B, T) || !ws || !geom || !coef || x == y || (Cin != 1 && Cin != 2) || B > 32767 || lds_floats < FX_RV_NC + FX_RV_NA)
+    return -1;
+  const size_t lds = sizeof(float) * (size_t)lds_floats;
+  if (lds > 160 * 1024) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(fx_sox_bank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+      hipSuccess) return -3;
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(fx_sox_bank_kernel, dim3(B * Cin * 2), dim3(64), lds, s, x, ws, T, geom, coef, lds_floats, (int64_t)B * Cin);
+  hipLaunchKernelGGL(fx_sox_mix_kernel, fx_grid(T, 2 * B, 256), dim3(256), 0, s, x, ws, y, Cin, T, coef);
   RFX_CHECK_LAUNCH();
   return 0;
 }

@@ -113,6 +113,86 @@ class RandomPedalboardReverb(_RandomEffect):
         return y
 
 
+_SOX_COMBS = (1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617)       # SoX reverb.c: filter lengths at 44100 Hz
+_SOX_ALLPASSES = (225, 341, 441, 556)
+_SOX_LDS_FLOATS = 160 * 1024 // 4                                    # one bank's delay lines share a workgroup's LDS
+
+
+def sox_reverb_plan(params, sample_rate):
+    """SoX `reverb`'s derived quantities of ONE drawn parameter set (reverb.c: reverb_create / filter_array_create): the pre-delay
+    in samples, comb feedback, damping and bank gain as the C floats SoX keeps, and the 8 comb + 4 all-pass lengths of the two
+    banks (wet channel 0: offset 0; wet channel 1: offset stereo_depth / 100).  SoX reads each value as a double from the
+    reference's f-string, so a float32 draw counts with its printed digits."""
+    params = {k: float(f"{v}") for k, v in params.items()}
+    scale = params["room_scale"] / 100.0 * 0.9 + 0.1
+    depth = params["stereo_depth"] / 100.0
+    a = -1.0 / math.log(1.0 - 0.3)                      # reverberance 0 -> feedback 0.3
+    b = 100.0 / (math.log(1.0 - 0.98) * a + 1.0)        # reverberance 100 -> feedback 0.98
+    r = sample_rate * (1.0 / 44100.0)
+    combs = [[int(scale * r * (t + 12 * off) + 0.5) for t in _SOX_COMBS] for off in (0.0, depth)]
+    allpasses = [[int(r * (t + 12 * off) + 0.5) for t in _SOX_ALLPASSES] for off in (0.0, depth)]
+    return dict(delay=int(params["pre_delay"] / 1000.0 * sample_rate + 0.5),
+                feedback=float(np.float32(1.0 - math.exp((params["reverberance"] - b) / (a * b)))),
+                damp=float(np.float32(params["high_freq_damping"] / 100.0 * 0.3 + 0.2)), gain=float(np.float32(0.015)),
+                wet_dry=float(params["wet_dry"]), comb_lengths=combs, allpass_lengths=allpasses,
+                lds_floats=max(sum(c) + sum(p) for c, p in zip(combs, allpasses)),
+                min_lag=min(min(c + p) for c, p in zip(combs, allpasses)))
+
+
+class RandomSoxReverb(_RandomEffect):
+    """effects.py:516-572: SoX `reverb ... --wet-only` (restated from SoX's reverb.c, parity unpinned: csrc/fx.hip,
+    tests/sox_reverb_ref.py) and the wet / dry mix.  The one effect with a STEREO result: ``(1, T)`` or ``(2, T)`` -> ``(2, T)``,
+    ``(B, 1, T)`` or ``(B, 2, T)`` -> ``(B, 2, T)``, one parameter set per clip; a mono clip is the dry part of both channels."""
+    defaults = dict(min_reverberance=10.0, max_reverberance=100.0, min_high_freq_damping=0.0, max_high_freq_damping=100.0,
+                    min_wet_dry=0.0, max_wet_dry=1.0, min_room_scale=5.0, max_room_scale=100.0, min_stereo_depth=20.0,
+                    max_stereo_depth=100.0, min_pre_delay=0.0, max_pre_delay=100.0)
+
+    def draw(self):                                    # effects.py:549-554
+        return dict(reverberance=rand(self.min_reverberance, self.max_reverberance),
+                    high_freq_damping=rand(self.min_high_freq_damping, self.max_high_freq_damping),
+                    room_scale=rand(self.min_room_scale, self.max_room_scale),
+                    stereo_depth=rand(self.min_stereo_depth, self.max_stereo_depth),
+                    wet_dry=rand(self.min_wet_dry, self.max_wet_dry), pre_delay=rand(self.min_pre_delay, self.max_pre_delay))
+
+    def render(self, clips, params):
+        """clips: (B, Cin, T) device tensor, Cin = 1 or 2; params: list of B dicts (draw()).  Returns (B, 2, T)."""
+        B, Cin, T = clips.shape
+        geom, coef, lds = [], [], 0
+        for b, p in enumerate(params):
+            if not p["stereo_depth"] > 0:
+                raise ValueError("SoX reverb with stereo_depth 0 renders one wet channel: not modelled")
+            q = sox_reverb_plan(p, self.sample_rate)
+            if q["min_lag"] < 1 or q["lds_floats"] > _SOX_LDS_FLOATS or q["delay"] < 0:
+                raise ValueError(f"SoX reverb at {self.sample_rate} Hz, room_scale {p['room_scale']}: shortest filter lag "
+                                 f"{q['min_lag']} samples, {q['lds_floats']} samples of delay lines per bank (1 and {_SOX_LDS_FLOATS} "
+                                 f"are the limits), pre-delay {q['delay']}")
+            lds = max(lds, q["lds_floats"])
+            for c in range(Cin):
+                for w in range(2):
+                    geom.append([q["delay"]] + q["comb_lengths"][w] + q["allpass_lengths"][w] + [b * Cin + c, 0, 0])
+                    coef.append([q["feedback"], q["damp"], q["gain"], q["wet_dry"]])
+        dev = clips.device
+        geom, coef = _vec(geom, dev, torch.int32), _vec(coef, dev)
+        L = _lib.lib()
+        ws = torch.empty(int(L.rfx_fx_sox_reverb_ws_floats(B, Cin, T)), device=dev, dtype=torch.float32)
+        y = torch.empty((B, 2, T), device=dev, dtype=torch.float32)
+        check(L.rfx_fx_sox_reverb(_ptr(clips), _ptr(y), _ptr(ws), B, Cin, T, _ptr(geom), _ptr(coef), lds, _stream()),
+              "rfx_fx_sox_reverb")
+        return y
+
+    def forward(self, x: torch.Tensor):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise ValueError("remfx_amd.effects render on the GPU: pass a CUDA tensor (there is no CPU path)")
+        if x.dim() not in (2, 3) or x.shape[-2] not in (1, 2):
+            raise ValueError(f"the SoX reverb takes (1 or 2, samples) or (batch, 1 or 2, samples), got {tuple(x.shape)} "
+                             "(beyond two channels SoX drops the stereo depth: not modelled)")
+        clips = x.reshape(-1, x.shape[-2], x.shape[-1]).to(torch.float32).contiguous()
+        sets = [self.draw() for _ in range(clips.shape[0])]
+        self.last_params = sets
+        y = self.render(clips, sets)
+        return y if x.dim() == 3 else y[0]
+
+
 class RandomPedalboardChorus(_RandomEffect):
     defaults = dict(min_rate_hz=0.25, max_rate_hz=4.0, min_depth=0.0, max_depth=0.6, min_centre_delay_ms=5.0,
                     max_centre_delay_ms=10.0, min_feedback=0.1, max_feedback=0.6, min_mix=0.1, max_mix=0.7)

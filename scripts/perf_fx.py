@@ -65,6 +65,13 @@ def main():
     ln = E.LoudnessNormalize(SR)
     cases["loudness measure (existing)"] = (lambda: ln.measure(x), None)
     cases["loudness measure joint, 32 x 2"] = (lambda: ln.measure_joint(x.view(B // 2, 2, T)), None)
+    rv = E.RandomPedalboardReverb(SR)
+    pr = [rv.draw() for _ in range(B)]
+    cases["reverb (existing)"] = (lambda: rv.render(x, pr), None)                # 1 bank per clip
+    sx = E.RandomSoxReverb(SR)
+    ps = [sx.draw() for _ in range(B)]
+    cases["sox_reverb, 64 x 1 (128 banks)"] = (lambda: sx.render(x.view(B, 1, T), ps), None)
+    cases["sox_reverb, 32 x 2 (128 banks)"] = (lambda: sx.render(x.view(B // 2, 2, T), ps[:B // 2]), None)
     rows = []
     for name, (fn, nbytes) in cases.items():
         ms = _time(fn, a.reps)
