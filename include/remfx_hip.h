@@ -410,6 +410,15 @@ int rfx_fx_scale(const float* x, float* y, int32_t B, int64_t T, const float* ga
 int rfx_fx_loudness_joint(const float* x, int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
                           double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs, float* gain,
                           void* stream);
+/* The normalisation of one round of batched dataset rendering (remfx_amd/datasets.py process_effects_batch): a round applies
+ * effects to a SUBSET of the clips of a (N, T) state buffer y and leaves the results as n compact rows x (n, T), x outside y.
+ * rows: n int32 on the device, 0 <= rows[i] < N, no row twice (the caller's duty: the library cannot see N).
+ * rfx_fx_loudness over the n compact rows of x (n, T), then y[rows[i]] = gain[i] * x[i] (rows == NULL:
+ * y row i).  Every addressed row of y is stored exactly once, no other row is touched.  ws: rfx_fx_normalize_ws_bytes(n, nhop)
+ * bytes, 8-byte aligned: n * nhop doubles (hop sums), then lufs[n] and gain[n] as floats, readable after the call. */
+int64_t rfx_fx_normalize_ws_bytes(int32_t n, int32_t nhop);
+int rfx_fx_normalize_rows(const float* x, float* y, const int32_t* rows, int32_t n, int64_t T, int32_t chunk, int32_t hop_len,
+                          int32_t nhop, int32_t nblk, double inv_block, const double* coef, float target_lufs, void* ws, void* stream);
 /* The rest of remfx/effects.py: RandomPedalboardLimiter (:468-494), RandomParametricEQ (:37-214), RandomStereoWidener (:217-252),
  * RandomVolumeAutomation (:255-294), RandomPedalboardPhaser (:418-465).  Parameters per row unless stated.
  * limiter: ws = 2 * B * T floats; params = 9 x B floats on the device, rows thr1 ratio1 c_attack1 c_release1 (stage 1),

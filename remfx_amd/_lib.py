@@ -209,6 +209,8 @@ SIGNATURES = {
     "rfx_fx_phaser": [_P, _P, _P, _I32, _I64, C.c_float, _P, _P, _P, _P, _P, _P],
     "rfx_fx_sox_reverb_ws_floats": [_I32, _I32, _I64],
     "rfx_fx_sox_reverb": [_P, _P, _P, _I32, _I32, _I64, _P, _P, _I32, _P],
+    "rfx_fx_normalize_ws_bytes": [_I32, _I32],
+    "rfx_fx_normalize_rows": [_P, _P, _P, _I32, _I64, _I32, _I32, _I32, _I32, C.c_double, _P, C.c_float, _P, _P],
     "rfx_localstate_gen_fwd": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
     "rfx_localstate_gen_bwd": [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "rfx_mha_fwd": [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P],
@@ -254,7 +256,7 @@ SIGNATURES = {
 }
 
 _RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",
-          "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats"}
+          "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats", "rfx_fx_normalize_ws_bytes"}
 _lib = None
 
 

@@ -10,6 +10,10 @@
 // the image: parity unpinned, oracle/ref_effects.py is the same restatement in numpy float64).
 #include "common.h"
 
+// Row table of the round normalisation (rfx_fx_normalize_rows): output row i goes to row rows[i] of a larger state buffer;
+// rows == nullptr is the dense case (row i).
+__device__ __forceinline__ int64_t fx_row(const int32_t* __restrict__ rows, int b) { return rows ? (int64_t)rows[b] : (int64_t)b; }
+
 // ---- distortion: pedalboard.Distortion = JUCE Gain(drive_db) -> WaveShaper(tanh) ------------------------------------
 __global__ __launch_bounds__(256) void fx_distortion_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t T,
                                                             const float* __restrict__ gain) {
@@ -480,11 +484,11 @@ __global__ void fx_loud_gate_kernel(const double* __restrict__ hop, int B, int C
   gain[b] = powf(10.0f, d / 20.0f);
 }
 __global__ __launch_bounds__(256) void fx_scale_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t T,
-                                                       const float* __restrict__ gain) {
+                                                       const float* __restrict__ gain, const int32_t* __restrict__ rows) {
   const int b = blockIdx.y;
   const float g = gain[b];
   const float* xr = x + (int64_t)b * T;
-  float* yr = y + (int64_t)b * T;
+  float* yr = y + fx_row(rows, b) * T;          // gain[i] * x[i] -> y[rows[i]]
   for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < T; n += (int64_t)gridDim.x * 256) yr[n] = g * xr[n];
 }
 
@@ -862,7 +866,28 @@ extern "C" int rfx_fx_phaser(const float* x, float* y, float* ws, int32_t B, int
 }
 extern "C" int rfx_fx_scale(const float* x, float* y, int32_t B, int64_t T, const float* gain, void* stream) {
   if (!fx_ok(x, y, B, T) || !gain) return -1;
-  hipLaunchKernelGGL(fx_scale_kernel, fx_grid(T, B, 256), dim3(256), 0, (hipStream_t)stream, x, y, T, gain);
+  hipLaunchKernelGGL(fx_scale_kernel, fx_grid(T, B, 256), dim3(256), 0, (hipStream_t)stream, x, y, T, gain, nullptr);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+// The normalisation of a round of batched dataset rendering: measure the n compact rows of x (the K-weighting and gate kernels
+// above, unchanged), then store gain[i] * x[i] into row rows[i] of the (N, T) buffer y (device int32 table; the CALLER guarantees
+// 0 <= rows[i] < N and that no row occurs twice; rows == nullptr: row i).  Every addressed row of y is written exactly once, the
+// others are not touched.  ws: rfx_fx_normalize_ws_bytes(n, nhop) bytes = n * nhop hop sums (double), then lufs[n] and gain[n] (float), which
+// stay readable there after the call.
+extern "C" int64_t rfx_fx_normalize_ws_bytes(int32_t n, int32_t nhop) {
+  return (int64_t)n * nhop * (int64_t)sizeof(double) + 2 * (int64_t)n * (int64_t)sizeof(float);
+}
+extern "C" int rfx_fx_normalize_rows(const float* x, float* y, const int32_t* rows, int32_t n, int64_t T, int32_t chunk,
+                                     int32_t hop_len, int32_t nhop, int32_t nblk, double inv_block, const double* coef,
+                                     float target_lufs, void* ws, void* stream) {
+  if (!fx_ok(x, y, n, T) || !ws || (rows && x == y)) return -1;
+  double* hop_ws = (double*)ws;
+  float* lufs = (float*)(hop_ws + (size_t)n * (nhop > 0 ? nhop : 0));
+  float* gain = lufs + n;
+  const int rc = fx_loudness(x, n, 1, T, chunk, hop_len, nhop, nblk, inv_block, coef, target_lufs, hop_ws, lufs, gain, stream);
+  if (rc) return rc;
+  hipLaunchKernelGGL(fx_scale_kernel, fx_grid(T, n, 256), dim3(256), 0, (hipStream_t)stream, x, y, T, gain, rows);
   RFX_CHECK_LAUNCH();
   return 0;
 }

@@ -8,6 +8,9 @@ What the hot path consumes is the batch tuple  (x_wet, y_dry, dry_labels, wet_la
 reference, datasets.py:109-202, 267-318, 399-452) runs ON THE DEVICE here: `process_effects` applies the randomly chosen
 kept / removed effects and the in-between loudness normalisation through remfx_amd.effects (csrc/fx.hip), for
 `EffectDataset(render_files=True)` (writes the reference's layout) and `DynamicEffectDataset` (on-the-fly augmentation).
+With ``parallel=True`` both render B clips per launch: the host draws stay per clip and in the per-item order
+(`plan_effects`), the rendering goes by rounds over the batch (`process_effects_batch`), and the clips and labels are those
+of ``parallel=False`` bit for bit under the same seeds.
 
 The classes take the reference's constructor arguments, so ``cfg/config.yaml``'s datamodule node instantiates
 unchanged.  Multi-GPU: the loaders shard by rank with a DistributedSampler (what Lightning injects for the
@@ -30,6 +33,11 @@ def load_wav(path):
     PCM32 / float32 WAV files the reference writes with torchaudio.save (datasets.py:447-448)."""
     from scipy.io import wavfile
     sr, a = wavfile.read(str(path))
+    return _pcm_to_float(a), int(sr)
+
+
+def _pcm_to_float(a):
+    """(samples,) or (samples, channels) of a WAV file's own dtype -> (channels, samples) float32 tensor in [-1, 1)."""
     if a.ndim == 1:
         a = a[:, None]
     if a.dtype == np.int16:
@@ -40,7 +48,27 @@ def load_wav(path):
         x = (a.astype(np.float32) - 128.0) / 128.0
     else:
         x = a.astype(np.float32)
-    return torch.from_numpy(np.ascontiguousarray(x.T)), int(sr)
+    return torch.from_numpy(np.ascontiguousarray(x.T))
+
+
+def open_wav(path):
+    """The samples of a WAV file as scipy maps them, (samples,) or (samples, channels) in the file's own dtype and NOT yet
+    decoded, and the sample rate: `read_wav_chunk` converts only the slice it is asked for.  Files scipy cannot map
+    (24-bit PCM) are read whole."""
+    from scipy.io import wavfile
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", wavfile.WavFileWarning)
+        try:
+            sr, a = wavfile.read(str(path), mmap=True)
+        except ValueError:
+            sr, a = wavfile.read(str(path))
+    return a, int(sr)
+
+
+def read_wav_chunk(path, start, stop, _opened=None):
+    """``load_wav(path)[0][:, start:stop]`` without decoding the rest of the file."""
+    a = _opened if _opened is not None else open_wav(path)[0]
+    return _pcm_to_float(a[start:stop])
 
 
 def save_wav(path, x, sample_rate):
@@ -96,13 +124,13 @@ def locate_files(root, mode):
 def select_random_chunk(audio_file, chunk_size, sample_rate, device=None):
     """utils.py:120-135: a random chunk of `chunk_size` samples AT `sample_rate` from a file (None when the file is too
     short or the chunk is nearly silent); the resampling runs on the device (remfx_amd.resample)."""
-    audio, sr = load_wav(audio_file)
+    audio, sr = open_wav(audio_file)                            # mapped, not decoded: only the chunk is converted to float
     new_chunk_size = int(chunk_size * (sr / sample_rate))
-    if new_chunk_size >= audio.shape[-1]:
+    if new_chunk_size >= audio.shape[0]:
         return None
-    max_len = audio.shape[-1] - new_chunk_size
+    max_len = audio.shape[0] - new_chunk_size
     random_start = torch.randint(0, max_len, (1,)).item()
-    chunk = audio[:, random_start:random_start + new_chunk_size]
+    chunk = read_wav_chunk(audio_file, random_start, random_start + new_chunk_size, _opened=audio)
     if torch.mean(torch.abs(chunk)) < 1e-4:                     # skip if energy too low
         return None
     if device is not None:
@@ -141,6 +169,89 @@ def process_effects(dry, effects, effects_to_keep, effects_to_remove, num_kept_e
     for i in dry_labels:
         dry_labels_tensor[i] = 1.0
     return normalize(dry), normalize(wet), dry_labels_tensor, wet_labels_tensor
+
+
+def plan_effects(effects, effects_to_keep, effects_to_remove, num_kept_effects, num_removed_effects, shuffle_kept_effects,
+                 shuffle_removed_effects):
+    """The host-side draws of ONE clip, exactly the random calls `process_effects` makes and in its order (randperm if
+    shuffling, rand(1) for the count, one ``effect.draw()`` per chosen effect; kept phase first, then the removed phase), with
+    no device work: ``effect(x)`` draws and then renders, and rendering consumes no random numbers.
+    Returns (kept, removed, dry_labels (5,), wet_labels (5,)): kept / removed are the ordered [(name, params), ...]."""
+    from .effects import Pedalboard_Effects as ALL_EFFECTS
+    phases, labels = [], []
+    for names, (r1, r2), shuffle in ((effects_to_keep, num_kept_effects, shuffle_kept_effects),
+                                     (effects_to_remove, num_removed_effects, shuffle_removed_effects)):
+        idx = torch.randperm(len(names)) if shuffle else torch.arange(len(names))
+        n = torch.round((r1 - r2) * torch.rand(1) + r2).int()
+        chosen = [names[i] for i in idx[:n]]
+        phases.append([(name, effects[name].draw()) for name in chosen])
+        lab = torch.zeros(NUM_EFFECTS)
+        for name in chosen:
+            lab[ALL_EFFECTS.index(type(effects[name]))] = 1.0
+        labels.append(lab)
+    return phases[0], phases[1], labels[0], labels[1]
+
+
+def _render_rounds(state, seqs, base, effects, normalize, row_tables):
+    """Round k applies every clip's k-th effect: ONE render per effect name over the rows that drew it (gathered from the
+    state), then ONE normalisation over the round's rows, which is the only writer of the state -- every active row once
+    (through the row table: rfx_fx_normalize_rows), the others not at all.  seqs[b]: the [(name, params), ...] of state row
+    base + b."""
+    from .effects import row_table
+    for k in range(max((len(q) for q in seqs), default=0)):
+        groups = {}                                          # effect name -> (rows, params), names in order of first use
+        for b, q in enumerate(seqs):
+            if len(q) > k:
+                rows, params = groups.setdefault(q[k][0], ([], []))
+                rows.append(base + b)
+                params.append(q[k][1])
+        all_rows = [r for rows, _ in groups.values() for r in rows]
+        table = row_table(all_rows, state.shape[0], state.device)
+        idx, parts, off = table.long(), [], 0
+        for name, (rows, params) in groups.items():
+            parts.append(effects[name].render(state.index_select(0, idx[off:off + len(rows)]), params))
+            off += len(rows)
+        clips = parts[0] if len(parts) == 1 else torch.cat(parts)
+        if row_tables:
+            normalize.normalize_rows(clips, state, table)
+        else:                                                # measure, scale, scatter with torch (scripts/perf_render.py compares)
+            state.index_copy_(0, idx, normalize(clips.unsqueeze(1)).squeeze(1))
+
+
+def process_effects_batch(dry, plans, effects, normalize, row_tables=True):
+    """`process_effects` for B clips at once.  dry: (B, 1, T) on the device; plans: B results of `plan_effects`; effects: the
+    name -> effect object dict; normalize: a LoudnessNormalize.  The clips live in one (2 B, T) state (rows 0 .. B - 1 dry,
+    B .. 2 B - 1 wet): the kept phase runs by rounds on the dry rows, the wet rows start as their copy and take the removed
+    phase, and the two final normalisations are one measurement over the 2 B rows.  Launch counts follow the plan structure
+    (rounds x effect names), not B.  Returns (dry (B, 1, T), wet (B, 1, T), dry_labels (B, 5), wet_labels (B, 5)), the labels
+    on the host like `process_effects`' own; bit for bit what B successive `process_effects` calls give under the same draws."""
+    if not (isinstance(dry, torch.Tensor) and dry.is_cuda and dry.dim() == 3 and dry.shape[1] == 1):
+        raise ValueError("process_effects_batch takes a (B, 1, T) CUDA tensor (remfx_amd.effects has no CPU path)")
+    B, _, T = dry.shape
+    if len(plans) != B:
+        raise ValueError(f"{len(plans)} plans for {B} clips")
+    state = torch.empty((2 * B, T), device=dry.device, dtype=torch.float32)
+    state[:B] = dry.reshape(B, T)
+    _render_rounds(state, [p[0] for p in plans], 0, effects, normalize, row_tables)
+    state[B:] = state[:B]
+    _render_rounds(state, [p[1] for p in plans], B, effects, normalize, row_tables)
+    out = normalize.normalize_rows(state, torch.empty_like(state)) if row_tables else normalize(state.unsqueeze(1)).squeeze(1)
+    return (out[:B].unsqueeze(1), out[B:].unsqueeze(1), torch.stack([p[2] for p in plans]), torch.stack([p[3] for p in plans]))
+
+
+def render_clips(chunks, plans, effects, normalize, row_tables=True):
+    """`process_effects_batch` over a LIST of (1, T_i) clips: clips of one length form one sub-batch (source files of different
+    sample rates can resample to chunks that differ by a sample).  Returns a list of (dry, wet, dry_labels, wet_labels) per clip,
+    in input order."""
+    by_len, out = {}, [None] * len(chunks)
+    for i, c in enumerate(chunks):
+        by_len.setdefault(c.shape[-1], []).append(i)
+    for ids in by_len.values():
+        d, w, dl, wl = process_effects_batch(torch.stack([chunks[i] for i in ids]), [plans[i] for i in ids], effects, normalize,
+                                             row_tables)
+        for j, i in enumerate(ids):
+            out[i] = (d[j], w[j], dl[j], wl[j])
+    return out
 
 
 def _random_chunk(files, chunk_size, sample_rate, device):
@@ -187,7 +298,7 @@ class EffectDataset(Dataset):
     def __init__(self, root=None, sample_rate=48000, chunk_size=262144, total_chunks=1000, effect_modules=None,
                  effects_to_keep=None, effects_to_remove=None, num_kept_effects=(1, 5), num_removed_effects=(1, 5),
                  shuffle_kept_effects=True, shuffle_removed_effects=False, render_files=True, render_root=None,
-                 mode="train", parallel=False, device=None):
+                 mode="train", parallel=False, device=None, render_batch_size=64):
         super().__init__()
         self.root, self.sample_rate, self.chunk_size, self.total_chunks = root, sample_rate, chunk_size, total_chunks
         self.mode, self.effects = mode, effect_modules or {}
@@ -195,6 +306,9 @@ class EffectDataset(Dataset):
         self.effects_to_remove = [] if effects_to_remove is None else list(effects_to_remove)
         self.num_kept_effects, self.num_removed_effects = list(num_kept_effects), list(num_removed_effects)
         self.shuffle_kept_effects, self.shuffle_removed_effects = shuffle_kept_effects, shuffle_removed_effects
+        self.parallel, self.render_batch_size = bool(parallel), int(render_batch_size)
+        if self.render_batch_size < 1:
+            raise ValueError(f"render_batch_size must be at least 1, got {render_batch_size}")
         self.validate_effect_input()
         effects_string = "_".join(self.effects_to_keep + ["_"] + self.effects_to_remove + ["_"]
                                   + [str(x) for x in self.num_kept_effects] + ["_"]
@@ -263,6 +377,8 @@ class EffectDataset(Dataset):
             shutil.rmtree(self.proc_root)
         self.proc_root.mkdir(parents=True, exist_ok=True)
         normalize = LoudnessNormalize(self.sample_rate, target_lufs_db=-20)
+        if self.parallel:
+            return self._render_batched(files, dev, normalize)
         for num_chunk in range(self.total_chunks):
             chunk = _random_chunk(files, self.chunk_size, self.sample_rate, dev)
             dry, wet, dry_effects, wet_effects = process_effects(
@@ -274,6 +390,29 @@ class EffectDataset(Dataset):
             save_wav(d / "target.wav", dry, self.sample_rate)
             torch.save(dry_effects, d / "dry_effects.pt")
             torch.save(wet_effects, d / "wet_effects.pt")
+
+    def _render_batched(self, files, dev, normalize):
+        """parallel=True: the same clips as the loop above (per clip: choose the chunk, then draw the plan -- the order of the
+        per-item path), rendered `render_batch_size` at a time by rounds and copied to the host once per batch."""
+        for first in range(0, self.total_chunks, self.render_batch_size):
+            chunks, plans = [], []
+            for _ in range(first, min(first + self.render_batch_size, self.total_chunks)):
+                chunks.append(_random_chunk(files, self.chunk_size, self.sample_rate, dev))
+                plans.append(plan_effects(self.effects, self.effects_to_keep, self.effects_to_remove, self.num_kept_effects,
+                                          self.num_removed_effects, self.shuffle_kept_effects, self.shuffle_removed_effects))
+            done = render_clips(chunks, plans, self.effects, normalize)
+            if len({d.shape for d, _, _, _ in done}) == 1:      # one device-to-host copy for the batch
+                host = torch.stack([torch.stack((d, w)) for d, w, _, _ in done]).cpu()
+                audio = [(host[i, 0], host[i, 1]) for i in range(len(done))]
+            else:
+                audio = [(d.cpu(), w.cpu()) for d, w, _, _ in done]
+            for i, ((dry, wet), (_, _, dry_effects, wet_effects)) in enumerate(zip(audio, done)):
+                d = self.proc_root / str(first + i)
+                d.mkdir(exist_ok=True)
+                save_wav(d / "input.wav", wet, self.sample_rate)
+                save_wav(d / "target.wav", dry, self.sample_rate)
+                torch.save(dry_effects.clone(), d / "dry_effects.pt")
+                torch.save(wet_effects.clone(), d / "wet_effects.pt")
 
     def _rendered_chunks(self):
         if self.proc_root is None or not self.proc_root.is_dir():
@@ -327,7 +466,7 @@ class DynamicEffectDataset(Dataset):
         self.num_kept_effects, self.num_removed_effects = list(num_kept_effects), list(num_removed_effects)
         self.shuffle_kept_effects, self.shuffle_removed_effects = shuffle_kept_effects, shuffle_removed_effects
         self.normalize = LoudnessNormalize(sample_rate, target_lufs_db=-20)
-        self.device, self.renders_on_device = device, True
+        self.device, self.renders_on_device, self.parallel = device, True, bool(parallel)
         self.files = locate_files(root, mode) if _usable_dir(root) else []
         if not any(self.files):
             warnings.warn("DynamicEffectDataset: no corpus (DATASET_ROOT): effects are rendered over seeded white-noise chunks",
@@ -342,16 +481,49 @@ class DynamicEffectDataset(Dataset):
     def __len__(self):
         return self.total_chunks
 
-    def __getitem__(self, _):
+    def _chunk(self):
         if not torch.cuda.is_available():
             raise RuntimeError("DynamicEffectDataset renders on the GPU (remfx_amd.effects has no CPU path)")
         dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.files:
-            chunk = _random_chunk(self.files, self.chunk_size, self.sample_rate, dev)
-        else:
-            chunk = (torch.randn(1, self.chunk_size, generator=self._noise) * 0.1).to(dev)
-        dry, wet, dry_effects, wet_effects = self.process_effects(chunk)
+            return _random_chunk(self.files, self.chunk_size, self.sample_rate, dev)
+        return (torch.randn(1, self.chunk_size, generator=self._noise) * 0.1).to(dev)
+
+    def __getitem__(self, _):
+        dry, wet, dry_effects, wet_effects = self.process_effects(self._chunk())
         return wet, dry, dry_effects, wet_effects
+
+    def render_batch(self, n):
+        """One collated batch of n fresh items, (wet (n, 1, T), dry (n, 1, T), dry_labels (n, 5), wet_labels (n, 5)) on the
+        device: the clips and labels n successive ``__getitem__`` calls give under the same seeds (per clip: chunk, then the
+        draws), rendered by rounds with one launch per effect and round (`process_effects_batch`)."""
+        chunks, plans = [], []
+        for _ in range(int(n)):
+            chunks.append(self._chunk())
+            plans.append(plan_effects(self.effects, self.effects_to_keep, self.effects_to_remove, self.num_kept_effects,
+                                      self.num_removed_effects, self.shuffle_kept_effects, self.shuffle_removed_effects))
+        done = render_clips(chunks, plans, self.effects, self.normalize)
+        dev = chunks[0].device
+        return (torch.stack([w for _, w, _, _ in done]), torch.stack([d for d, _, _, _ in done]),
+                torch.stack([dl for _, _, dl, _ in done]).to(dev), torch.stack([wl for _, _, _, wl in done]).to(dev))
+
+
+class _RenderedBatches(Dataset):
+    """What `EffectDatamodule._dl` iterates for a DynamicEffectDataset(parallel=True): item i is the i-th collated batch of this
+    rank's share of the epoch, rendered on request.  The items are fresh random clips whatever the index, so no sampler or
+    shuffling is involved; under torch.distributed every rank renders ceil(len / world_size) clips, a DistributedSampler's share."""
+
+    def __init__(self, dataset, batch_size, world_size=1):
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self.clips = -(-len(dataset) // max(1, int(world_size)))
+
+    def __len__(self):
+        return -(-self.clips // self.batch_size)
+
+    def __getitem__(self, i):
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return self.dataset.render_batch(min(self.batch_size, self.clips - i * self.batch_size))
 
 
 class InferenceDataset(Dataset):
@@ -414,6 +586,10 @@ class EffectDatamodule:
 
     def _dl(self, ds, bs, shuffle):
         import torch.distributed as dist
+        if getattr(ds, "parallel", False) and hasattr(ds, "render_batch"):
+            # device-side batched rendering: the loader's items ARE the batches (no collation, main process only)
+            world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+            return DataLoader(_RenderedBatches(ds, bs, world), batch_size=None, shuffle=False, num_workers=0)
         sampler = None
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             sampler = torch.utils.data.distributed.DistributedSampler(ds, shuffle=shuffle)

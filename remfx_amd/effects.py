@@ -58,6 +58,15 @@ def _vec(vals, device, dtype=torch.float32):
     return torch.tensor(np.asarray(vals), dtype=dtype).to(device)
 
 
+def row_table(rows, nstate, device):
+    """A host sequence of row numbers -> the int32 device table rfx_fx_normalize_rows reads.  Checked HERE, on the host: the
+    kernel indexes the state buffer with these values and cannot see its size."""
+    rows = [int(r) for r in rows]
+    if not rows or min(rows) < 0 or max(rows) >= nstate or len(set(rows)) != len(rows):
+        raise ValueError(f"row table {rows}: needs distinct rows in [0, {nstate})")
+    return torch.tensor(rows, dtype=torch.int32).to(device)
+
+
 class _RandomEffect(torch.nn.Module):
     """Keeps every ``min_* / max_*`` range of the reference constructor.  ``draw()`` samples ONE parameter set with the
     reference's calls in the reference's order; ``forward`` draws one set per clip of a batch (one set for all channels of
@@ -362,6 +371,31 @@ class LoudnessNormalize(torch.nn.Module):
                                                p["coef"].ctypes.data_as(C.c_void_p), float(self.target_lufs_db), _ptr(hop_ws),
                                                _ptr(lufs), _ptr(gain), _stream()), "rfx_fx_loudness_joint")
         return lufs, gain
+
+    def normalize_rows(self, clips, state, rows=None):
+        """One round's normalisation in one call: measure the n compact rows of ``clips`` (n, T) and store gain[i] * clips[i] into
+        row rows[i] of ``state`` (N, T) (rows None: row i, state is (n, T)).  ``rows``: a host sequence (checked and uploaded) or
+        a table from `row_table`.  The other rows of ``state`` are not touched.  Returns ``state``."""
+        n, T = clips.shape
+        if (clips.dtype != torch.float32 or state.dtype != torch.float32 or not clips.is_contiguous() or not state.is_contiguous()
+                or state.dim() != 2 or state.shape[1] != T or state.device != clips.device):
+            raise ValueError("normalize_rows takes contiguous fp32 (n, T) clips and a (N, T) state on one device")
+        if rows is None:
+            if state.shape[0] != n:
+                raise ValueError("normalize_rows without a row table: state and clips need the same number of rows")
+        else:
+            if not isinstance(rows, torch.Tensor):
+                rows = row_table(rows, state.shape[0], state.device)
+            if rows.dtype != torch.int32 or rows.shape != (n,) or rows.device != state.device or n > state.shape[0]:
+                raise ValueError(f"normalize_rows: a table of {tuple(rows.shape)} rows for {n} clips")
+            if clips.untyped_storage().data_ptr() == state.untyped_storage().data_ptr():
+                raise ValueError("normalize_rows: the clips must live outside the state buffer")
+        p, L = self._plan(T), _lib.lib()
+        ws = torch.empty(int(L.rfx_fx_normalize_ws_bytes(n, p["nhop"])) // 8 + 1, device=clips.device, dtype=torch.float64)
+        check(L.rfx_fx_normalize_rows(_ptr(clips), _ptr(state), _ptr(rows), n, T, p["chunk"], p["hop"], p["nhop"], p["nblk"], p["inv"],
+                                      p["coef"].ctypes.data_as(C.c_void_p), float(self.target_lufs_db), _ptr(ws), _stream()),
+              "rfx_fx_normalize_rows")
+        return state
 
     def forward(self, x: torch.Tensor):
         clips, restore = _as_clips(x)
