@@ -17,15 +17,20 @@ unchanged.  Multi-GPU: the loaders shard by rank with a DistributedSampler (what
 reference), see ``EffectDatamodule._dl``.
 """
 import os
+import random
+import shutil
 import sys
 import warnings
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-NUM_EFFECTS = 5      # len(effects.Pedalboard_Effects)
+from .effects import LoudnessNormalize, Pedalboard_Effects as ALL_EFFECTS, require_device, row_table
+
+NUM_EFFECTS = len(ALL_EFFECTS)
 
 
 def load_wav(path):
@@ -147,7 +152,6 @@ def process_effects(dry, effects, effects_to_keep, effects_to_remove, num_kept_e
     clip, random subset of the effects to remove applied on top for the wet clip, loudness normalisation after every effect
     and at the end; the same random calls in the same order as the reference.  dry: (1, T) on the device.
     Returns (normalized_dry, normalized_wet, dry_labels (5,), wet_labels (5,))."""
-    from .effects import Pedalboard_Effects as ALL_EFFECTS
     idx = torch.randperm(len(effects_to_keep)) if shuffle_kept_effects else torch.arange(len(effects_to_keep))
     r1, r2 = num_kept_effects[0], num_kept_effects[1]
     n = torch.round((r1 - r2) * torch.rand(1) + r2).int()
@@ -177,7 +181,6 @@ def plan_effects(effects, effects_to_keep, effects_to_remove, num_kept_effects, 
     shuffling, rand(1) for the count, one ``effect.draw()`` per chosen effect; kept phase first, then the removed phase), with
     no device work: ``effect(x)`` draws and then renders, and rendering consumes no random numbers.
     Returns (kept, removed, dry_labels (5,), wet_labels (5,)): kept / removed are the ordered [(name, params), ...]."""
-    from .effects import Pedalboard_Effects as ALL_EFFECTS
     phases, labels = [], []
     for names, (r1, r2), shuffle in ((effects_to_keep, num_kept_effects, shuffle_kept_effects),
                                      (effects_to_remove, num_removed_effects, shuffle_removed_effects)):
@@ -192,12 +195,29 @@ def plan_effects(effects, effects_to_keep, effects_to_remove, num_kept_effects, 
     return phases[0], phases[1], labels[0], labels[1]
 
 
+class EffectRecipe(NamedTuple):
+    """What a dataset does to its clips, in the positional order of `process_effects` and `plan_effects`: the name -> effect
+    object dict, the names to keep and to remove, the [min, max] number of each, and whether each list is shuffled."""
+    effects: dict
+    effects_to_keep: list
+    effects_to_remove: list
+    num_kept_effects: list
+    num_removed_effects: list
+    shuffle_kept_effects: bool
+    shuffle_removed_effects: bool
+
+    def plan(self):
+        return plan_effects(*self)
+
+    def process(self, dry, normalize):
+        return process_effects(dry, *self, normalize)
+
+
 def _render_rounds(state, seqs, base, effects, normalize, row_tables):
     """Round k applies every clip's k-th effect: ONE render per effect name over the rows that drew it (gathered from the
     state), then ONE normalisation over the round's rows, which is the only writer of the state -- every active row once
     (through the row table: rfx_fx_normalize_rows), the others not at all.  seqs[b]: the [(name, params), ...] of state row
     base + b."""
-    from .effects import row_table
     for k in range(max((len(q) for q in seqs), default=0)):
         groups = {}                                          # effect name -> (rows, params), names in order of first use
         for b, q in enumerate(seqs):
@@ -225,8 +245,9 @@ def process_effects_batch(dry, plans, effects, normalize, row_tables=True):
     phase, and the two final normalisations are one measurement over the 2 B rows.  Launch counts follow the plan structure
     (rounds x effect names), not B.  Returns (dry (B, 1, T), wet (B, 1, T), dry_labels (B, 5), wet_labels (B, 5)), the labels
     on the host like `process_effects`' own; bit for bit what B successive `process_effects` calls give under the same draws."""
-    if not (isinstance(dry, torch.Tensor) and dry.is_cuda and dry.dim() == 3 and dry.shape[1] == 1):
-        raise ValueError("process_effects_batch takes a (B, 1, T) CUDA tensor (remfx_amd.effects has no CPU path)")
+    require_device(dry)
+    if dry.dim() != 3 or dry.shape[1] != 1:
+        raise ValueError(f"process_effects_batch takes a (B, 1, T) tensor, got {tuple(dry.shape)}")
     B, _, T = dry.shape
     if len(plans) != B:
         raise ValueError(f"{len(plans)} plans for {B} clips")
@@ -255,7 +276,6 @@ def render_clips(chunks, plans, effects, normalize, row_tables=True):
 
 
 def _random_chunk(files, chunk_size, sample_rate, device):
-    import random
     chunk = None
     corpus = random.choice(files)
     while chunk is None:
@@ -282,7 +302,44 @@ class SyntheticEffectDataset(Dataset):
         return x, y, torch.zeros(self.k), wet
 
 
-class EffectDataset(Dataset):
+class _RecipeDataset(Dataset):
+    """What EffectDataset and DynamicEffectDataset share: the reference's constructor (both classes take the same arguments), the
+    recipe built from it, the device the clips are rendered on.  A subclass finishes its construction in ``_open``."""
+
+    _SEEDS = {"train": 12345, "val": 22345, "test": 32345}
+
+    def __init__(self, root=None, sample_rate=48000, chunk_size=262144, total_chunks=1000, effect_modules=None,
+                 effects_to_keep=None, effects_to_remove=None, num_kept_effects=(1, 5), num_removed_effects=(1, 5),
+                 shuffle_kept_effects=True, shuffle_removed_effects=False, render_files=True, render_root=None,
+                 mode="train", parallel=False, device=None):
+        super().__init__()
+        self.root, self.sample_rate, self.chunk_size, self.total_chunks = root, sample_rate, chunk_size, total_chunks
+        self.mode, self.parallel, self.device = mode, bool(parallel), device
+        self.recipe = EffectRecipe(effect_modules or {}, [] if effects_to_keep is None else list(effects_to_keep),
+                                   [] if effects_to_remove is None else list(effects_to_remove), list(num_kept_effects),
+                                   list(num_removed_effects), shuffle_kept_effects, shuffle_removed_effects)
+        self.__dict__.update(self.recipe._asdict())          # the reference's attributes: self.effects, self.effects_to_keep, ...
+        self._open(render_files, render_root)
+
+    def _device(self):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{type(self).__name__} renders on the GPU (remfx_amd.effects has no CPU path)")
+        return torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def _render_fresh(self, n, chunk, normalize):
+        """n fresh clips -- per clip: ``chunk()`` chooses the source, then the plan is drawn, the order of the per-item path --
+        rendered as one batch.  Returns `render_clips`' list."""
+        chunks, plans = [], []
+        for _ in range(n):
+            chunks.append(chunk())
+            plans.append(self.recipe.plan())
+        return render_clips(chunks, plans, self.effects, normalize)
+
+    def __len__(self):
+        return self.total_chunks
+
+
+class EffectDataset(_RecipeDataset):
     """remfx.datasets.EffectDataset (datasets.py:333-468), consumer side.
 
     * rendered chunks under ``proc_root`` -> served from disk exactly like the reference's __getitem__;
@@ -293,43 +350,33 @@ class EffectDataset(Dataset):
       only (the other ranks wait at a barrier); an existing rendered set is replaced only after upstream's y/n question on a
       terminal or with REMFX_OVERWRITE_RENDERED=1, and kept (with a warning) otherwise."""
 
-    _SEEDS = {"train": 12345, "val": 22345, "test": 32345}
-
-    def __init__(self, root=None, sample_rate=48000, chunk_size=262144, total_chunks=1000, effect_modules=None,
-                 effects_to_keep=None, effects_to_remove=None, num_kept_effects=(1, 5), num_removed_effects=(1, 5),
-                 shuffle_kept_effects=True, shuffle_removed_effects=False, render_files=True, render_root=None,
-                 mode="train", parallel=False, device=None, render_batch_size=64):
-        super().__init__()
-        self.root, self.sample_rate, self.chunk_size, self.total_chunks = root, sample_rate, chunk_size, total_chunks
-        self.mode, self.effects = mode, effect_modules or {}
-        self.effects_to_keep = [] if effects_to_keep is None else list(effects_to_keep)
-        self.effects_to_remove = [] if effects_to_remove is None else list(effects_to_remove)
-        self.num_kept_effects, self.num_removed_effects = list(num_kept_effects), list(num_removed_effects)
-        self.shuffle_kept_effects, self.shuffle_removed_effects = shuffle_kept_effects, shuffle_removed_effects
-        self.parallel, self.render_batch_size = bool(parallel), int(render_batch_size)
+    def __init__(self, *args, render_batch_size=64, **kwargs):
+        self.render_batch_size = int(render_batch_size)
         if self.render_batch_size < 1:
             raise ValueError(f"render_batch_size must be at least 1, got {render_batch_size}")
+        super().__init__(*args, **kwargs)
+
+    def _open(self, render_files, render_root):
         self.validate_effect_input()
         effects_string = "_".join(self.effects_to_keep + ["_"] + self.effects_to_remove + ["_"]
                                   + [str(x) for x in self.num_kept_effects] + ["_"]
                                   + [str(x) for x in self.num_removed_effects])          # datasets.py:370-379
-        self.proc_root = (Path(str(render_root)) / "processed" / effects_string / mode
+        self.proc_root = (Path(str(render_root)) / "processed" / effects_string / self.mode
                           if render_root is not None and "<unset env" not in str(render_root) else None)
         rendered = self._rendered_chunks()
         self.synthetic = None
-        self.device = device
-        if _usable_dir(root) and render_files and self.proc_root is not None:
+        if _usable_dir(self.root) and render_files and self.proc_root is not None:
             self._render(rendered)
         elif rendered:
-            if render_files and rendered != total_chunks:
-                warnings.warn(f"EffectDataset(mode={mode!r}): render_files=True but no corpus to render from; serving the "
-                              f"{rendered} chunks already under {self.proc_root} (asked for {total_chunks})", stacklevel=2)
+            if render_files and rendered != self.total_chunks:
+                warnings.warn(f"EffectDataset(mode={self.mode!r}): render_files=True but no corpus to render from; serving the "
+                              f"{rendered} chunks already under {self.proc_root} (asked for {self.total_chunks})", stacklevel=4)
             self.total_chunks = rendered                       # datasets.py:451 (render_files=False branch)
         else:
             warnings.warn("EffectDataset: no corpus (DATASET_ROOT) and no rendered chunks: serving seeded white-noise "
-                          "clips (BASELINE.json synthetic inputs)", stacklevel=2)
-            self.synthetic = SyntheticEffectDataset(total_chunks=total_chunks, chunk_size=chunk_size,
-                                                    seed=self._SEEDS.get(mode, 42345))
+                          "clips (BASELINE.json synthetic inputs)", stacklevel=4)
+            self.synthetic = SyntheticEffectDataset(total_chunks=self.total_chunks, chunk_size=self.chunk_size,
+                                                    seed=self._SEEDS.get(self.mode, 42345))
 
     def _render(self, rendered):
         """datasets.py:381-452 on the device.  Rank 0 renders, the other ranks wait at a barrier and then list the same
@@ -337,10 +384,7 @@ class EffectDataset(Dataset):
         input / target / label files of a chunk apart).  An existing non-empty rendered set is never deleted implicitly:
         upstream asks y/n on stdin (datasets.py:385-395) -- so does this on a terminal; without one it takes
         REMFX_OVERWRITE_RENDERED=1 as the "y" and otherwise KEEPS the set with a warning."""
-        import shutil
-        from .effects import LoudnessNormalize
-        if not torch.cuda.is_available():
-            raise RuntimeError("EffectDataset(render_files=True) renders on the GPU (remfx_amd.effects has no CPU path)")
+        self._device()                                       # no GPU: raise before joining any process group
         # scripts/train.py instantiates the datamodule BEFORE the Trainer brings the process group up: under a launcher (WORLD_SIZE > 1
         # in the environment) join the group here, or every rank would think it is rank 0 of 1 and render into the same directory
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 and torch.distributed.is_available() and not torch.distributed.is_initialized():
@@ -350,14 +394,14 @@ class EffectDataset(Dataset):
         rank = torch.distributed.get_rank() if dist_on else 0
         try:
             if rank == 0:
-                self._render_rank0(rendered, shutil, LoudnessNormalize)
+                self._render_rank0(rendered)
         finally:
             if dist_on:
                 torch.distributed.barrier()                  # the other ranks list proc_root only after rank 0 is done
         self.total_chunks = self._rendered_chunks() or self.total_chunks
 
-    def _render_rank0(self, rendered, shutil, LoudnessNormalize):
-        dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+    def _render_rank0(self, rendered):
+        dev = self._device()
         files = locate_files(self.root, self.mode)
         if not files or not any(files):
             raise ValueError(f"EffectDataset: no audio files of the known corpora under {self.root} for mode {self.mode!r}")
@@ -377,42 +421,33 @@ class EffectDataset(Dataset):
             shutil.rmtree(self.proc_root)
         self.proc_root.mkdir(parents=True, exist_ok=True)
         normalize = LoudnessNormalize(self.sample_rate, target_lufs_db=-20)
+        chunk = lambda: _random_chunk(files, self.chunk_size, self.sample_rate, dev)
         if self.parallel:
-            return self._render_batched(files, dev, normalize)
+            return self._render_batched(chunk, normalize)
         for num_chunk in range(self.total_chunks):
-            chunk = _random_chunk(files, self.chunk_size, self.sample_rate, dev)
-            dry, wet, dry_effects, wet_effects = process_effects(
-                chunk, self.effects, self.effects_to_keep, self.effects_to_remove, self.num_kept_effects,
-                self.num_removed_effects, self.shuffle_kept_effects, self.shuffle_removed_effects, normalize)
-            d = self.proc_root / str(num_chunk)
-            d.mkdir(exist_ok=True)
-            save_wav(d / "input.wav", wet, self.sample_rate)
-            save_wav(d / "target.wav", dry, self.sample_rate)
-            torch.save(dry_effects, d / "dry_effects.pt")
-            torch.save(wet_effects, d / "wet_effects.pt")
+            self._write_chunk(num_chunk, *self.recipe.process(chunk(), normalize))
 
-    def _render_batched(self, files, dev, normalize):
-        """parallel=True: the same clips as the loop above (per clip: choose the chunk, then draw the plan -- the order of the
-        per-item path), rendered `render_batch_size` at a time by rounds and copied to the host once per batch."""
+    def _render_batched(self, chunk, normalize):
+        """parallel=True: the same clips as the loop above, rendered `render_batch_size` at a time by rounds and copied to the
+        host once per batch."""
         for first in range(0, self.total_chunks, self.render_batch_size):
-            chunks, plans = [], []
-            for _ in range(first, min(first + self.render_batch_size, self.total_chunks)):
-                chunks.append(_random_chunk(files, self.chunk_size, self.sample_rate, dev))
-                plans.append(plan_effects(self.effects, self.effects_to_keep, self.effects_to_remove, self.num_kept_effects,
-                                          self.num_removed_effects, self.shuffle_kept_effects, self.shuffle_removed_effects))
-            done = render_clips(chunks, plans, self.effects, normalize)
+            done = self._render_fresh(min(self.render_batch_size, self.total_chunks - first), chunk, normalize)
             if len({d.shape for d, _, _, _ in done}) == 1:      # one device-to-host copy for the batch
                 host = torch.stack([torch.stack((d, w)) for d, w, _, _ in done]).cpu()
                 audio = [(host[i, 0], host[i, 1]) for i in range(len(done))]
             else:
                 audio = [(d.cpu(), w.cpu()) for d, w, _, _ in done]
             for i, ((dry, wet), (_, _, dry_effects, wet_effects)) in enumerate(zip(audio, done)):
-                d = self.proc_root / str(first + i)
-                d.mkdir(exist_ok=True)
-                save_wav(d / "input.wav", wet, self.sample_rate)
-                save_wav(d / "target.wav", dry, self.sample_rate)
-                torch.save(dry_effects.clone(), d / "dry_effects.pt")
-                torch.save(wet_effects.clone(), d / "wet_effects.pt")
+                self._write_chunk(first + i, dry, wet, dry_effects, wet_effects)
+
+    def _write_chunk(self, num_chunk, dry, wet, dry_effects, wet_effects):
+        """One rendered chunk in the reference's layout (datasets.py:445-450)."""
+        d = self.proc_root / str(num_chunk)
+        d.mkdir(exist_ok=True)
+        save_wav(d / "input.wav", wet, self.sample_rate)
+        save_wav(d / "target.wav", dry, self.sample_rate)
+        torch.save(dry_effects.clone(), d / "dry_effects.pt")        # a batch's labels are rows of one tensor: save the row alone
+        torch.save(wet_effects.clone(), d / "wet_effects.pt")
 
     def _rendered_chunks(self):
         if self.proc_root is None or not self.proc_root.is_dir():
@@ -422,19 +457,15 @@ class EffectDataset(Dataset):
     def validate_effect_input(self):
         """The three checks of datasets.py:470-505: effect objects are Pedalboard_Effects members, every name to keep /
         remove is a key of effect_modules, and the [min, max] counts are ordered."""
-        from .effects import Pedalboard_Effects
         for effect in self.effects.values():
-            if type(effect) not in Pedalboard_Effects:
-                raise ValueError(f"Effect {effect} not found in ALL_EFFECTS. Please choose from {Pedalboard_Effects}")
+            if type(effect) not in ALL_EFFECTS:
+                raise ValueError(f"Effect {effect} not found in ALL_EFFECTS. Please choose from {ALL_EFFECTS}")
         for name in self.effects_to_keep + self.effects_to_remove:
             if name not in self.effects:
                 raise ValueError(f"Effect {name} not found in self.effects. Please choose from {list(self.effects)}")
         for lo_hi, what in ((self.num_kept_effects, "kept"), (self.num_removed_effects, "removed")):
             if lo_hi[0] > lo_hi[1]:
                 raise ValueError(f"num_{what}_effects must be a tuple of (min, max). Got {lo_hi}")
-
-    def __len__(self):
-        return self.total_chunks
 
     def __getitem__(self, idx):
         if self.synthetic is not None:
@@ -447,44 +478,28 @@ class EffectDataset(Dataset):
         return inp, tgt, dry_effect_names, wet_effect_names
 
 
-class DynamicEffectDataset(Dataset):
+class DynamicEffectDataset(_RecipeDataset):
     """remfx.datasets.DynamicEffectDataset (datasets.py:205-330; cfg/exp/5-5_full_cls_dynamic.yaml): every item is a fresh
     random chunk with freshly drawn effects -- rendered on the device (`device`, default the current GPU), so use
     ``num_workers=0``.  Without a corpus (``root`` unset / missing) the source chunks are seeded white noise at about
     -20 dB and the effects are still drawn and rendered: on-the-fly augmentation stays exercisable offline."""
 
-    def __init__(self, root=None, sample_rate=48000, chunk_size=262144, total_chunks=1000, effect_modules=None,
-                 effects_to_keep=None, effects_to_remove=None, num_kept_effects=(1, 5), num_removed_effects=(1, 5),
-                 shuffle_kept_effects=True, shuffle_removed_effects=False, render_files=True, render_root=None,
-                 mode="train", parallel=False, device=None):
-        super().__init__()
-        from .effects import LoudnessNormalize
-        self.root, self.sample_rate, self.chunk_size, self.total_chunks = root, sample_rate, chunk_size, total_chunks
-        self.mode, self.effects = mode, effect_modules or {}
-        self.effects_to_keep = [] if effects_to_keep is None else list(effects_to_keep)
-        self.effects_to_remove = [] if effects_to_remove is None else list(effects_to_remove)
-        self.num_kept_effects, self.num_removed_effects = list(num_kept_effects), list(num_removed_effects)
-        self.shuffle_kept_effects, self.shuffle_removed_effects = shuffle_kept_effects, shuffle_removed_effects
-        self.normalize = LoudnessNormalize(sample_rate, target_lufs_db=-20)
-        self.device, self.renders_on_device, self.parallel = device, True, bool(parallel)
-        self.files = locate_files(root, mode) if _usable_dir(root) else []
+    renders_on_device = True
+
+    def _open(self, render_files, render_root):
+        self.normalize = LoudnessNormalize(self.sample_rate, target_lufs_db=-20)
+        self.files = locate_files(self.root, self.mode) if _usable_dir(self.root) else []
         if not any(self.files):
             warnings.warn("DynamicEffectDataset: no corpus (DATASET_ROOT): effects are rendered over seeded white-noise chunks",
-                          stacklevel=2)
+                          stacklevel=3)
             self.files = []
-        self._noise = torch.Generator().manual_seed(EffectDataset._SEEDS.get(mode, 42345))
+        self._noise = torch.Generator().manual_seed(self._SEEDS.get(self.mode, 42345))
 
     def process_effects(self, dry):
-        return process_effects(dry, self.effects, self.effects_to_keep, self.effects_to_remove, self.num_kept_effects,
-                               self.num_removed_effects, self.shuffle_kept_effects, self.shuffle_removed_effects, self.normalize)
-
-    def __len__(self):
-        return self.total_chunks
+        return self.recipe.process(dry, self.normalize)
 
     def _chunk(self):
-        if not torch.cuda.is_available():
-            raise RuntimeError("DynamicEffectDataset renders on the GPU (remfx_amd.effects has no CPU path)")
-        dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = self._device()
         if self.files:
             return _random_chunk(self.files, self.chunk_size, self.sample_rate, dev)
         return (torch.randn(1, self.chunk_size, generator=self._noise) * 0.1).to(dev)
@@ -497,13 +512,8 @@ class DynamicEffectDataset(Dataset):
         """One collated batch of n fresh items, (wet (n, 1, T), dry (n, 1, T), dry_labels (n, 5), wet_labels (n, 5)) on the
         device: the clips and labels n successive ``__getitem__`` calls give under the same seeds (per clip: chunk, then the
         draws), rendered by rounds with one launch per effect and round (`process_effects_batch`)."""
-        chunks, plans = [], []
-        for _ in range(int(n)):
-            chunks.append(self._chunk())
-            plans.append(plan_effects(self.effects, self.effects_to_keep, self.effects_to_remove, self.num_kept_effects,
-                                      self.num_removed_effects, self.shuffle_kept_effects, self.shuffle_removed_effects))
-        done = render_clips(chunks, plans, self.effects, self.normalize)
-        dev = chunks[0].device
+        done = self._render_fresh(int(n), self._chunk, self.normalize)
+        dev = done[0][0].device
         return (torch.stack([w for _, w, _, _ in done]), torch.stack([d for d, _, _, _ in done]),
                 torch.stack([dl for _, _, dl, _ in done]).to(dev), torch.stack([wl for _, _, _, wl in done]).to(dev))
 

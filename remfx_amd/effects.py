@@ -7,7 +7,7 @@ Here the same classes -- same names (they are the dict keys of RemFXChainInferen
 unchanged), same parameter ranges, same random draws in the same order (``rand`` = torch.rand(1), ``loguniform`` =
 scipy) -- render through the HIP kernels of csrc/fx.hip, one launch per effect for a whole batch of clips with
 per-clip parameters.  ``forward(x)`` takes the reference's ``(channels, samples)`` tensor or a batch
-``(B, 1, samples)``; tensors must live on the GPU (no CPU path: the library raises otherwise).
+``(B, 1, samples)``; tensors must live on the GPU: the library raises otherwise.
 
 Algorithms are restatements of the published JUCE / pedalboard / pyloudnorm code (oracle/ref_effects.py lists
 them; both packages are absent here, parity unpinned).
@@ -35,27 +35,44 @@ def randint(low=0, high=1):                            # effects.py:33-34
     return torch.randint(low, high + 1, (1,)).numpy()[0]
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+def _call(name, *args):
+    """Launch the library's entry point `name` on the current stream: a tensor goes as its device pointer, a numpy array as its
+    host pointer, None as a null pointer, any other value as it is.  `args` holds the tensors until the launch is queued: a
+    block freed before that would be handed to the next allocation."""
+    ptrs = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray)
+            else C.c_void_p(0) if a is None else a for a in args]
+    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
+    check(getattr(_lib.lib(), name)(*ptrs, stream), name)
 
 
-def _stream():
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
+def _ws_size(name, *dims):
+    """The workspace size the library's `name` query gives for a launch of these dimensions."""
+    return int(getattr(_lib.lib(), name)(*dims))
 
 
-def _as_clips(x):
-    """(channels, T) or (B, C, T) -> contiguous (N, T) fp32 device view + a function restoring the shape."""
+def require_device(x):
     if not (isinstance(x, torch.Tensor) and x.is_cuda):
         raise ValueError("remfx_amd.effects render on the GPU: pass a CUDA tensor (there is no CPU path)")
-    shape = x.shape
+
+
+def _check_clips(x):
+    require_device(x)
     if x.dim() not in (2, 3):
-        raise ValueError(f"effects take (channels, samples) or (batch, channels, samples), got {tuple(shape)}")
-    flat = x.reshape(-1, shape[-1]).to(torch.float32).contiguous()
-    return flat, (lambda y: y.view(shape))
+        raise ValueError(f"effects take (channels, samples) or (batch, channels, samples), got {tuple(x.shape)}")
+
+
+def _rows(x):
+    """(..., T) -> contiguous (N, T) fp32; ``.view(x.shape)`` restores the shape of a result."""
+    return x.reshape(-1, x.shape[-1]).to(torch.float32).contiguous()
 
 
 def _vec(vals, device, dtype=torch.float32):
     return torch.tensor(np.asarray(vals), dtype=dtype).to(device)
+
+
+def _col(params, f, device, dtype=torch.float32):
+    """One value per parameter set -- ``p[f]`` for a key, ``f(p)`` for a function -- as a device vector."""
+    return _vec([p[f] if isinstance(f, str) else f(p) for p in params], device, dtype)
 
 
 def row_table(rows, nstate, device):
@@ -73,6 +90,9 @@ class _RandomEffect(torch.nn.Module):
     a 2-D input, as pedalboard applies one board to all channels) and renders."""
 
     defaults = {}
+    renders_clips = False     # True: render takes (B, C, T) clips with one parameter set each, not (N, T) rows with one per row
+    in_place = False          # True: render scales its rows in place, and forward hands back x itself with the result in it
+    check_input = staticmethod(_check_clips)          # raises ValueError for what forward does not take
 
     def __init__(self, sample_rate: float, **ranges):
         super().__init__()
@@ -92,14 +112,25 @@ class _RandomEffect(torch.nn.Module):
         """clips: (N, T) device tensor; params: list of N dicts (draw()).  Returns (N, T)."""
         raise NotImplementedError
 
+    def draw_for(self, T):
+        """The parameter set of one clip of T samples."""
+        return self.draw()
+
     def forward(self, x: torch.Tensor):
-        clips, restore = _as_clips(x)
+        self.check_input(x)
         nsets = x.shape[0] if x.dim() == 3 else 1
-        sets = [self.draw() for _ in range(nsets)]
-        per = clips.shape[0] // nsets
-        params = [s for s in sets for _ in range(per)]
+        sets = [self.draw_for(x.shape[-1]) for _ in range(nsets)]
         self.last_params = sets
-        return restore(self.render(clips, params))
+        if self.renders_clips:
+            y = self.render(x.reshape(nsets, x.shape[-2], x.shape[-1]).to(torch.float32).contiguous(), sets)
+            return y if x.dim() == 3 else y[0]
+        rows = _rows(x)
+        y = self.render(rows, [s for s in sets for _ in range(rows.shape[0] // nsets)])
+        if not self.in_place:
+            return y.view(x.shape)
+        if y.data_ptr() != x.data_ptr():
+            x.copy_(y.view(x.shape))
+        return x
 
 
 class RandomPedalboardReverb(_RandomEffect):
@@ -112,13 +143,12 @@ class RandomPedalboardReverb(_RandomEffect):
 
     def render(self, clips, params):
         dev = clips.device
-        damp = _vec([p["damping"] * 0.4 for p in params], dev)                       # juce::Reverb::setParameters
-        fb = _vec([p["room_size"] * 0.28 + 0.7 for p in params], dev)
-        wet1 = _vec([0.5 * (p["wet_dry"] * 3.0) * (1.0 + p["width"]) for p in params], dev)
-        dry = _vec([(1.0 - p["wet_dry"]) * 2.0 for p in params], dev)
+        damp = _col(params, lambda p: p["damping"] * 0.4, dev)                       # juce::Reverb::setParameters
+        fb = _col(params, lambda p: p["room_size"] * 0.28 + 0.7, dev)
+        wet1 = _col(params, lambda p: 0.5 * (p["wet_dry"] * 3.0) * (1.0 + p["width"]), dev)
+        dry = _col(params, lambda p: (1.0 - p["wet_dry"]) * 2.0, dev)
         y = torch.empty_like(clips)
-        check(_lib.lib().rfx_fx_reverb(_ptr(clips), _ptr(y), clips.shape[0], clips.shape[1], int(self.sample_rate), _ptr(damp),
-                                       _ptr(fb), _ptr(wet1), _ptr(dry), _stream()), "rfx_fx_reverb")
+        _call("rfx_fx_reverb", clips, y, clips.shape[0], clips.shape[1], int(self.sample_rate), damp, fb, wet1, dry)
         return y
 
 
@@ -155,6 +185,7 @@ class RandomSoxReverb(_RandomEffect):
     defaults = dict(min_reverberance=10.0, max_reverberance=100.0, min_high_freq_damping=0.0, max_high_freq_damping=100.0,
                     min_wet_dry=0.0, max_wet_dry=1.0, min_room_scale=5.0, max_room_scale=100.0, min_stereo_depth=20.0,
                     max_stereo_depth=100.0, min_pre_delay=0.0, max_pre_delay=100.0)
+    renders_clips = True
 
     def draw(self):                                    # effects.py:549-554
         return dict(reverberance=rand(self.min_reverberance, self.max_reverberance),
@@ -182,24 +213,17 @@ class RandomSoxReverb(_RandomEffect):
                     coef.append([q["feedback"], q["damp"], q["gain"], q["wet_dry"]])
         dev = clips.device
         geom, coef = _vec(geom, dev, torch.int32), _vec(coef, dev)
-        L = _lib.lib()
-        ws = torch.empty(int(L.rfx_fx_sox_reverb_ws_floats(B, Cin, T)), device=dev, dtype=torch.float32)
+        ws = torch.empty(_ws_size("rfx_fx_sox_reverb_ws_floats", B, Cin, T), device=dev, dtype=torch.float32)
         y = torch.empty((B, 2, T), device=dev, dtype=torch.float32)
-        check(L.rfx_fx_sox_reverb(_ptr(clips), _ptr(y), _ptr(ws), B, Cin, T, _ptr(geom), _ptr(coef), lds, _stream()),
-              "rfx_fx_sox_reverb")
+        _call("rfx_fx_sox_reverb", clips, y, ws, B, Cin, T, geom, coef, lds)
         return y
 
-    def forward(self, x: torch.Tensor):
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            raise ValueError("remfx_amd.effects render on the GPU: pass a CUDA tensor (there is no CPU path)")
+    @staticmethod
+    def check_input(x):
+        require_device(x)
         if x.dim() not in (2, 3) or x.shape[-2] not in (1, 2):
             raise ValueError(f"the SoX reverb takes (1 or 2, samples) or (batch, 1 or 2, samples), got {tuple(x.shape)} "
                              "(beyond two channels SoX drops the stereo depth: not modelled)")
-        clips = x.reshape(-1, x.shape[-2], x.shape[-1]).to(torch.float32).contiguous()
-        sets = [self.draw() for _ in range(clips.shape[0])]
-        self.last_params = sets
-        y = self.render(clips, sets)
-        return y if x.dim() == 3 else y[0]
 
 
 class RandomPedalboardChorus(_RandomEffect):
@@ -212,12 +236,9 @@ class RandomPedalboardChorus(_RandomEffect):
                     feedback=rand(self.min_feedback, self.max_feedback), mix=rand(self.min_mix, self.max_mix))
 
     def render(self, clips, params):
-        dev = clips.device
-        v = {k: _vec([p[k] for p in params], dev) for k in ("rate_hz", "depth", "centre_delay_ms", "feedback", "mix")}
+        cols = [_col(params, k, clips.device) for k in ("rate_hz", "depth", "centre_delay_ms", "feedback", "mix")]
         y = torch.empty_like(clips)
-        check(_lib.lib().rfx_fx_chorus(_ptr(clips), _ptr(y), clips.shape[0], clips.shape[1], float(self.sample_rate),
-                                       _ptr(v["rate_hz"]), _ptr(v["depth"]), _ptr(v["centre_delay_ms"]), _ptr(v["feedback"]),
-                                       _ptr(v["mix"]), _stream()), "rfx_fx_chorus")
+        _call("rfx_fx_chorus", clips, y, clips.shape[0], clips.shape[1], float(self.sample_rate), *cols)
         return y
 
 
@@ -232,11 +253,9 @@ class RandomPedalboardDelay(_RandomEffect):
 
     def render(self, clips, params):
         dev = clips.device
-        d = _vec([int(p["delay_seconds"] * self.sample_rate) for p in params], dev, torch.int32)
-        fb, mix = _vec([p["feedback"] for p in params], dev), _vec([p["mix"] for p in params], dev)
+        d = _col(params, lambda p: int(p["delay_seconds"] * self.sample_rate), dev, torch.int32)
         y = torch.empty_like(clips)
-        check(_lib.lib().rfx_fx_delay(_ptr(clips), _ptr(y), clips.shape[0], clips.shape[1], _ptr(d), _ptr(fb), _ptr(mix),
-                                      _stream()), "rfx_fx_delay")
+        _call("rfx_fx_delay", clips, y, clips.shape[0], clips.shape[1], d, _col(params, "feedback", dev), _col(params, "mix", dev))
         return y
 
 
@@ -247,10 +266,9 @@ class RandomPedalboardDistortion(_RandomEffect):
         return dict(drive_db=rand(self.min_drive_db, self.max_drive_db))
 
     def render(self, clips, params):
-        g = _vec([10.0 ** (p["drive_db"] / 20.0) for p in params], clips.device)
+        g = _col(params, lambda p: 10.0 ** (p["drive_db"] / 20.0), clips.device)
         y = torch.empty_like(clips)
-        check(_lib.lib().rfx_fx_distortion(_ptr(clips), _ptr(y), clips.shape[0], clips.shape[1], _ptr(g), _stream()),
-              "rfx_fx_distortion")
+        _call("rfx_fx_distortion", clips, y, clips.shape[0], clips.shape[1], g)
         return y
 
 
@@ -269,33 +287,24 @@ class RandomPedalboardCompressor(_RandomEffect):
 
     def render(self, clips, params):
         dev = clips.device
-        cte = lambda ms: _ballistics_cte(ms, self.sample_rate)
-        thr = _vec([10.0 ** (p["threshold_db"] / 20.0) for p in params], dev)
-        ratio = _vec([p["ratio"] for p in params], dev)
-        ca, cr = _vec([cte(p["attack_ms"]) for p in params], dev), _vec([cte(p["release_ms"]) for p in params], dev)
+        thr = _col(params, lambda p: 10.0 ** (p["threshold_db"] / 20.0), dev)
+        ratio = _col(params, "ratio", dev)
+        ca = _col(params, lambda p: _ballistics_cte(p["attack_ms"], self.sample_rate), dev)
+        cr = _col(params, lambda p: _ballistics_cte(p["release_ms"], self.sample_rate), dev)
         y, ws = torch.empty_like(clips), torch.empty_like(clips)
-        check(_lib.lib().rfx_fx_compressor(_ptr(clips), _ptr(y), _ptr(ws), clips.shape[0], clips.shape[1], _ptr(thr), _ptr(ratio),
-                                           _ptr(ca), _ptr(cr), _stream()), "rfx_fx_compressor")
+        _call("rfx_fx_compressor", clips, y, ws, clips.shape[0], clips.shape[1], thr, ratio, ca, cr)
         return y
 
 
 def _k_weighting(rate):
     """pyloudnorm "K-weighting": high shelf (+4 dB, 1500 Hz, Q 1/sqrt2) then high pass (38 Hz, Q 0.5), normalised by a0."""
-    def coef(G, Q, fc, shelf):
-        A = 10.0 ** (G / 40.0)
-        w0 = 2.0 * np.pi * (fc / rate)
-        alpha = np.sin(w0) / (2.0 * Q)
-        c = np.cos(w0)
-        if shelf:
-            b = [A * ((A + 1) + (A - 1) * c + 2 * np.sqrt(A) * alpha), -2 * A * ((A - 1) + (A + 1) * c),
-                 A * ((A + 1) + (A - 1) * c - 2 * np.sqrt(A) * alpha)]
-            a = [(A + 1) - (A - 1) * c + 2 * np.sqrt(A) * alpha, 2 * ((A - 1) - (A + 1) * c),
-                 (A + 1) - (A - 1) * c - 2 * np.sqrt(A) * alpha]
-        else:
-            b = [(1 + c) / 2, -(1 + c), (1 + c) / 2]
-            a = [1 + alpha, -2 * c, 1 - alpha]
-        return np.array(b, dtype=np.float64) / a[0], np.array(a, dtype=np.float64) / a[0]
-    return coef(4.0, 1.0 / np.sqrt(2.0), 1500.0, True), coef(0.0, 0.5, 38.0, False)
+    w0 = 2.0 * np.pi * (38.0 / rate)
+    alpha = np.sin(w0) / (2.0 * 0.5)
+    c = np.cos(w0)
+    b = [(1 + c) / 2, -(1 + c), (1 + c) / 2]
+    a = [1 + alpha, -2 * c, 1 - alpha]
+    high_pass = np.array(b, dtype=np.float64) / a[0], np.array(a, dtype=np.float64) / a[0]
+    return biqaud(4.0, 1500.0, 1.0 / np.sqrt(2.0), rate, "high_shelf"), high_pass
 
 
 def _transition(sections, steps):
@@ -328,6 +337,7 @@ class LoudnessNormalize(torch.nn.Module):
         self._cache = {}
 
     def _plan(self, T):
+        """(hops per row, the launch arguments every measuring entry point takes ahead of the target level) of T-sample clips."""
         p = self._cache.get(T)
         if p is None:
             rate = self.sample_rate
@@ -343,33 +353,28 @@ class LoudnessNormalize(torch.nn.Module):
             (b1, a1), (b2, a2) = _k_weighting(rate)
             M = _transition([(b1, a1), (b2, a2)], chunk)
             coef = np.concatenate([b1, a1, b2, a2, M.reshape(-1)]).astype(np.float64)
-            p = dict(nblk=nblk, hop=hop, nhop=nblk + 3, chunk=chunk, coef=coef, inv=1.0 / (T_g * rate))
+            p = nblk + 3, (chunk, hop, nblk + 3, nblk, 1.0 / (T_g * rate), coef)         # the cache keeps coef alive
             self._cache[T] = p
         return p
 
     def measure(self, clips):
         """(N, T) device clips -> (lufs (N,), gain (N,)) device tensors."""
         N, T = clips.shape
-        p = self._plan(T)
-        hop_ws = torch.empty((N, p["nhop"]), device=clips.device, dtype=torch.float64)
+        nhop, plan = self._plan(T)
+        hop_ws = torch.empty((N, nhop), device=clips.device, dtype=torch.float64)
         lufs = torch.empty(N, device=clips.device, dtype=torch.float32)
         gain = torch.empty_like(lufs)
-        coef = p["coef"]
-        check(_lib.lib().rfx_fx_loudness(_ptr(clips), N, T, p["chunk"], p["hop"], p["nhop"], p["nblk"], p["inv"],
-                                         coef.ctypes.data_as(C.c_void_p), float(self.target_lufs_db), _ptr(hop_ws), _ptr(lufs),
-                                         _ptr(gain), _stream()), "rfx_fx_loudness")
+        _call("rfx_fx_loudness", clips, N, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
         return lufs, gain
 
     def measure_joint(self, clips):
         """(B, C, T) device clips -> (lufs (B,), gain (B,)): every clip's C channels measured together."""
         B, Ch, T = clips.shape
-        p = self._plan(T)
-        hop_ws = torch.empty((B * Ch, p["nhop"]), device=clips.device, dtype=torch.float64)
+        nhop, plan = self._plan(T)
+        hop_ws = torch.empty((B * Ch, nhop), device=clips.device, dtype=torch.float64)
         lufs = torch.empty(B, device=clips.device, dtype=torch.float32)
         gain = torch.empty_like(lufs)
-        check(_lib.lib().rfx_fx_loudness_joint(_ptr(clips), B, Ch, T, p["chunk"], p["hop"], p["nhop"], p["nblk"], p["inv"],
-                                               p["coef"].ctypes.data_as(C.c_void_p), float(self.target_lufs_db), _ptr(hop_ws),
-                                               _ptr(lufs), _ptr(gain), _stream()), "rfx_fx_loudness_joint")
+        _call("rfx_fx_loudness_joint", clips, B, Ch, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
         return lufs, gain
 
     def normalize_rows(self, clips, state, rows=None):
@@ -390,23 +395,30 @@ class LoudnessNormalize(torch.nn.Module):
                 raise ValueError(f"normalize_rows: a table of {tuple(rows.shape)} rows for {n} clips")
             if clips.untyped_storage().data_ptr() == state.untyped_storage().data_ptr():
                 raise ValueError("normalize_rows: the clips must live outside the state buffer")
-        p, L = self._plan(T), _lib.lib()
-        ws = torch.empty(int(L.rfx_fx_normalize_ws_bytes(n, p["nhop"])) // 8 + 1, device=clips.device, dtype=torch.float64)
-        check(L.rfx_fx_normalize_rows(_ptr(clips), _ptr(state), _ptr(rows), n, T, p["chunk"], p["hop"], p["nhop"], p["nblk"], p["inv"],
-                                      p["coef"].ctypes.data_as(C.c_void_p), float(self.target_lufs_db), _ptr(ws), _stream()),
-              "rfx_fx_normalize_rows")
+        nhop, plan = self._plan(T)
+        ws = torch.empty(_ws_size("rfx_fx_normalize_ws_bytes", n, nhop) // 8 + 1, device=clips.device, dtype=torch.float64)
+        _call("rfx_fx_normalize_rows", clips, state, rows, n, T, *plan, float(self.target_lufs_db), ws)
         return state
 
+    @staticmethod
+    def _scale(rows, gain):
+        """(N, T) rows times their (N,) gains, as a new tensor."""
+        y = torch.empty_like(rows)
+        _call("rfx_fx_scale", rows, y, rows.shape[0], rows.shape[1], gain)
+        return y
+
+    def normalize_joint(self, clips):
+        """(B, C, T) contiguous fp32 device clips -> the same shape: every clip measured jointly and scaled by its one gain."""
+        B, Ch, T = clips.shape
+        _, gain = self.measure_joint(clips)
+        return self._scale(clips.view(B * Ch, T), gain.repeat_interleave(Ch)).view(B, Ch, T)
+
     def forward(self, x: torch.Tensor):
-        clips, restore = _as_clips(x)
+        _check_clips(x)
+        rows = _rows(x)
         if x.dim() == 2 and x.shape[0] != 1:
-            _, gain = self.measure_joint(clips.view(1, *clips.shape))
-            gain = gain.expand(clips.shape[0]).contiguous()
-        else:
-            _, gain = self.measure(clips)
-        y = torch.empty_like(clips)
-        check(_lib.lib().rfx_fx_scale(_ptr(clips), _ptr(y), clips.shape[0], clips.shape[1], _ptr(gain), _stream()), "rfx_fx_scale")
-        return restore(y)
+            return self.normalize_joint(rows.unsqueeze(0)).view(x.shape)
+        return self._scale(rows, self.measure(rows)[1]).view(x.shape)
 
 
 _RBJ = {    # RBJ cookbook biquads as (b0, b1, b2, a0, a1, a2) of (A, cos w0, alpha, sqrt A)
@@ -457,7 +469,7 @@ def _eq_render(clips, params, sample_rate):
         raise ValueError("parametric EQ: every clip of one launch needs the same number of bands")
     coef = torch.from_numpy(np.stack([r for _, r in rows])).to(clips.device)
     y = torch.empty_like(clips)
-    check(_lib.lib().rfx_fx_eq(_ptr(clips), _ptr(y), N, T, nsec, chunk, _ptr(coef), _stream()), "rfx_fx_eq")
+    _call("rfx_fx_eq", clips, y, N, T, nsec, chunk, coef)
     return y
 
 
@@ -474,9 +486,8 @@ def parametric_eq(x, sample_rate: float, low_shelf_gain_db: float = 0.0, low_she
              high_shelf_q_factor=high_shelf_q_factor)
     is_np = isinstance(x, np.ndarray)
     t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda() if is_np else x
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise ValueError("remfx_amd.effects render on the GPU: pass a CUDA tensor or a numpy array (there is no CPU path)")
-    flat = t.reshape(-1, t.shape[-1]).to(torch.float32).contiguous()
+    require_device(t)
+    flat = _rows(t)
     y = _eq_render(flat, [p] * flat.shape[0], sample_rate).view(t.shape)
     return y.cpu().numpy().astype(dtype) if is_np else y
 
@@ -507,8 +518,7 @@ def _widener_gains(width):
 
 
 def _check_stereo(x):
-    if not (isinstance(x, torch.Tensor) and x.is_cuda):
-        raise ValueError("remfx_amd.effects render on the GPU: pass a CUDA tensor (there is no CPU path)")
+    require_device(x)
     if x.dim() not in (2, 3) or x.shape[-2] != 2:
         raise ValueError(f"the stereo widener takes (2, samples) or (batch, 2, samples), got {tuple(x.shape)}")
 
@@ -516,7 +526,7 @@ def _check_stereo(x):
 def stereo_widener(x: torch.Tensor, width):
     """effects.py:217-235 on the device: x (2, T) or (B, 2, T) CUDA, width a number or one per clip.  Returns a new tensor."""
     _check_stereo(x)
-    flat = x.reshape(-1, x.shape[-1]).to(torch.float32).contiguous()
+    flat = _rows(x)
     widths = list(width) if isinstance(width, (list, tuple)) else [width] * (flat.shape[0] // 2)
     return _widener_render(flat, widths).view(x.shape)
 
@@ -525,8 +535,7 @@ def _widener_render(rows, widths):
     g = [_widener_gains(w) for w in widths]
     gm, gs = _vec([a for a, _ in g], rows.device), _vec([b for _, b in g], rows.device)
     y = torch.empty_like(rows)
-    check(_lib.lib().rfx_fx_widener(_ptr(rows), _ptr(y), rows.shape[0] // 2, rows.shape[1], _ptr(gm), _ptr(gs), _stream()),
-          "rfx_fx_widener")
+    _call("rfx_fx_widener", rows, y, rows.shape[0] // 2, rows.shape[1], gm, gs)
     return y
 
 
@@ -534,6 +543,7 @@ class RandomStereoWidener(_RandomEffect):
     """effects.py:238-252.  Stereo only: any other channel count raises ValueError (upstream: IndexError for mono, channels
     beyond two silently dropped)."""
     defaults = dict(min_width=0.0, max_width=1.0)
+    check_input = staticmethod(_check_stereo)
 
     def draw(self):                                    # effects.py:251
         return dict(width=rand(self.min_width, self.max_width))
@@ -544,21 +554,21 @@ class RandomStereoWidener(_RandomEffect):
             raise ValueError("the stereo widener renders (left, right) row pairs")
         return _widener_render(clips, [p["width"] for p in params[::2]])
 
-    def forward(self, x: torch.Tensor):
-        _check_stereo(x)
-        return super().forward(x)
-
 
 class RandomVolumeAutomation(_RandomEffect):
     """effects.py:255-294: piecewise-linear dB ramps over Dirichlet-drawn segments.  Like upstream, ``forward`` scales ``x`` IN
     PLACE and returns it."""
     defaults = dict(min_segments=1, max_segments=3, min_gain_db=-6.0, max_gain_db=6.0)
+    in_place = True
 
     def draw(self, T):                                 # effects.py:274-291
         n = randint(self.min_segments, self.max_segments)
         lengths = (T * np.random.dirichlet([rand(0, 10) for _ in range(n)], 1)).astype("int")[0]
         gains = [rand(self.min_gain_db, self.max_gain_db) for _ in range(n)]
         return dict(num_segments=int(n), segment_lengths=[int(v) for v in lengths], end_gains_db=gains)
+
+    def draw_for(self, T):                             # the one draw that depends on the clip: segment lengths in samples
+        return self.draw(T)
 
     def render(self, clips, params):
         """Scales the (N, T) fp32 clips in place and returns them."""
@@ -574,22 +584,9 @@ class RandomVolumeAutomation(_RandomEffect):
             d0 += [0.0] + g[:-1] + [0.0] * pad
             d1 += g + [0.0] * pad
         dev = clips.device
-        # held until the launch is queued: a freed block would be handed to the next _vec
-        ends, d0, d1 = _vec(ends, dev, torch.int32), _vec(d0, dev), _vec(d1, dev)
-        check(_lib.lib().rfx_fx_volume(_ptr(clips), clips.shape[0], clips.shape[1], S, _ptr(ends), _ptr(d0), _ptr(d1), _stream()),
-              "rfx_fx_volume")
+        # _call holds the three tables until the launch is queued: a freed block would be handed to the next _vec
+        _call("rfx_fx_volume", clips, clips.shape[0], clips.shape[1], S, _vec(ends, dev, torch.int32), _vec(d0, dev), _vec(d1, dev))
         return clips
-
-    def forward(self, x: torch.Tensor):
-        clips, _ = _as_clips(x)
-        nsets = x.shape[0] if x.dim() == 3 else 1
-        sets = [self.draw(x.shape[-1]) for _ in range(nsets)]
-        per = clips.shape[0] // nsets
-        self.last_params = sets
-        self.render(clips, [s for s in sets for _ in range(per)])
-        if clips.data_ptr() != x.data_ptr():
-            x.copy_(clips.view(x.shape))
-        return x
 
 
 class RandomPedalboardPhaser(_RandomEffect):
@@ -604,12 +601,10 @@ class RandomPedalboardPhaser(_RandomEffect):
     def render(self, clips, params):
         dev = clips.device
         N, T = clips.shape
-        v = {k: _vec([p[k] for p in params], dev) for k in ("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix")}
-        L = _lib.lib()
-        ws = torch.empty(int(L.rfx_fx_phaser_ws_floats(N, T)), device=dev, dtype=torch.float32)
+        cols = [_col(params, k, dev) for k in ("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix")]
+        ws = torch.empty(_ws_size("rfx_fx_phaser_ws_floats", N, T), device=dev, dtype=torch.float32)
         y = torch.empty_like(clips)
-        check(L.rfx_fx_phaser(_ptr(clips), _ptr(y), _ptr(ws), N, T, float(self.sample_rate), _ptr(v["rate_hz"]), _ptr(v["depth"]),
-                              _ptr(v["centre_frequency_hz"]), _ptr(v["feedback"]), _ptr(v["mix"]), _stream()), "rfx_fx_phaser")
+        _call("rfx_fx_phaser", clips, y, ws, N, T, float(self.sample_rate), *cols)
         return y
 
 
@@ -639,7 +634,7 @@ class RandomPedalboardLimiter(_RandomEffect):
         prm = _vec(np.asarray(cols).T.copy(), clips.device)
         ws = torch.empty((2, N, T), device=clips.device, dtype=torch.float32)
         y = torch.empty_like(clips)
-        check(_lib.lib().rfx_fx_limiter(_ptr(clips), _ptr(y), _ptr(ws), N, T, _ptr(prm), _stream()), "rfx_fx_limiter")
+        _call("rfx_fx_limiter", clips, y, ws, N, T, prm)
         return y
 
 
@@ -671,7 +666,7 @@ class RandomAudioEffectsChannel(torch.nn.Module):
             for fx, p in self.stages:
                 if p < torch.rand(1):
                     continue
-                fired.append((type(fx).__name__, fx.draw(T) if isinstance(fx, RandomVolumeAutomation) else fx.draw()))
+                fired.append((type(fx).__name__, fx.draw_for(T)))
             out.append(fired)
         return out
 
@@ -692,11 +687,7 @@ class RandomAudioEffectsChannel(torch.nn.Module):
             else:
                 idx = torch.tensor([b * Ch + c for b, _ in sel for c in range(Ch)], device=y.device)
                 y.index_copy_(0, idx, fx.render(y.index_select(0, idx), params))
-        _, gain = self.normalize.measure_joint(y.view(B, Ch, T))
-        gain = gain.repeat_interleave(Ch)
-        out = torch.empty_like(y)
-        check(_lib.lib().rfx_fx_scale(_ptr(y), _ptr(out), B * Ch, T, _ptr(gain), _stream()), "rfx_fx_scale")
-        return out.view(x.shape)
+        return self.normalize.normalize_joint(y.view(B, Ch, T)).view(x.shape)
 
 
 # label order: column k of dry / wet label tensors (effects.py:699-707)

@@ -50,14 +50,13 @@ def main():
     norm = E.LoudnessNormalize(SR, target_lufs_db=-20)
     for label, (B, kw) in CONFIGS.items():
         x = (torch.randn(B, 1, a.T, generator=torch.Generator().manual_seed(1)) * 0.1).to(dev)
-        order = (kw["effects_to_keep"], kw["effects_to_remove"], kw["num_kept_effects"], kw["num_removed_effects"],
-                 kw["shuffle_kept_effects"], kw["shuffle_removed_effects"])
+        recipe = D.EffectRecipe(fx, **kw)
 
         def per_item():
-            return [D.process_effects(x[b], fx, *order, norm) for b in range(B)]
+            return [recipe.process(x[b], norm) for b in range(B)]
 
         def batched(row_tables):
-            return D.process_effects_batch(x, [D.plan_effects(fx, *order) for _ in range(B)], fx, norm, row_tables=row_tables)
+            return D.process_effects_batch(x, [recipe.plan() for _ in range(B)], fx, norm, row_tables=row_tables)
 
         print(f"{label}, T = {a.T}: ms per batch over {a.batches} batches after {a.warmup} warm-up batches")
         med = {}
