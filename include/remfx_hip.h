@@ -633,6 +633,34 @@ int rfx_sisdr_finish(const double* sums, int32_t R, int64_t L, int32_t zero_mean
  * auraloss MultiResolutionSTFTLoss behind models.py:320. */
 int rfx_mrstft_combine(const float* const* sums, const int64_t* n, int32_t nres, int32_t R, int32_t per_example_sc, float* out,
                        void* stream);
+/* One auraloss STFTLoss resolution with a frequency scale and all three magnitude terms (auraloss.freq.STFTLoss.forward with
+ * scale="mel" and w_sc / w_log_mag / w_lin_mag; the class behind models.py:320 built with other keywords than the reference passes):
+ * replaces torch.matmul(self.fb, x_mag) on both magnitude spectra, SpectralConvergenceLoss and the two STFTMagnitudeLoss passes.
+ * xc, yc: frame-major complex spectra [R][frames][bins][2] (rfx_fft_analysis, RFX_STFT_COMPLEX_FM).  |X| = sqrt(max(re^2 + im^2, eps)).
+ * The filter bank is BANDED: fb_idx [n_out][3] int32 = { first bin, length, offset into fb_w } per filter, fb_w = the n_w weights of
+ * filter 0, 1, ... packed (first + length <= bins, offset + length <= n_w: the caller guarantees it).  Mx = fb |X|, My = fb |Y|.
+ * fb_idx == NULL: the identity (linear scale), n_out = bins.
+ * sums [R][4] fp64 = { sum (My - Mx)^2, sum My^2, sum |log Mx - log My|, sum |Mx - My| } per row, written, not accumulated: every
+ * workgroup stores its partial into its own slot of ws -- rfx_stft_scaled_loss_ws(R, frames) doubles, no initialisation needed -- and
+ * the slots are added in order (bit-reproducible, no zero fill, no atomics).  mx / my (both or neither): [R][frames][n_out] fp32, the
+ * projected magnitudes for rfx_stft_scaled_loss_grad.  bins * 8 + n_w * 4 bytes of LDS must fit 64 KiB (-1 otherwise). */
+int64_t rfx_stft_scaled_loss_ws(int32_t R, int32_t frames);
+int rfx_stft_scaled_loss(const float* xc, const float* yc, int32_t R, int32_t frames, int32_t bins, const int32_t* fb_idx,
+                         const float* fb_w, int32_t n_out, int32_t n_w, float eps, double* ws, double* sums, float* mx, float* my,
+                         void* stream);
+/* Its backward: gxc [R][frames][bins][2] = d|X| * X / |X| (0 where the power was clamped), d|X| = fb^T dM,
+ * dM = w_sc (Mx - My) / (sqrt(A) sqrt(B)) + (w_lm / Mx + w_lin) sign(Mx - My) with A, B of the row (per_example_sc) or of the batch.
+ * fbt_idx [bins][3] / fbt_w: the band of the TRANSPOSED bank, { first filter, count, offset } per bin -- every bin gathers from its
+ * (at most two, for a triangular bank) filters: no scatter, no atomics.  NULL: identity.  w_sc, w_lm, w_lin carry the 1 / nres,
+ * 1 / R and 1 / (R n) factors; gup (may be NULL) as for rfx_stft_loss_grad.  gxc then goes through rfx_fft_synthesis. */
+int rfx_stft_scaled_loss_grad(const float* xc, const float* mx, const float* my, int32_t R, int32_t frames, int32_t bins,
+                              const int32_t* fbt_idx, const float* fbt_w, int32_t n_out, float eps, const double* sums,
+                              int32_t per_example_sc, float w_sc, float w_lm, float w_lin, const float* gup, float* gxc, void* stream);
+/* rfx_mrstft_combine on the fp64 [R][4] row sums of rfx_stft_scaled_loss with auraloss's term weights:
+ * out[0] = mean_k (w_sc sc_k + w_lm lm_k + w_lin lin_k), lin_k = sum_r D_r / (R n_k), n[k] = frames * n_out; a term whose weight is
+ * zero is not evaluated (auraloss MultiResolutionSTFTLoss / STFTLoss.forward).  sums / n are HOST arrays of nres <= 8 entries. */
+int rfx_mrstft_combine_w(const double* const* sums, const int64_t* n, int32_t nres, int32_t R, int32_t per_example_sc, float w_sc,
+                         float w_lm, float w_lin, float* out, void* stream);
 
 /* ---- optimiser (flat fp32 buffers) ----------------------------------------------
  * Replaces torch.optim.AdamW.step + Lightning gradient_clip_val (models.py:185-191,

@@ -148,6 +148,11 @@ SIGNATURES = {
     "rfx_sisdr_sums": [_P, _P, _I32, _I64, _I64, _I64, _P, _P, _P],
     "rfx_sisdr_finish": [_P, _I32, _I64, _I32, C.c_double, _P, _P],
     "rfx_mrstft_combine": [_P, _P, _I32, _I32, _I32, _P, _P],
+    "rfx_stft_scaled_loss_ws": [_I32, _I32],
+    "rfx_stft_scaled_loss": [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P, _P],
+    "rfx_stft_scaled_loss_grad": [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, C.c_float, _P, _I32, C.c_float, C.c_float, C.c_float,
+                                  _P, _P, _P],
+    "rfx_mrstft_combine_w": [_P, _P, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float, _P, _P],
     "rfx_zero": [_P, _I64, _P],
     "rfx_sumsq": [_P, _I64, _P, _P, _P],
     "rfx_clip_coef": [_P, C.c_float, C.c_float, _P, _P, _P],
@@ -255,7 +260,7 @@ SIGNATURES = {
     "rfx_cl_dconv_bwd": [_P, _P, _P],
 }
 
-_RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",
+_RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_stft_scaled_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",
           "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats", "rfx_fx_normalize_ws_bytes"}
 _lib = None
 

@@ -137,6 +137,168 @@ __global__ __launch_bounds__(64) void mrstft_combine_kernel(const MrCombineArgs 
   if (lane == 0) a.out[0] = (float)(total / (double)a.nres);
 }
 
+// ---- auraloss STFTLoss with a frequency scale (scale="mel") and the three magnitude term weights -------------------------------
+// A triangular filter bank is banded: filter f covers bins [first_f, first_f + len_f) and every bin feeds at most two filters, so the
+// (n_out x bins) matmul auraloss runs on the magnitudes (torch.matmul(self.fb, x_mag)) is ~2 * bins multiply-adds per frame and
+// belongs in the pass that already walks the spectra.  Band tables: idx[n][3] = { first, len, offset into w }, w = the weights of
+// row 0, row 1, ... packed.  The forward takes the band of fb (one row per filter), the backward the band of fb^T (one row per bin).
+//
+// Forward, one workgroup per (row, frame group), one frame at a time:
+//   1. 256 threads read the frame's line of X and Y and store { |X|, |Y| } (sqrt of the clamped power) as one float2 per bin in LDS;
+//   2. eight lanes per filter walk its band (lane j takes elements j, j + 8, ...), so a ds_read_b64 fetches both magnitudes of a bin
+//      and the eight lanes of a filter read 64 contiguous bytes; the partial dot products meet in a fixed xor butterfly (4, 2, 1);
+//   3. lane 0 of the eight adds the filter's four terms to its fp64 partials and stores Mx, My for the backward.
+// The magnitudes of a frame are ONE line (no row pitch to pad): two lanes of a 32-lane half collide only when their bins differ by a
+// non-zero multiple of 32 (64 banks / 2 dwords), which the band starts of neighbouring filters decide, not a pitch.  The weights sit
+// behind the magnitudes in LDS, staged once per workgroup.
+// Identity (idx == NULL, the linear scale with non-default weights): Mx = |X| per bin, no LDS.
+__global__ __launch_bounds__(256) void stft_scaled_loss_kernel(const float2* __restrict__ xc, const float2* __restrict__ yc, int frames,
+                                                               int bins, const int32_t* __restrict__ idx, const float* __restrict__ fbw,
+                                                               int n_out, int n_w, float eps, double* __restrict__ slots,
+                                                               float* __restrict__ mx, float* __restrict__ my) {
+  extern __shared__ float2 rfx_scaled_lds_[];
+  float2* mag = rfx_scaled_lds_;                                  // [bins]
+  float* wl = (float*)(rfx_scaled_lds_ + bins);                   // [n_w]
+  const int r = blockIdx.y, tid = threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (idx) {
+    for (int i = tid; i < n_w; i += 256) wl[i] = fbw[i];
+  }
+  for (int fr = blockIdx.x; fr < frames; fr += gridDim.x) {
+    const int64_t line = (int64_t)r * frames + fr;
+    const float2* xr = xc + line * bins;
+    const float2* yr = yc + line * bins;
+    if (!idx) {
+      for (int b = tid; b < bins; b += 256) {
+        const float2 x = xr[b], y = yr[b];
+        const float a = sqrtf(fmaxf(rfx_pow2(x.x, x.y), eps)), c = sqrtf(fmaxf(rfx_pow2(y.x, y.y), eps));
+        const float d = c - a;
+        acc[0] += (double)d * (double)d; acc[1] += (double)c * (double)c;
+        acc[2] += (double)fabsf(logf(a) - logf(c)); acc[3] += (double)fabsf(a - c);
+        if (mx) { mx[line * n_out + b] = a; my[line * n_out + b] = c; }
+      }
+      continue;
+    }
+    __syncthreads();                                              // the previous frame's band walks are done (and wl is staged)
+    for (int b = tid; b < bins; b += 256) {
+      const float2 x = xr[b], y = yr[b];
+      mag[b] = make_float2(sqrtf(fmaxf(rfx_pow2(x.x, x.y), eps)), sqrtf(fmaxf(rfx_pow2(y.x, y.y), eps)));
+    }
+    __syncthreads();
+    const int j = tid & 7;
+    for (int f0 = 0; f0 < n_out; f0 += 32) {                      // wave-uniform trip count: the shuffles below run in every lane
+      const int f = f0 + (tid >> 3);
+      int first = 0, len = 0, off = 0;
+      if (f < n_out) { first = idx[3 * f]; len = idx[3 * f + 1]; off = idx[3 * f + 2]; }
+      float a = 0.f, c = 0.f;
+      for (int i = j; i < len; i += 8) {
+        const float w = wl[off + i];
+        const float2 m = mag[first + i];
+        a = fmaf(w, m.x, a); c = fmaf(w, m.y, c);
+      }
+#pragma unroll
+      for (int o = 4; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); c += __shfl_xor(c, o, 64); }
+      if (j == 0 && f < n_out) {
+        const float d = c - a;
+        acc[0] += (double)d * (double)d; acc[1] += (double)c * (double)c;
+        acc[2] += (double)fabsf(logf(a) - logf(c)); acc[3] += (double)fabsf(a - c);
+        if (mx) { mx[line * n_out + f] = a; my[line * n_out + f] = c; }
+      }
+    }
+  }
+  rfx_block_store_slot<4>(acc, slots, r, gridDim.x, blockIdx.x);
+}
+
+// G = d|X| * X / |X| with d|X| = fb^T dM and, per filter,
+//   dM = ksc (Mx - My) + (w_lm / Mx + w_lin) sign(Mx - My),   ksc = w_sc / (sqrt(A) sqrt(B))
+// (A, B of the row, or of the whole batch when !per_example; the sign of log Mx - log My is the sign of Mx - My, so identical signals
+// get an exactly zero gradient).  One workgroup per (row, frame group): the frame's dM in LDS, then every bin GATHERS from the filters
+// of its row of the transposed band -- no scatter, no atomics.  tidx == NULL: identity.
+__global__ __launch_bounds__(256) void stft_scaled_loss_grad_kernel(const float2* __restrict__ xc, const float* __restrict__ mx,
+                                                                    const float* __restrict__ my, int R, int frames, int bins, int n_out,
+                                                                    const int32_t* __restrict__ tidx, const float* __restrict__ tw,
+                                                                    float eps, const double* __restrict__ sums, int per_example,
+                                                                    float w_sc, float w_lm, float w_lin, const float* __restrict__ gup,
+                                                                    float2* __restrict__ gxc) {
+  extern __shared__ float2 rfx_scaled_lds_[];
+  float* dm = (float*)rfx_scaled_lds_;                            // [n_out]
+  __shared__ float ksc_s;
+  const int r = blockIdx.y, tid = threadIdx.x;
+  if (gup) { const float u = gup[0]; w_sc *= u; w_lm *= u; w_lin *= u; }
+  if (tid < 64) {
+    double A = 0.0, B = 0.0;
+    if (per_example) { A = sums[4 * r]; B = sums[4 * r + 1]; }
+    else {
+      for (int q = tid; q < R; q += 64) { A += sums[4 * q]; B += sums[4 * q + 1]; }     // rows in lane order, fixed butterfly
+      A = rfx_wave_sum_d(A); B = rfx_wave_sum_d(B);
+    }
+    if (tid == 0) ksc_s = (A > 0.0 && B > 0.0) ? (float)((double)w_sc / (sqrt(A) * sqrt(B))) : 0.f;
+  }
+  __syncthreads();
+  const float ksc = ksc_s;
+  for (int fr = blockIdx.x; fr < frames; fr += gridDim.x) {
+    const int64_t line = (int64_t)r * frames + fr;
+    __syncthreads();                                              // the previous frame's gathers are done
+    for (int f = tid; f < n_out; f += 256) {
+      const float a = mx[line * n_out + f], c = my[line * n_out + f];
+      const float sg = a > c ? 1.f : (a < c ? -1.f : 0.f);
+      dm[f] = ksc * (a - c) + (w_lm / a + w_lin) * sg;
+    }
+    __syncthreads();
+    const float2* xr = xc + line * bins;
+    float2* gr = gxc + line * bins;
+    for (int b = tid; b < bins; b += 256) {
+      const float2 x = xr[b];
+      const float px = rfx_pow2(x.x, x.y);
+      float2 g = make_float2(0.f, 0.f);
+      if (px > eps) {                                             // clamp(min=eps) passes no gradient below eps
+        float d;
+        if (tidx) {
+          const int first = tidx[3 * b], len = tidx[3 * b + 1], off = tidx[3 * b + 2];
+          d = 0.f;
+          for (int i = 0; i < len; ++i) d = fmaf(tw[off + i], dm[first + i], d);
+        } else {
+          d = dm[b];
+        }
+        const float s = d / sqrtf(px);
+        g.x = s * x.x; g.y = s * x.y;
+      }
+      gr[b] = g;
+    }
+  }
+}
+
+// rfx_mrstft_combine with the three term weights of auraloss STFTLoss (w_sc, w_log_mag, w_lin_mag) on the fp64 [R][4] row sums of
+// rfx_stft_scaled_loss: out[0] = (1 / nres) sum_k (w_sc sc_k + w_lm lm_k + w_lin lin_k), lin_k = sum_r D_r / (R n_k).  A term whose
+// weight is zero is left out, as auraloss does not evaluate it.  One wave, rows in lane order, fixed butterfly.
+struct MrCombineWArgs {
+  const double* sums[8];
+  double n[8];
+  int nres, R, per_example;
+  float w_sc, w_lm, w_lin;
+  float* out;
+};
+__global__ __launch_bounds__(64) void mrstft_combine_w_kernel(const MrCombineWArgs a) {
+  const int lane = threadIdx.x;
+  double total = 0.0;
+  for (int k = 0; k < a.nres; ++k) {
+    const double* s = a.sums[k];
+    double sc = 0.0, sa = 0.0, sb = 0.0, sl = 0.0, sd = 0.0;
+    for (int r = lane; r < a.R; r += 64) {
+      const double A = s[4 * r], B = s[4 * r + 1];
+      sc += sqrt(A) / sqrt(B);
+      sa += A; sb += B; sl += s[4 * r + 2]; sd += s[4 * r + 3];
+    }
+    sc = rfx_wave_sum_d(sc); sa = rfx_wave_sum_d(sa); sb = rfx_wave_sum_d(sb); sl = rfx_wave_sum_d(sl); sd = rfx_wave_sum_d(sd);
+    const double scv = a.per_example ? sc / (double)a.R : sqrt(sa) / sqrt(sb);
+    const double cells = (double)a.R * a.n[k];
+    if (a.w_sc != 0.f) total += (double)a.w_sc * scv;
+    if (a.w_lm != 0.f) total += (double)a.w_lm * (sl / cells);
+    if (a.w_lin != 0.f) total += (double)a.w_lin * (sd / cells);
+  }
+  if (lane == 0) a.out[0] = (float)(total / (double)a.nres);
+}
+
 // The scalar tail of auraloss SISDRLoss over the fp64 row sums of rfx_sisdr_sums: out[0] = -mean_r 10 log10(|alpha t|^2 / (|x - alpha t|^2 + eps) + eps),
 // alpha = <x, t> / (|t|^2 + eps), after removing the row means when zero_mean (the ~22 one-element torch launches it replaces ran
 // twice per training step).  One wave, rows in lane order, fixed butterfly.
@@ -223,6 +385,58 @@ extern "C" int rfx_mrstft_combine(const float* const* sums, const int64_t* n, in
   }
   a.nres = nres; a.R = R; a.per_example = per_example_sc; a.out = out;
   hipLaunchKernelGGL(mrstft_combine_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+// one slot per workgroup: frame groups per row
+static int scaled_grid(int frames) { return frames < 1 ? 1 : (frames > 64 ? 64 : frames); }
+static size_t scaled_lds(int bins, int n_w) { return (size_t)bins * sizeof(float2) + (size_t)n_w * sizeof(float); }
+#define RFX_SCALED_LDS_MAX (64 * 1024)
+extern "C" int64_t rfx_stft_scaled_loss_ws(int32_t R, int32_t frames) {
+  if (R <= 0 || frames <= 0) return 0;
+  return (int64_t)4 * R * scaled_grid(frames);
+}
+extern "C" int rfx_stft_scaled_loss(const float* xc, const float* yc, int32_t R, int32_t frames, int32_t bins, const int32_t* fb_idx,
+                                    const float* fb_w, int32_t n_out, int32_t n_w, float eps, double* ws, double* sums, float* mx,
+                                    float* my, void* stream) {
+  if (!xc || !yc || !sums || !ws || R <= 0 || frames <= 0 || bins <= 0 || (!mx) != (!my)) return -1;
+  if (fb_idx ? (!fb_w || n_out <= 0 || n_w <= 0) : (n_out != bins)) return -1;
+  const size_t lds = fb_idx ? scaled_lds(bins, n_w) : 0;
+  if (lds > RFX_SCALED_LDS_MAX) return -1;
+  const int g = scaled_grid(frames);
+  hipLaunchKernelGGL(stft_scaled_loss_kernel, dim3(g, R), dim3(256), lds, (hipStream_t)stream, (const float2*)xc, (const float2*)yc,
+                     frames, bins, fb_idx, fb_w, n_out, fb_idx ? n_w : 0, eps, ws, mx, my);
+  RFX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rfx_slot_sum_kernel<double>, RFX_SLOT_SUM_GRID(4 * R), 0, (hipStream_t)stream, ws, R, g, 4, sums);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_stft_scaled_loss_grad(const float* xc, const float* mx, const float* my, int32_t R, int32_t frames, int32_t bins,
+                                         const int32_t* fbt_idx, const float* fbt_w, int32_t n_out, float eps, const double* sums,
+                                         int32_t per_example_sc, float w_sc, float w_lm, float w_lin, const float* gup, float* gxc,
+                                         void* stream) {
+  if (!xc || !mx || !my || !sums || !gxc || R <= 0 || frames <= 0 || bins <= 0 || n_out <= 0) return -1;
+  if (fbt_idx ? !fbt_w : (n_out != bins)) return -1;
+  const size_t lds = (size_t)n_out * sizeof(float);
+  if (lds > RFX_SCALED_LDS_MAX) return -1;
+  const int g = frames > 512 ? 512 : frames;
+  hipLaunchKernelGGL(stft_scaled_loss_grad_kernel, dim3(g, R), dim3(256), lds, (hipStream_t)stream, (const float2*)xc, mx, my, R,
+                     frames, bins, n_out, fbt_idx, fbt_w, eps, sums, per_example_sc, w_sc, w_lm, w_lin, gup, (float2*)gxc);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_mrstft_combine_w(const double* const* sums, const int64_t* n, int32_t nres, int32_t R, int32_t per_example_sc,
+                                    float w_sc, float w_lm, float w_lin, float* out, void* stream) {
+  if (!sums || !n || !out || nres <= 0 || nres > 8 || R <= 0) return -1;
+  MrCombineWArgs a;
+  for (int k = 0; k < 8; ++k) { a.sums[k] = nullptr; a.n[k] = 1.0; }
+  for (int k = 0; k < nres; ++k) {
+    if (!sums[k] || n[k] <= 0) return -1;
+    a.sums[k] = sums[k];
+    a.n[k] = (double)n[k];
+  }
+  a.nres = nres; a.R = R; a.per_example = per_example_sc; a.w_sc = w_sc; a.w_lm = w_lm; a.w_lin = w_lin; a.out = out;
+  hipLaunchKernelGGL(mrstft_combine_w_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
   RFX_CHECK_LAUNCH();
   return 0;
 }

@@ -6,12 +6,22 @@ Mirrors the auraloss objects the reference instantiates (remfx/models.py:7-8,
       mean over resolutions of [ ||Y|-|X||_F / ||Y||_F  +  mean |log|X| - log|Y|| ]
   SISDRLoss(zero_mean=True, eps=1e-8)
   nn.L1Loss
-`n_bins` / `sample_rate` kwargs are accepted and inert, as upstream with scale=None
-(SURVEY App. B Q4).
+The class takes auraloss's keywords under auraloss's names.  With scale=None and weights (1, 1, 0) -- what the reference
+builds -- `n_bins` / `sample_rate` are inert, as upstream, and the path above runs.  Otherwise:
+  scale="mel"            |X|, |Y| go through a librosa-default mel filter bank (`mel_filterbank`) of `n_bins` filters at
+                         `sample_rate` before the terms: rfx_stft_scaled_loss walks the BANDED bank inside the reduction pass
+  w_sc, w_log_mag, w_lin_mag   per resolution w_sc sc + w_log_mag mean|log Mx - log My| + w_lin_mag mean|Mx - My|
+                         (rfx_mrstft_combine_w; gradient rfx_stft_scaled_loss_grad + rfx_fft_synthesis)
+  scale="chroma", w_phs != 0, perceptual_weighting, scale_invariance, output != "loss", reduction != "mean", mag_distance != "L1",
+  a window other than hann      raise NotImplementedError at construction: nothing is accepted and dropped.
+One deliberate difference: a mel filter without a non-zero weight (more filters than the low bins can carry) makes auraloss return
+NaN (log 0 - log 0); here the constructor raises ValueError naming the resolution and the count.
+`STFTLoss` is the single-resolution class auraloss exports, over the same function.
 """
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -25,6 +35,7 @@ WIN_LENGTHS = (600, 1200, 240)
 
 
 FUSED_GRAD = os.environ.get("RFX_LOSS_FUSED_GRAD", "1") != "0"    # A/B: 0 = rfx_stft_loss_grad_m + rfx_fft_synthesis as two launches
+PAIRED = os.environ.get("RFX_LOSS_PAIRED", "1") != "0"            # A/B: 0 = two analyses + rfx_stft_loss_reduce / _grad at every n_fft
 
 _MEMO = None
 
@@ -93,9 +104,147 @@ def _pair_sums(x2, y2, n_fft, hop, win, w, eps, store):
     return sums, X, ym
 
 
+DEFAULT_WEIGHTS = (1.0, 1.0, 0.0)        # auraloss: w_sc, w_log_mag, w_lin_mag
+
+
+def _hz_to_mel(f):
+    """Slaney's mel scale (librosa.hz_to_mel, htk=False): linear below 1 kHz (200 / 3 Hz per mel), then log with step ln(6.4) / 27."""
+    f = np.asarray(f, dtype=np.float64)
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+    return np.where(f >= min_log_hz, min_log_mel + np.log(np.maximum(f, min_log_hz) / min_log_hz) / logstep, f / f_sp)
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
+    return np.where(m >= min_log_mel, min_log_hz * np.exp(logstep * (m - min_log_mel)), f_sp * m)
+
+
+def mel_filterbank(sample_rate, n_fft, n_mels):
+    """librosa.filters.mel(sr=sample_rate, n_fft=n_fft, n_mels=n_mels) with its defaults, restated (librosa is not a dependency):
+    Slaney mel scale, fmin = 0, fmax = sr / 2, triangles between n_mels + 2 edge frequencies equally spaced in mel, each scaled by
+    2 / (f[i + 2] - f[i]) (Slaney area normalisation).  fp64 arithmetic; returns fp32 (n_mels, n_fft / 2 + 1) -- what
+    auraloss.freq.STFTLoss(scale="mel") multiplies the magnitudes by."""
+    bins = n_fft // 2 + 1
+    freqs = np.linspace(0.0, sample_rate / 2.0, bins)
+    edges = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sample_rate / 2.0), n_mels + 2))
+    fdiff = np.diff(edges)
+    ramps = edges[:, None] - freqs[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    w = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (edges[2:] - edges[:-2]))[:, None]
+    return torch.from_numpy(w.astype(np.float32))
+
+
+def pack_banded(dense):
+    """(rows, cols) matrix -> (idx int32 [rows, 3], w fp32 [n_w]): per row the first non-zero column, the length up to the last one
+    and the offset of its weights in w -- the form rfx_stft_scaled_loss (fb) and rfx_stft_scaled_loss_grad (fb^T) take.  Exact:
+    interior zeros of a row are kept, so any matrix round-trips; a triangular bank costs ~2 * cols weights instead of rows * cols."""
+    d = np.asarray(dense, dtype=np.float32)
+    idx, w = np.zeros((d.shape[0], 3), dtype=np.int32), []
+    for r in range(d.shape[0]):
+        nz = np.nonzero(d[r])[0]
+        first, ln = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if nz.size else (0, 0)
+        idx[r] = (first, ln, sum(len(c) for c in w))
+        w.append(d[r, first:first + ln])
+    w = np.concatenate(w) if w else np.zeros(0, dtype=np.float32)
+    if w.size == 0:
+        w = np.zeros(1, dtype=np.float32)
+    return torch.from_numpy(idx), torch.from_numpy(np.ascontiguousarray(w))
+
+
+class _Bank:
+    """One resolution's banded filter bank on the device: the band of fb (forward) and of fb^T (backward)."""
+
+    def __init__(self, idx, w, tidx, tw, n_out, bins):
+        self.idx, self.w, self.tidx, self.tw, self.n_out, self.bins = idx, w, tidx, tw, n_out, bins
+
+
+def _scaled_sums(X, Y, bank, eps, weights, store):
+    """Row sums [R, 4] fp64 of one resolution through rfx_stft_scaled_loss (+ Mx, My with store=True).  Memoised next to the spectra:
+    metric-style repeats of the same (spectra, filter bank, weights) evaluation inside stft_memo() reuse them."""
+    R, frames, bins = X.shape[:3]
+    n_out = bank.n_out if bank is not None else bins
+    key = ("ssums", X.data_ptr(), Y.data_ptr(), eps, bank.w.data_ptr() if bank is not None else 0, weights)
+    hit = _MEMO.get(key) if _MEMO is not None else None
+    if hit is not None and (hit[1] is not None or not store):
+        return hit
+    sums = torch.empty((R, 4), device=X.device, dtype=torch.float64)         # written, not accumulated: no zero fill
+    mx = torch.empty((R, frames, n_out), device=X.device, dtype=torch.float32) if store else None
+    my = torch.empty((R, frames, n_out), device=X.device, dtype=torch.float32) if store else None
+    ws = torch.empty(int(_lib.lib().rfx_stft_scaled_loss_ws(R, frames)), device=X.device, dtype=torch.float64)   # one slot per workgroup
+    if bank is not None and (bank.bins != bins or bank.w.device != X.device):
+        raise ValueError(f"filter bank for {bank.bins} bins on {bank.w.device}, spectrum has {bins} on {X.device}")
+    check(_lib.lib().rfx_stft_scaled_loss(_ptr(X), _ptr(Y), R, frames, bins, _ptr(bank.idx if bank is not None else None),
+                                          _ptr(bank.w if bank is not None else None), n_out,
+                                          bank.w.numel() if bank is not None else 0, eps, _ptr(ws), _ptr(sums), _ptr(mx), _ptr(my),
+                                          _stream()), "rfx_stft_scaled_loss")
+    hit = (sums, mx, my)
+    if _MEMO is not None and ("spec", X.data_ptr()) in _MEMO and ("spec", Y.data_ptr()) in _MEMO:
+        _MEMO[key] = hit                                                     # both spectra are held by the memo: pointers stay valid
+    return hit
+
+
+def _scaled_forward(ctx, x, y, fft_sizes, hops, wins, eps, per_example_sc, weights, banks):
+    """auraloss STFTLoss.forward with a frequency scale and / or non-default term weights, per resolution: two memoised spectra,
+    rfx_stft_scaled_loss, then one rfx_mrstft_combine_w over all resolutions."""
+    _req(x, "input"); _req(y, "target")
+    L = x.shape[-1]
+    x2, y2 = x.reshape(-1, L).contiguous(), y.reshape(-1, L).contiguous()
+    R = x2.shape[0]
+    saved = []
+    for (n_fft, hop, win), bank in zip(zip(fft_sizes, hops, wins), banks):
+        w = stft.hann(win, x.device)
+        X = _spectrum(x2, n_fft, hop, win, w)
+        Y = _spectrum(y2, n_fft, hop, win, w)
+        sums, mx, my = _scaled_sums(X, Y, bank, eps, weights, ctx.needs_input_grad[0])
+        n_out = bank.n_out if bank is not None else X.shape[2]
+        saved.append((X, mx, my, sums, X.shape[1] * n_out, n_fft, hop, win, bank))
+    nres, total = len(saved), None
+    for c0 in range(0, nres, 8):                   # rfx_mrstft_combine_w takes up to 8 resolutions per launch
+        part = saved[c0:c0 + 8]
+        m = len(part)
+        t = torch.empty((), device=x.device, dtype=torch.float32)
+        sp = (C.c_void_p * m)(*[_ptr(e[3]) for e in part])
+        nn_ = (C.c_int64 * m)(*[int(e[4]) for e in part])
+        check(_lib.lib().rfx_mrstft_combine_w(sp, nn_, m, R, 1 if per_example_sc else 0, weights[0], weights[1], weights[2], _ptr(t),
+                                              _stream()), "rfx_mrstft_combine_w")
+        total = t if nres <= 8 else (t * (m / nres) if total is None else total + t * (m / nres))
+    ctx.scaled = True
+    ctx.saved = saved
+    ctx.meta = (x.shape, R, L, eps, per_example_sc, nres, weights)
+    return total
+
+
+def _scaled_backward(ctx, g):
+    shape, R, L, eps, per_example_sc, nres, (w_sc, w_lm, w_lin) = ctx.meta
+    gx = torch.empty((R, L), device=g.device, dtype=torch.float32)        # the first resolution writes it, the others add (accum)
+    gup = g.detach().reshape(1).float().contiguous()                      # upstream scalar gradient stays on the device
+    for ires, (X, mx, my, sums, n, n_fft, hop, win, bank) in enumerate(ctx.saved):
+        frames, bins = X.shape[1], X.shape[2]
+        G = torch.empty_like(X)
+        check(_lib.lib().rfx_stft_scaled_loss_grad(
+            _ptr(X), _ptr(mx), _ptr(my), R, frames, bins, _ptr(bank.tidx if bank is not None else None),
+            _ptr(bank.tw if bank is not None else None), n // frames, eps, _ptr(sums), 1 if per_example_sc else 0,
+            w_sc / (nres * R) if per_example_sc else w_sc / nres, w_lm / (nres * R * n), w_lin / (nres * R * n), _ptr(gup), _ptr(G),
+            _stream()), "rfx_stft_scaled_loss_grad")
+        d = stft._desc(R, L, n_fft, hop, win, bins, 0, frames, _SPEC_MODE, in_mode=0, herm=0, scale=1.0, accum=1 if ires else 0)
+        check(_lib.lib().rfx_fft_synthesis(C.byref(d), _ptr(G), _ptr(stft.hann(win, g.device)), None, _ptr(stft.syn_ws(d, g.device)),
+                                           _ptr(gx), _stream()), "rfx_fft_synthesis")
+    ctx.saved = None
+    return gx.view(shape)
+
+
 class _MRSTFTFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, y, fft_sizes, hops, wins, eps, per_example_sc):
+    def forward(ctx, x, y, fft_sizes, hops, wins, eps, per_example_sc, *scaled):
+        # scaled = (weights, banks): the three term weights and one banded filter bank (or None) per resolution; absent, or the
+        # default (1, 1, 0) without a bank: the path below, untouched
+        ctx.n_extra, ctx.scaled = len(scaled), False
+        if scaled and (tuple(scaled[0]) != DEFAULT_WEIGHTS or any(b is not None for b in scaled[1])):
+            return _scaled_forward(ctx, x, y, fft_sizes, hops, wins, eps, per_example_sc, tuple(scaled[0]), scaled[1])
         _req(x, "input"); _req(y, "target")
         L = x.shape[-1]
         x2, y2 = x.reshape(-1, L).contiguous(), y.reshape(-1, L).contiguous()
@@ -103,7 +252,7 @@ class _MRSTFTFn(torch.autograd.Function):
         saved, total = [], None
         for n_fft, hop, win in zip(fft_sizes, hops, wins):
             w = stft.hann(win, x.device)
-            if n_fft in (512, 1024, 2048):
+            if PAIRED and n_fft in (512, 1024, 2048):
                 # both spectra of a frame from one complex FFT, sums in its epilogue: no spectrum is written unless the backward
                 # needs it, and then only the prediction's + the target's magnitudes
                 sums, X, Y = _pair_sums(x2, y2, n_fft, hop, win, w, eps, ctx.needs_input_grad[0])
@@ -141,6 +290,8 @@ class _MRSTFTFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.scaled:
+            return (_scaled_backward(ctx, g),) + (None,) * (6 + ctx.n_extra)
         shape, R, L, eps, per_example_sc, nres = ctx.meta
         gx = torch.empty((R, L), device=g.device, dtype=torch.float32)    # the first resolution writes it, the others add (accum)
         gval = 1.0               # the scalar upstream gradient stays on the device: the kernels multiply their weights by *gup
@@ -172,19 +323,90 @@ class _MRSTFTFn(torch.autograd.Function):
             check(_lib.lib().rfx_fft_synthesis(C.byref(d), _ptr(G), _ptr(w), None, _ptr(stft.syn_ws(d, g.device)), _ptr(gx), _stream()),
                   "rfx_fft_synthesis")
         ctx.saved = None
-        return gx.view(shape), None, None, None, None, None, None
+        return (gx.view(shape),) + (None,) * (6 + ctx.n_extra)
+
+
+def _check_honoured(scale, w_phs, perceptual_weighting, scale_invariance, output, reduction, mag_distance, window):
+    """auraloss keywords this port does not implement raise here instead of being accepted and dropped."""
+    bad = []
+    if scale not in (None, "mel"):
+        bad.append(f"scale={scale!r} (None and 'mel' are implemented)")
+    if w_phs != 0:
+        bad.append(f"w_phs={w_phs!r} (the phase term)")
+    if perceptual_weighting:
+        bad.append("perceptual_weighting=True (the A-weighting prefilter)")
+    if scale_invariance:
+        bad.append("scale_invariance=True")
+    if output != "loss":
+        bad.append(f"output={output!r}")
+    if reduction != "mean":
+        bad.append(f"reduction={reduction!r}")
+    if mag_distance != "L1":
+        bad.append(f"mag_distance={mag_distance!r}")
+    if window != "hann_window":
+        bad.append(f"window={window!r}")
+    if bad:
+        raise NotImplementedError("MultiResolutionSTFTLoss / STFTLoss on HIP kernels does not implement: " + "; ".join(bad))
 
 
 class MultiResolutionSTFTLoss(nn.Module):
-    def __init__(self, fft_sizes=FFT_SIZES, hop_sizes=HOP_SIZES, win_lengths=WIN_LENGTHS, n_bins=None,
-                 sample_rate=None, eps=1e-8, per_example_sc=True, **kwargs):
+    """auraloss.freq.MultiResolutionSTFTLoss with auraloss's keyword names and defaults (module docstring: what is implemented and
+    what raises).  `per_example_sc` picks the spectral-convergence form of auraloss >= 0.4 (True) or the older whole-batch norm.
+    With scale="mel" the dense banks are `self.filterbanks` (one fp32 (n_bins, n_fft / 2 + 1) per resolution); they and their banded
+    forms are non-persistent buffers, so `.to(device)` moves them and checkpoints keep their keys."""
+
+    def __init__(self, fft_sizes=FFT_SIZES, hop_sizes=HOP_SIZES, win_lengths=WIN_LENGTHS, window="hann_window", w_sc=1.0,
+                 w_log_mag=1.0, w_lin_mag=0.0, w_phs=0.0, sample_rate=None, scale=None, n_bins=None, perceptual_weighting=False,
+                 scale_invariance=False, eps=1e-8, output="loss", reduction="mean", mag_distance="L1", device=None,
+                 per_example_sc=True):
         super().__init__()
         self.fft_sizes, self.hop_sizes, self.win_lengths = tuple(fft_sizes), tuple(hop_sizes), tuple(win_lengths)
+        if not len(self.fft_sizes) == len(self.hop_sizes) == len(self.win_lengths):
+            raise ValueError("fft_sizes, hop_sizes and win_lengths need one entry per resolution")
         self.eps, self.per_example_sc = eps, per_example_sc
+        _check_honoured(scale, w_phs, perceptual_weighting, scale_invariance, output, reduction, mag_distance, window)
+        self.scale, self.n_bins, self.sample_rate = scale, n_bins, sample_rate
+        self.weights = (float(w_sc), float(w_log_mag), float(w_lin_mag))
+        self._nbank = 0
+        if scale == "mel":
+            if n_bins is None or sample_rate is None:
+                raise ValueError('scale="mel" needs n_bins (the number of mel filters) and sample_rate')
+            for k, n_fft in enumerate(self.fft_sizes):
+                fb = mel_filterbank(sample_rate, n_fft, n_bins)
+                empty = int((fb.abs().sum(1) == 0).sum())
+                if empty:
+                    raise ValueError(f"mel filter bank of resolution {k} (n_fft={n_fft}, sample_rate={sample_rate}): {empty} of "
+                                     f"{n_bins} filters have no non-zero weight (narrower than a bin); auraloss would return NaN. "
+                                     "Use fewer n_bins or a larger n_fft")
+                idx, w = pack_banded(fb.numpy())
+                tidx, tw = pack_banded(fb.numpy().T)
+                for name, t in (("fb", fb), ("fb_idx", idx), ("fb_w", w), ("fbt_idx", tidx), ("fbt_w", tw)):
+                    self.register_buffer(f"{name}_{k}", t, persistent=False)
+            self._nbank = len(self.fft_sizes)
+
+    @property
+    def filterbanks(self):
+        return [getattr(self, f"fb_{k}") for k in range(self._nbank)]
+
+    def _banks(self):
+        if not self._nbank:
+            return (None,) * len(self.fft_sizes)
+        return tuple(_Bank(getattr(self, f"fb_idx_{k}"), getattr(self, f"fb_w_{k}"), getattr(self, f"fbt_idx_{k}"),
+                           getattr(self, f"fbt_w_{k}"), self.n_bins, n_fft // 2 + 1) for k, n_fft in enumerate(self.fft_sizes))
 
     def forward(self, input, target):
+        if self.scale is None and self.weights == DEFAULT_WEIGHTS:
+            return _MRSTFTFn.apply(input, target, self.fft_sizes, self.hop_sizes, self.win_lengths, self.eps,
+                                   self.per_example_sc)
         return _MRSTFTFn.apply(input, target, self.fft_sizes, self.hop_sizes, self.win_lengths, self.eps,
-                               self.per_example_sc)
+                               self.per_example_sc, self.weights, self._banks())
+
+
+class STFTLoss(MultiResolutionSTFTLoss):
+    """auraloss.freq.STFTLoss: one resolution (auraloss's defaults 1024 / 256 / 1024) of the same function."""
+
+    def __init__(self, fft_size=1024, hop_size=256, win_length=1024, **kwargs):
+        super().__init__(fft_sizes=(fft_size,), hop_sizes=(hop_size,), win_lengths=(win_length,), **kwargs)
 
 
 class _L1Fn(torch.autograd.Function):

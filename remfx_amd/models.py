@@ -127,6 +127,15 @@ class RemFX(_Base):
         return loss
 
 
+def _mrstft(num_bins, sample_rate, mrstft_kwargs=None):
+    """The wrappers' MultiResolutionSTFTLoss: the reference's construction (n_bins = the wrapper's STFT bin count, inert with
+    scale=None) with the optional `mrstft_kwargs` merged over it -- e.g. `+model.network.mrstft_kwargs.scale=mel` plus its own
+    `n_bins` (the number of mel filters, which replaces the wrapper's bin count) on the command line."""
+    kw = dict(n_bins=num_bins, sample_rate=sample_rate)
+    kw.update(dict(mrstft_kwargs) if mrstft_kwargs else {})
+    return MultiResolutionSTFTLoss(**kw)
+
+
 class _RemovalWrapper(nn.Module):
     """forward((x, target)) -> (loss, output); sample(x) -> output; loss = MRSTFT + 100 * L1."""
 
@@ -135,10 +144,10 @@ class _RemovalWrapper(nn.Module):
 
 
 class TCNModel(_RemovalWrapper):
-    def __init__(self, sample_rate, num_bins, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, **kwargs):
         super().__init__()
         self.model = TCN(**kwargs)
-        self.mrstftloss = MultiResolutionSTFTLoss(n_bins=num_bins, sample_rate=sample_rate)
+        self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
 
     def forward(self, batch):
@@ -153,12 +162,12 @@ class TCNModel(_RemovalWrapper):
 
 
 class DemucsModel(_RemovalWrapper):
-    def __init__(self, sample_rate, **kwargs) -> None:
+    def __init__(self, sample_rate, mrstft_kwargs=None, **kwargs) -> None:
         super().__init__()
         from .hdemucs import HDemucs
         self.model = HDemucs(**kwargs)
         self.num_bins = kwargs["nfft"] // 2 + 1
-        self.mrstftloss = MultiResolutionSTFTLoss(n_bins=self.num_bins, sample_rate=sample_rate)
+        self.mrstftloss = _mrstft(self.num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
 
     def forward(self, batch):
@@ -172,7 +181,7 @@ class DemucsModel(_RemovalWrapper):
 
 class OpenUnmixModel(_RemovalWrapper):
     def __init__(self, n_fft: int = 2048, hop_length: int = 512, n_channels: int = 1, alpha: float = 0.3,
-                 sample_rate: int = 22050):
+                 sample_rate: int = 22050, mrstft_kwargs=None):
         super().__init__()
         from .umx import OpenUnmix, Separator
         from .utils import spectrogram
@@ -184,7 +193,7 @@ class OpenUnmixModel(_RemovalWrapper):
         self.model = OpenUnmix(nb_channels=n_channels, nb_bins=self.num_bins)
         self.separator = Separator(target_models={"other": self.model}, nb_channels=n_channels,
                                    sample_rate=sample_rate, n_fft=n_fft, n_hop=hop_length)
-        self.mrstftloss = MultiResolutionSTFTLoss(n_bins=self.num_bins, sample_rate=sample_rate)
+        self.mrstftloss = _mrstft(self.num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
 
     def forward(self, batch):
@@ -199,11 +208,11 @@ class OpenUnmixModel(_RemovalWrapper):
 
 
 class DCUNetModel(_RemovalWrapper):
-    def __init__(self, sample_rate, num_bins, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, **kwargs):
         super().__init__()
         from .dcunet import DCUNet
         self.model = DCUNet(**kwargs)          # asteroid keeps its own sample_rate default (wrapper swallows it)
-        self.mrstftloss = MultiResolutionSTFTLoss(n_bins=num_bins, sample_rate=sample_rate)
+        self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
 
     def forward(self, batch):
@@ -221,12 +230,12 @@ class DPTNetModel(_RemovalWrapper):
     """models.py:327-344: asteroid DPTNet (cfg/model/dptnet.yaml) + MRSTFT + 100 L1; no target crop (the network pads / crops
     its output to the input length)."""
 
-    def __init__(self, sample_rate, num_bins, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, **kwargs):
         super().__init__()
         from .dptnet import DPTNet
         self.model = DPTNet(**kwargs)
         self.num_bins = num_bins
-        self.mrstftloss = MultiResolutionSTFTLoss(n_bins=num_bins, sample_rate=sample_rate)
+        self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
 
     def forward(self, batch):
@@ -346,10 +355,10 @@ class RemFXChainInference(_Base):
     SURVEY 3.3), instead of the reference's batch-1 python loop."""
 
     def __init__(self, models, sample_rate, num_bins, effect_order, classifier=None,
-                 shuffle_effect_order=False, use_all_effect_models=False):
+                 shuffle_effect_order=False, use_all_effect_models=False, mrstft_kwargs=None):
         super().__init__()
         self.model = models                                     # plain dict, as upstream (Q6)
-        self.mrstftloss = MultiResolutionSTFTLoss(n_bins=num_bins, sample_rate=sample_rate)
+        self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
         self.metrics = nn.ModuleDict({"SISDR": SISDRLoss(), "STFT": MultiResolutionSTFTLoss()})
         self.sample_rate = sample_rate
