@@ -818,6 +818,20 @@ int rfx_cl_dconv_bwd(const rfx_cl_dconv_desc* d, float* pgrad, void* stream);
 int rfx_cl_rowsum(const rfx_cl_tensor* x, int32_t N, int32_t A, int32_t B, int32_t C, int32_t G, float scale, float* partial, float* out,
                   int32_t accumulate, void* stream);
 
+/* Segmented long-file inference (remfx_amd/segment.py; the call site is the reference's scripts/remfx_detect.py:44-55, which runs
+ * the whole file as one clip).  hop = L - overlap; segment i of S starts at s_i = min(i * hop, max(T - L, 0)): the last one is
+ * tail-aligned, only T < L is zero-padded (S = 1).  S = 1 for T <= L, else ceil((T - L) / hop) + 1; both calls return -1 when the
+ * caller's S differs.  T, L < 2^30.
+ *   split: x (rows, T) -> out (rows * S, L), out[r * S + i][j] = x[r][s_i + j], zeros beyond T.
+ *   merge: y (rows * S, Lp), Lp = L - lead - trail, clip sample j belonging to input sample s_i + lead + j
+ *          -> out (rows, T - lead - trail) covering input samples [lead, T - trail):
+ *          out[r][t] = sum_i w[t - s_i] y[r * S + i][t - s_i] / sum_i w[t - s_i] over the clips covering t, w[j] = min(j + 1, Lp - j),
+ *          terms in increasing i, fp32.  Needs lead + trail <= overlap.  Each output sample is computed by one thread and stored
+ *          once: no atomics, no zero-filled target, bit-reproducible. */
+int rfx_segment_split(const float* x, float* out, int32_t rows, int64_t T, int32_t L, int32_t hop, int32_t S, void* stream);
+int rfx_segment_merge(const float* y, float* out, int32_t rows, int64_t T, int32_t L, int32_t hop, int32_t lead, int32_t trail,
+                      int32_t S, void* stream);
+
 int rfx_abi_version(void);
 /* channel tiles per wave the MFMA forward kernel should use for M output rows and reduction length K
  * (0 = thin path; short-K, output-bound problems get R = 1 for occupancy);

@@ -258,6 +258,8 @@ SIGNATURES = {
     "rfx_cl_dconv_ok": [_I32, _I32, _I32, _I32],
     "rfx_cl_dconv_fwd": [_P, _P],
     "rfx_cl_dconv_bwd": [_P, _P, _P],
+    "rfx_segment_split": [_P, _P, _I32, _I64, _I32, _I32, _I32, _P],
+    "rfx_segment_merge": [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _P],
 }
 
 _RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_stft_scaled_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",

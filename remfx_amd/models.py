@@ -377,6 +377,13 @@ class RemFXChainInference(_Base):
                 labels = torch.hstack(self.classifier(x))
                 rem_fx_labels = torch.where(labels > 0.5, 1.0, 0.0)    # strict >, models.py:61-64
         self.last_labels = rem_fx_labels
+        output = self._remove_by_labels(x, rem_fx_labels, effects_order, verbose)
+        loss = self.mrstftloss(output, y) + self.l1loss(output, y) * 100
+        return loss, output
+
+    def _remove_by_labels(self, x, rem_fx_labels, effects_order, verbose=False):
+        """Labels -> per-clip ordered chain -> removal models on sub-batches of clips that share their next effect.  The part of
+        forward() between the detector and the loss, shared with sample_long()."""
         lab = rem_fx_labels.detach().cpu()
         if self.use_all_effect_models:
             present = [list(ALL_EFFECT_NAMES) for _ in range(x.shape[0])]
@@ -401,8 +408,46 @@ class RemFXChainInference(_Base):
                     output.index_copy_(0, sel, res)
                     for i in idxs:
                         todo[i].pop(0)
-        loss = self.mrstftloss(output, y) + self.l1loss(output, y) * 100
-        return loss, output
+        return output
+
+    def sample_long(self, x, segment=262144, overlap=0.25, batch=64, detect="segment", labels=None, verbose=False,
+                    order=None):
+        """Detect-and-remove on a long (B, C, T) signal through overlapping clips of `segment` samples (remfx_amd/segment.py):
+        the networks see the clip length they were trained on, the cost grows linearly with T, and the detected chain may change
+        along the file.  Every channel is a row of its own.  Returns (output (B, C, T), segment_labels (B * C, S, 5));
+        `self.last_plan.starts` holds the clips' first samples for a timeline.
+          detect="segment": every clip is detected on its own and forward()'s grouping builds per-clip chains;
+          detect="file":    the detector's probabilities are averaged over a row's clips and thresholded once (strict > 0.5).
+        Without a classifier, `labels` (one row of 5 per file row, or one for all) is broadcast to the clips."""
+        from . import segment as seg
+        if detect not in ("segment", "file"):
+            raise ValueError(f"sample_long: detect must be 'segment' or 'file' (got {detect!r})")
+        B, Cn, T = x.shape
+        rows = B * Cn
+        plan = seg.SegmentPlan(T, segment, seg.overlap_samples(segment, overlap))
+        S = plan.n_segments
+        clips = seg.split(x, plan)                                       # (rows * S, 1, L)
+        n, step = clips.shape[0], max(1, int(batch))
+        if self.classifier:
+            with torch.no_grad():
+                probs = torch.cat([torch.hstack(self.classifier(clips[k:k + step])) for k in range(0, n, step)])
+            if detect == "file":
+                probs = probs.view(rows, S, -1).mean(1, keepdim=True).expand(rows, S, -1).reshape(n, -1)
+            seg_labels = torch.where(probs > 0.5, 1.0, 0.0)              # strict >, as forward()
+        else:
+            if labels is None:
+                raise ValueError("sample_long: no classifier, so `labels` (one row of 5 per file) is required")
+            lab = torch.as_tensor(labels, dtype=torch.float32, device=x.device).reshape(-1, len(ALL_EFFECT_NAMES))
+            if lab.shape[0] not in (1, rows):
+                raise ValueError(f"sample_long: labels has {lab.shape[0]} rows for {rows} file rows")
+            seg_labels = lab.expand(rows, -1).unsqueeze(1).expand(rows, S, -1).reshape(n, -1)
+        self.last_labels, self.last_plan = seg_labels, plan
+        effects_order = order if order else self.effect_order
+        out_clips = torch.empty_like(clips)
+        for k in range(0, n, step):
+            out_clips[k:k + step] = self._remove_by_labels(clips[k:k + step], seg_labels[k:k + step], effects_order,
+                                                           verbose and k == 0)
+        return seg.merge(out_clips, plan, channels=Cn), seg_labels.view(rows, S, -1)
 
     def test_step(self, batch, batch_idx):
         x, y, _, _ = batch
