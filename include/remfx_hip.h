@@ -627,6 +627,48 @@ int rfx_sisdr_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t
 /* The scalar tail of SISDRLoss in one launch: out[0] = -mean_r 10 log10(|a t|^2 / (|x - a t|^2 + eps) + eps), a = <x,t> / (|t|^2 + eps),
  * from the row sums of rfx_sisdr_sums (row means removed when zero_mean); auraloss SISDRLoss behind models.py:227-255. */
 int rfx_sisdr_finish(const double* sums, int32_t R, int64_t L, int32_t zero_mean, double eps, float* out, void* stream);
+/* ---- time-domain training losses (auraloss.time SISDRLoss / SDSDRLoss / SNRLoss / ESRLoss / DCLoss / LogCoshLoss) ----
+ * x, t: R rows of L fp32 samples, row strides x_rs / t_rs in samples (unit sample stride).  Optional prefilter (has_taps != 0): both
+ * signals are replaced by s~[n] = h_prev s[n-1] + h_cur s[n] + h_next s[n+1], zeros outside [0, L) of the ROW (conv1d, padding 1).
+ * With S = { Sx, St, Sxt, Sxx, Stt } of the filtered rows, primes = centred when zero_mean (Sxx' = Sxx - Sx^2 / L, ...):
+ *   ESR    (Stt - 2 Sxt + Sxx) / (Stt + eps)                       DC   ((St - Sx) / L)^2 / (Stt / L + eps)      (never centred)
+ *   SNR    -10 log10(Stt' / (Sxx' - 2 Sxt' + Stt' + eps) + eps)
+ *   SISDR  al = Sxt' / (Stt' + eps);  -10 log10(al^2 Stt' / (Sxx' - 2 al Sxt' + al^2 Stt' + eps) + eps)
+ *   SDSDR  same al;                   -10 log10(al^2 Stt' / (Sxx' - 2 Sxt' + Stt' + eps) + eps)
+ *   LOGCOSH  mean_n log(cosh(a (x - t)) + eps) / a     (elementwise: rfx_logcosh_rows / rfx_logcosh_grad, no prefilter) */
+#define RFX_TIME_SISDR 0
+#define RFX_TIME_SDSDR 1
+#define RFX_TIME_SNR 2
+#define RFX_TIME_ESR 3
+#define RFX_TIME_DC 4
+#define RFX_TIME_LOGCOSH 5
+#define RFX_REDUCE_MEAN 0
+#define RFX_REDUCE_SUM 1
+#define RFX_REDUCE_NONE 2
+/* sums [R][5] fp64 of the filtered rows, written, not accumulated: every workgroup stores its partial into its own slot of ws
+ * (rfx_time_sums_ws(R, L) doubles, no initialisation needed), added in slot order.  Without taps: the kernel, grid and bits of
+ * rfx_sisdr_sums. */
+int64_t rfx_time_sums_ws(int32_t R, int64_t L);
+int rfx_time_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, int32_t has_taps, double h_prev,
+                  double h_cur, double h_next, double* ws, double* sums, void* stream);
+/* From the row sums (kind LOGCOSH: sums [R][1] of rfx_logcosh_rows), in fp64: rows [R] fp32 = the per-row losses; coef [R][3] fp64
+ * (may be NULL) = (a, b, c) with d loss_r / d x~[n] = a x~[n] + b t~[n] + c (zeros for LOGCOSH); out[0] = their mean / sum
+ * (RFX_REDUCE_NONE: out untouched, may be NULL).  kind SISDR with RFX_REDUCE_MEAN returns the bits of rfx_sisdr_finish. */
+int rfx_time_loss_rows(const double* sums, int32_t R, int64_t L, int32_t kind, int32_t zero_mean, double eps, int32_t reduction,
+                       float* rows, double* coef, float* out, void* stream);
+/* gx [R][L] contiguous = g_r (h_prev u[n+1] + h_cur u[n] + h_next u[n-1]), u[m] = a_r x~[m] + b_r t~[m] + c_r inside the row, 0 outside
+ * (without taps: g_r u[n]); every element formed in fp64 and rounded once.  g_r from gup on the device: gup[0] / R (MEAN), gup[0] (SUM),
+ * gup[r] (NONE). */
+int rfx_time_loss_grad(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, const double* coef,
+                       int32_t has_taps, double h_prev, double h_cur, double h_next, const float* gup, int32_t reduction, float* gx,
+                       void* stream);
+/* sums [R] fp64 = sum_n log(cosh(a (x - t)) + eps) / a per row (ws: rfx_logcosh_ws(R, L) doubles, slots as above), then
+ * rfx_time_loss_rows(kind LOGCOSH);  gx [R][L] = g_r sinh(a z) / (cosh(a z) + eps) / L with g_r as for rfx_time_loss_grad. */
+int64_t rfx_logcosh_ws(int32_t R, int64_t L);
+int rfx_logcosh_rows(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, double a, double eps, double* ws,
+                     double* sums, void* stream);
+int rfx_logcosh_grad(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, double a, double eps,
+                     const float* gup, int32_t reduction, float* gx, void* stream);
 /* The scalar tail of MultiResolutionSTFTLoss in one launch: sums[k] = the [R][3] row sums of resolution k (rfx_stft_pair_loss /
  * rfx_stft_loss_reduce), n[k] = spectrum cells per row; out[0] = mean_k (sc_k + lm_k) with sc_k = mean_r sqrt(A_r / B_r)
  * (per_example_sc) or sqrt(sum A / sum B), lm_k = sum_r C_r / (R n_k).  sums / n are HOST arrays of nres <= 8 entries.

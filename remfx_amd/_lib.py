@@ -147,6 +147,13 @@ SIGNATURES = {
     "rfx_l1_grad": [_P, _P, _I64, C.c_float, _P, _P, _P],
     "rfx_sisdr_sums": [_P, _P, _I32, _I64, _I64, _I64, _P, _P, _P],
     "rfx_sisdr_finish": [_P, _I32, _I64, _I32, C.c_double, _P, _P],
+    "rfx_time_sums_ws": [_I32, _I64],
+    "rfx_time_sums": [_P, _P, _I32, _I64, _I64, _I64, _I32, C.c_double, C.c_double, C.c_double, _P, _P, _P],
+    "rfx_time_loss_rows": [_P, _I32, _I64, _I32, _I32, C.c_double, _I32, _P, _P, _P, _P],
+    "rfx_time_loss_grad": [_P, _P, _I32, _I64, _I64, _I64, _P, _I32, C.c_double, C.c_double, C.c_double, _P, _I32, _P, _P],
+    "rfx_logcosh_ws": [_I32, _I64],
+    "rfx_logcosh_rows": [_P, _P, _I32, _I64, _I64, _I64, C.c_double, C.c_double, _P, _P, _P],
+    "rfx_logcosh_grad": [_P, _P, _I32, _I64, _I64, _I64, C.c_double, C.c_double, _P, _I32, _P, _P],
     "rfx_mrstft_combine": [_P, _P, _I32, _I32, _I32, _P, _P],
     "rfx_stft_scaled_loss_ws": [_I32, _I32],
     "rfx_stft_scaled_loss": [_P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _P, _P, _P, _P, _P],
@@ -263,7 +270,7 @@ SIGNATURES = {
 }
 
 _RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_stft_scaled_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",
-          "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats", "rfx_fx_normalize_ws_bytes"}
+          "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats", "rfx_fx_normalize_ws_bytes", "rfx_time_sums_ws", "rfx_logcosh_ws"}
 _lib = None
 
 

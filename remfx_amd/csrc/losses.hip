@@ -446,3 +446,335 @@ extern "C" int rfx_sisdr_finish(const double* sums, int32_t R, int64_t L, int32_
   RFX_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- time-domain training losses (auraloss.time: SISDRLoss, SDSDRLoss, SNRLoss, ESRLoss, DCLoss, LogCoshLoss) ---------------------
+// The five ratio losses are functions of the row sums { Sx, St, Sxt, Sxx, Stt } of the (optionally FIR-filtered) rows, so
+//   d loss_r / d x~[n] = 2 dl/dSxx x~[n] + dl/dSxt t~[n] + dl/dSx = a_r x~[n] + b_r t~[n] + c_r
+// with three per-row coefficients: one sums pass, one per-row kernel (fp64), one streaming gradient pass.
+// The optional prefilter is x~[n] = h_prev x[n-1] + h_cur x[n] + h_next x[n+1] with zeros outside the row.
+
+// Row sums of the filtered rows.  One element per lane; the two neighbours come from the adjacent lanes (the loop bound is uniform in
+// the workgroup, lanes past L hold 0, which IS the halo value), only lanes 0 / 63 of a wave load theirs -- from inside the row, or 0 at
+// the row's ends, never the neighbouring row's memory.
+__global__ __launch_bounds__(256) void time_sums_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t L, int64_t xs,
+                                                        int64_t ts, double hp, double hc, double hn, double* __restrict__ slots) {
+  const int r = blockIdx.y, lane = threadIdx.x & 63;
+  const float* xr = x + (int64_t)r * xs;
+  const float* tr = t + (int64_t)r * ts;
+  double s[5] = {0, 0, 0, 0, 0};
+  for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < L; i0 += (int64_t)gridDim.x * 256) {
+    const int64_t i = i0 + threadIdx.x;
+    const bool in = i < L;
+    const float xc = in ? xr[i] : 0.f, tc = in ? tr[i] : 0.f;
+    float xm = __shfl_up(xc, 1, 64), xp = __shfl_down(xc, 1, 64);
+    float tm = __shfl_up(tc, 1, 64), tp = __shfl_down(tc, 1, 64);
+    if (lane == 0) { const bool ok = in && i >= 1; xm = ok ? xr[i - 1] : 0.f; tm = ok ? tr[i - 1] : 0.f; }
+    if (lane == 63) { const bool ok = i + 1 < L; xp = ok ? xr[i + 1] : 0.f; tp = ok ? tr[i + 1] : 0.f; }
+    if (in) {
+      const double a = hp * (double)xm + hc * (double)xc + hn * (double)xp;
+      const double b = hp * (double)tm + hc * (double)tc + hn * (double)tp;
+      s[0] += a; s[1] += b; s[2] += a * b; s[3] += a * a; s[4] += b * b;
+    }
+  }
+  rfx_block_store_slot<5>(s, slots, r, gridDim.x, blockIdx.x);
+}
+
+// Per-row losses, gradient coefficients and the reduced scalar from the fp64 row sums.  One wave, rows in lane order, fixed butterfly.
+// With f(Sxx', Sxt', Stt') on the (centred) sums, fa = df/dSxx', fb = df/dSxt':  a = 2 fa, b = fb and, through the centring
+// Sxx' = Sxx - Sx^2 / n, Sxt' = Sxt - Sx St / n,  c = -(2 fa Sx + fb St) / n  (0 without it).
+// The SI-SDR value is written exactly as in sisdr_finish_kernel: reduction "mean" returns the same bits.
+__global__ __launch_bounds__(64) void time_loss_rows_kernel(const double* __restrict__ sums, int R, double L, int kind, int zero_mean,
+                                                            double eps, int reduction, float* __restrict__ rows,
+                                                            double* __restrict__ coef, float* __restrict__ out) {
+  const int lane = threadIdx.x;
+  const bool logk = kind <= RFX_TIME_SNR;
+  const double K10 = -4.3429448190325182765;            // -10 / ln 10
+  double acc = 0.0;
+  for (int r = lane; r < R; r += 64) {
+    double ca = 0.0, cb = 0.0, cc = 0.0, val;
+    if (kind == RFX_TIME_LOGCOSH) {                      // sums [R][1] = sum_n log(cosh(a z) + eps) / a
+      val = sums[r] / L;
+      acc += val;
+    } else {
+      const double sx = sums[5 * r], st = sums[5 * r + 1];
+      double sxt = sums[5 * r + 2], sxx = sums[5 * r + 3], stt = sums[5 * r + 4];
+      if (kind == RFX_TIME_ESR) {
+        const double inv = 1.0 / (stt + eps);
+        val = (stt - 2.0 * sxt + sxx) * inv;
+        ca = 2.0 * inv; cb = -2.0 * inv;
+        acc += val;
+      } else if (kind == RFX_TIME_DC) {
+        const double d = (st - sx) / L, inv = 1.0 / (stt / L + eps);
+        val = d * d * inv;
+        cc = -2.0 * d / L * inv;
+        acc += val;
+      } else {
+        const bool zm = zero_mean != 0;
+        if (zm) { sxt -= sx * st / L; sxx -= sx * sx / L; stt -= st * st / L; }
+        double fa, fb, lg;
+        if (kind == RFX_TIME_SNR) {
+          const double den = sxx - 2.0 * sxt + stt + eps;
+          const double q = stt / den + eps;
+          lg = log10(q);
+          fa = K10 / q * (-stt / (den * den));
+          fb = -2.0 * fa;
+        } else {
+          const double ia = 1.0 / (stt + eps);
+          const double alpha = sxt / (stt + eps);
+          const double tt = alpha * alpha * stt;
+          double res, dres;                              // the residual energy and d res / d Sxt'
+          if (kind == RFX_TIME_SISDR) {
+            res = sxx - 2.0 * alpha * sxt + tt;
+            dres = -2.0 * alpha - 2.0 * sxt * ia + 2.0 * alpha * stt * ia;
+          } else {
+            res = sxx - 2.0 * sxt + stt;
+            dres = -2.0;
+          }
+          lg = log10(tt / (res + eps) + eps);
+          const double den = res + eps, q = tt / den + eps;
+          const double dtt = 2.0 * alpha * stt * ia;     // d tt / d Sxt'
+          fa = K10 / q * (-tt / (den * den));
+          fb = K10 / q * ((dtt * den - tt * dres) / (den * den));
+        }
+        acc += 10.0 * lg;
+        val = -(10.0 * lg);
+        ca = 2.0 * fa; cb = fb;
+        if (zm) cc = -(2.0 * fa * sx + fb * st) / L;
+      }
+    }
+    rows[r] = (float)val;
+    if (coef) { coef[3 * r] = ca; coef[3 * r + 1] = cb; coef[3 * r + 2] = cc; }
+  }
+  acc = rfx_wave_sum_d(acc);
+  if (lane == 0 && out) {
+    const double tot = logk ? -acc : acc;
+    out[0] = (float)(reduction == RFX_REDUCE_MEAN ? tot / (double)R : tot);
+  }
+}
+
+// upstream gradient of row r, read on the device: one value (/ R for "mean") or one per row ("none")
+__device__ __forceinline__ double rfx_row_gup(const float* __restrict__ gup, int reduction, int r, int R) {
+  if (reduction == RFX_REDUCE_NONE) return (double)gup[r];
+  return reduction == RFX_REDUCE_MEAN ? (double)gup[0] / (double)R : (double)gup[0];
+}
+
+struct TimeGradArgs {
+  const float* x; const float* t; float* gx;
+  const double* coef; const float* gup;
+  int64_t L, xs, ts;
+  double hp, hc, hn;
+  int R, reduction;
+};
+
+// gx[n] for one element from the five-sample windows of x and t (row ends are zeros): the scalar head / tail of a row
+template <bool TAPS>
+__device__ __forceinline__ float time_grad_one(const float* __restrict__ xr, const float* __restrict__ tr, int64_t n, int64_t L, double a,
+                                               double b, double c, double hp, double hc, double hn) {
+  if (!TAPS) return (float)(a * (double)xr[n] + b * (double)tr[n] + c);
+  double xw[5], tw[5], u[3];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const int64_t m = n + k - 2;
+    const bool ok = m >= 0 && m < L;
+    xw[k] = ok ? (double)xr[m] : 0.0; tw[k] = ok ? (double)tr[m] : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {                          // u[n - 1 + k], zero outside the row
+    const int64_t m = n + k - 1;
+    const double xf = hp * xw[k] + hc * xw[k + 1] + hn * xw[k + 2], tf = hp * tw[k] + hc * tw[k + 1] + hn * tw[k + 2];
+    u[k] = (m >= 0 && m < L) ? a * xf + b * tf + c : 0.0;
+  }
+  return (float)(hn * u[0] + hc * u[1] + hp * u[2]);
+}
+
+// four consecutive samples of a row, as one 16-byte access when the row's phase allows it
+__device__ __forceinline__ f32x4 time_ld4(const float* __restrict__ p, bool vec) {
+  if (vec) return rfx_ld4(p);
+  return f32x4{p[0], p[1], p[2], p[3]};
+}
+
+// The gradient pass: gx[r][n] = g_r (h_prev u[n+1] + h_cur u[n] + h_next u[n-1]), u[m] = a x~[m] + b t~[m] + c inside the row and 0
+// outside (the adjoint of the zero-padded filter), every element formed in fp64 and rounded once.  A lane owns the four samples
+// n0 .. n0+3 of a 16-byte-aligned group of gx; the two samples on either side come from the neighbouring lanes' groups, and from memory
+// (inside the row, else 0) at the ends of a wave and of the vector body.  x / t rows whose 16-byte phase differs from gx's are read as
+// four dwords.  The <= 3 samples in front of the first aligned group and behind the last full one go through time_grad_one.
+template <bool TAPS>
+__global__ __launch_bounds__(256) void time_loss_grad_kernel(const TimeGradArgs p) {
+  const int r = blockIdx.y, lane = threadIdx.x & 63;
+  const float* xr = p.x + (int64_t)r * p.xs;
+  const float* tr = p.t + (int64_t)r * p.ts;
+  float* gr = p.gx + (int64_t)r * p.L;
+  const double g = rfx_row_gup(p.gup, p.reduction, r, p.R);
+  const double a = g * p.coef[3 * r], b = g * p.coef[3 * r + 1], c = g * p.coef[3 * r + 2];
+  const double hp = p.hp, hc = p.hc, hn = p.hn;
+  const int64_t L = p.L;
+  const int phg = (int)(((uintptr_t)gr >> 2) & 3);
+  int64_t head = (4 - phg) & 3;
+  head = head < L ? head : L;
+  const int64_t nvec = (L - head) >> 2, tail0 = head + 4 * nvec;
+  const bool xvec = (int)((((uintptr_t)(xr + head)) >> 2) & 3) == 0, tvec = (int)((((uintptr_t)(tr + head)) >> 2) & 3) == 0;
+  if (blockIdx.x == 0 && threadIdx.x < 6) {              // scalar head (lanes 0..2) and tail (lanes 3..5)
+    const int64_t n = threadIdx.x < 3 ? (int64_t)threadIdx.x : tail0 + threadIdx.x - 3;
+    if (threadIdx.x < 3 ? n < head : n < L) gr[n] = time_grad_one<TAPS>(xr, tr, n, L, a, b, c, hp, hc, hn);
+  }
+  for (int64_t k0 = (int64_t)blockIdx.x * 256; k0 < nvec; k0 += (int64_t)gridDim.x * 256) {
+    const int64_t k = k0 + threadIdx.x;
+    const bool in = k < nvec;
+    const int64_t n0 = head + 4 * k;
+    f32x4 xv = {0.f, 0.f, 0.f, 0.f}, tv = {0.f, 0.f, 0.f, 0.f};
+    if (in) { xv = time_ld4(xr + n0, xvec); tv = time_ld4(tr + n0, tvec); }
+    if (!TAPS) {
+      if (in) {
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (float)(a * (double)xv[j] + b * (double)tv[j] + c);
+        rfx_st4(gr + n0, o);
+      }
+      continue;
+    }
+    // window w[0..7] = samples n0-2 .. n0+5
+    double xw[8], tw[8];
+    {
+      float xl0 = __shfl_up(xv[2], 1, 64), xl1 = __shfl_up(xv[3], 1, 64), xh0 = __shfl_down(xv[0], 1, 64), xh1 = __shfl_down(xv[1], 1, 64);
+      float tl0 = __shfl_up(tv[2], 1, 64), tl1 = __shfl_up(tv[3], 1, 64), th0 = __shfl_down(tv[0], 1, 64), th1 = __shfl_down(tv[1], 1, 64);
+      if (in && (lane == 0 || k == 0)) {
+        const bool o1 = n0 >= 1, o2 = n0 >= 2;
+        xl0 = o2 ? xr[n0 - 2] : 0.f; xl1 = o1 ? xr[n0 - 1] : 0.f;
+        tl0 = o2 ? tr[n0 - 2] : 0.f; tl1 = o1 ? tr[n0 - 1] : 0.f;
+      }
+      if (in && (lane == 63 || k + 1 >= nvec)) {
+        const bool o4 = n0 + 4 < L, o5 = n0 + 5 < L;
+        xh0 = o4 ? xr[n0 + 4] : 0.f; xh1 = o5 ? xr[n0 + 5] : 0.f;
+        th0 = o4 ? tr[n0 + 4] : 0.f; th1 = o5 ? tr[n0 + 5] : 0.f;
+      }
+      xw[0] = xl0; xw[1] = xl1; xw[6] = xh0; xw[7] = xh1;
+      tw[0] = tl0; tw[1] = tl1; tw[6] = th0; tw[7] = th1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { xw[2 + j] = xv[j]; tw[2 + j] = tv[j]; }
+    }
+    if (in) {
+      double u[6];                                       // u[n0-1 .. n0+4]
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const int64_t m = n0 - 1 + j;
+        const double xf = hp * xw[j] + hc * xw[j + 1] + hn * xw[j + 2], tf = hp * tw[j] + hc * tw[j + 1] + hn * tw[j + 2];
+        u[j] = (m >= 0 && m < L) ? a * xf + b * tf + c : 0.0;
+      }
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = (float)(hn * u[j] + hc * u[j + 1] + hp * u[j + 2]);
+      rfx_st4(gr + n0, o);
+    }
+  }
+}
+
+// log(cosh(y) + eps) = |y| + log((1 + e^-2|y|) / 2 + eps e^-|y|): no overflow for any y.  fp64: with x close to t the value is ~y^2 / 2
+// next to cosh ~ 1, which fp32 resolves to 1e-7 ABSOLUTE only.
+__global__ __launch_bounds__(256) void logcosh_rows_kernel(const float* __restrict__ x, const float* __restrict__ t, int64_t L, int64_t xs,
+                                                           int64_t ts, double a, double eps, double* __restrict__ slots) {
+  const int r = blockIdx.y;
+  const float* xr = x + (int64_t)r * xs;
+  const float* tr = t + (int64_t)r * ts;
+  double s[1] = {0.0};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L; i += (int64_t)gridDim.x * 256) {
+    const double y = fabs(a * ((double)xr[i] - (double)tr[i]));
+    const double e1 = exp(-y);
+    s[0] += y + log(0.5 * (1.0 + e1 * e1) + eps * e1);
+  }
+  s[0] /= a;
+  rfx_block_store_slot<1>(s, slots, r, gridDim.x, blockIdx.x);
+}
+
+// gx[r][n] = g_r sinh(a z) / (cosh(a z) + eps) / L = g_r sign(z) (1 - e2) / (1 + e2 + 2 eps e1) / L,  e1 = e^-|a z|, e2 = e1^2
+__global__ __launch_bounds__(256) void logcosh_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, int R, int64_t L,
+                                                           int64_t xs, int64_t ts, double a, double eps, const float* __restrict__ gup,
+                                                           int reduction, float* __restrict__ gx) {
+  const int r = blockIdx.y;
+  const float* xr = x + (int64_t)r * xs;
+  const float* tr = t + (int64_t)r * ts;
+  float* gr = gx + (int64_t)r * L;
+  const double w = rfx_row_gup(gup, reduction, r, R) / (double)L;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L; i += (int64_t)gridDim.x * 256) {
+    const double z = a * ((double)xr[i] - (double)tr[i]);
+    const double e1 = exp(-fabs(z)), e2 = e1 * e1;
+    const double v = w * (1.0 - e2) / (1.0 + e2 + 2.0 * eps * e1);
+    gr[i] = (float)(z < 0.0 ? -v : v);
+  }
+}
+
+static int time_sums_grid(int64_t L) {
+  int g = grid_x(L);
+  return g > RFX_SISDR_SLOTS ? RFX_SISDR_SLOTS : g;
+}
+// streaming passes over [R][n units]: ~4096 workgroups in all, at least 1024 units each before another workgroup is worth its launch
+static int time_stream_grid(int64_t units, int R) {
+  int64_t want = (units + 1023) / 1024, cap = 4096 / R;
+  cap = cap < 1 ? 1 : cap;
+  want = want > cap ? cap : want;
+  return (int)(want < 1 ? 1 : want);
+}
+static bool time_kind_ok(int kind) { return kind >= RFX_TIME_SISDR && kind <= RFX_TIME_LOGCOSH; }
+static bool time_red_ok(int red) { return red >= RFX_REDUCE_MEAN && red <= RFX_REDUCE_NONE; }
+
+extern "C" int64_t rfx_time_sums_ws(int32_t R, int64_t L) {
+  if (R <= 0 || L <= 0) return 0;
+  return (int64_t)5 * R * time_sums_grid(L);
+}
+extern "C" int rfx_time_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, int32_t has_taps,
+                             double h_prev, double h_cur, double h_next, double* ws, double* sums, void* stream) {
+  if (!x || !t || !sums || !ws || R <= 0 || L <= 0) return -1;
+  const int g = time_sums_grid(L);                       // the grid of rfx_sisdr_sums: without taps, its kernel and its bits
+  if (has_taps)
+    hipLaunchKernelGGL(time_sums_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream, x, t, L, x_rs, t_rs, h_prev, h_cur, h_next, ws);
+  else
+    hipLaunchKernelGGL(sisdr_sums_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream, x, t, L, x_rs, t_rs, ws);
+  RFX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rfx_slot_sum_kernel<double>, RFX_SLOT_SUM_GRID(5 * R), 0, (hipStream_t)stream, ws, R, g, 5, sums);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_time_loss_rows(const double* sums, int32_t R, int64_t L, int32_t kind, int32_t zero_mean, double eps,
+                                  int32_t reduction, float* rows, double* coef, float* out, void* stream) {
+  if (!sums || !rows || R <= 0 || L <= 0 || !time_kind_ok(kind) || !time_red_ok(reduction)) return -1;
+  if (reduction != RFX_REDUCE_NONE && !out) return -1;
+  hipLaunchKernelGGL(time_loss_rows_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sums, R, (double)L, kind, zero_mean, eps,
+                     reduction, rows, coef, out);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_time_loss_grad(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, const double* coef,
+                                  int32_t has_taps, double h_prev, double h_cur, double h_next, const float* gup, int32_t reduction,
+                                  float* gx, void* stream) {
+  if (!x || !t || !coef || !gup || !gx || R <= 0 || L <= 0 || !time_red_ok(reduction)) return -1;
+  if ((((uintptr_t)x | (uintptr_t)t | (uintptr_t)gx) & 3) != 0) return -1;
+  TimeGradArgs p;
+  p.x = x; p.t = t; p.gx = gx; p.coef = coef; p.gup = gup; p.L = L; p.xs = x_rs; p.ts = t_rs;
+  p.hp = h_prev; p.hc = h_cur; p.hn = h_next; p.R = R; p.reduction = reduction;
+  const dim3 grid(time_stream_grid((L + 3) / 4, R), R);
+  if (has_taps) hipLaunchKernelGGL(time_loss_grad_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(time_loss_grad_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int64_t rfx_logcosh_ws(int32_t R, int64_t L) {
+  if (R <= 0 || L <= 0) return 0;
+  return (int64_t)R * time_sums_grid(L);
+}
+extern "C" int rfx_logcosh_rows(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, double a, double eps,
+                                double* ws, double* sums, void* stream) {
+  if (!x || !t || !sums || !ws || R <= 0 || L <= 0 || !(a > 0.0)) return -1;
+  const int g = time_sums_grid(L);
+  hipLaunchKernelGGL(logcosh_rows_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream, x, t, L, x_rs, t_rs, a, eps, ws);
+  RFX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(rfx_slot_sum_kernel<double>, RFX_SLOT_SUM_GRID(R), 0, (hipStream_t)stream, ws, R, g, 1, sums);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int rfx_logcosh_grad(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, double a, double eps,
+                                const float* gup, int32_t reduction, float* gx, void* stream) {
+  if (!x || !t || !gup || !gx || R <= 0 || L <= 0 || !(a > 0.0) || !time_red_ok(reduction)) return -1;
+  hipLaunchKernelGGL(logcosh_grad_kernel, dim3(time_stream_grid(L, R), R), dim3(256), 0, (hipStream_t)stream, x, t, R, L, x_rs, t_rs, a,
+                     eps, gup, reduction, gx);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}

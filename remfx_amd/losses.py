@@ -17,6 +17,17 @@ builds -- `n_bins` / `sample_rate` are inert, as upstream, an
 One deliberate difference: a mel filter without a non-zero weight (more filters than the low bins can carry) makes auraloss return
 NaN (log 0 - log 0); here the constructor raises ValueError naming the resolution and the count.
 `STFTLoss` is the single-resolution class auraloss exports, over the same function.
+
+Time-domain losses (auraloss.time; auraloss is not available to pin them: PARITY UNPINNED, restated in tests/time_loss_ref.py), on
+(..., L) inputs taken as R rows of L samples, reduction "mean" / "sum" / "none" over the rows, differentiable in the prediction:
+  SISDRLoss, SDSDRLoss, SNRLoss (zero_mean=True, eps=1e-8), ESRLoss, DCLoss (eps=1e-8), LogCoshLoss (a=1.0, eps=1e-8)
+The five ratio losses are functions of the row sums {Sx, St, Sxt, Sxx, Stt}, so their gradient is a x + b t + c with three fp64
+numbers per row: rfx_time_sums, rfx_time_loss_rows, and ONE rfx_time_loss_grad launch in the backward.
+`prefilter=(h_prev, h_cur, h_next)` is a keyword this port adds (auraloss applies its FIRFilter as a separate module): both signals are
+first replaced by h_prev s[n-1] + h_cur s[n] + h_next s[n+1], zeros outside the row -- conv1d with those weights and padding=1;
+pre-emphasis is (-0.85, 1, 0), and the three conv weights of an auraloss FIRFilter of the first-order kinds can be passed as they are
+(the A-weighting kind is not implemented).  Unknown `reduction`, a `prefilter` that is not three finite numbers, L < 1: ValueError.
+SISDRLoss without a gradient to compute and with default keywords is the metric it always was: rfx_sisdr_sums + rfx_sisdr_finish.
 """
 import ctypes as C
 import os
@@ -435,16 +446,124 @@ class L1Loss(nn.Module):
         return _L1Fn.apply(input, target)
 
 
-class SISDRLoss(nn.Module):
-    """-SI-SDR (auraloss.time.SISDRLoss, zero_mean=True, eps=1e-8, reduction='mean');
-    metric only (no gradient), models.py:227-255."""
+TIME_KINDS = {"sisdr": 0, "sdsdr": 1, "snr": 2, "esr": 3, "dc": 4, "logcosh": 5}          # RFX_TIME_* of include/remfx_hip.h
+REDUCTIONS = {"mean": 0, "sum": 1, "none": 2}                                                 # RFX_REDUCE_*
 
-    def __init__(self, zero_mean=True, eps=1e-8):
+
+def _check_reduction(reduction):
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction={reduction!r}: one of 'mean', 'sum', 'none'")
+    return reduction
+
+
+def _check_prefilter(prefilter):
+    """None, or the three conv weights (h_prev, h_cur, h_next) of a first-order FIR prefilter as finite numbers."""
+    if prefilter is None:
+        return None
+    try:
+        taps = tuple(float(v) for v in prefilter)
+    except (TypeError, ValueError):
+        raise ValueError(f"prefilter={prefilter!r}: three finite numbers (h_prev, h_cur, h_next), e.g. (-0.85, 1, 0)") from None
+    if len(taps) != 3 or not all(np.isfinite(v) for v in taps):
+        raise ValueError(f"prefilter={prefilter!r}: three finite numbers (h_prev, h_cur, h_next), e.g. (-0.85, 1, 0)")
+    return taps
+
+
+def _rows(input, target):
+    """(..., L) -> R rows of L samples with unit sample stride; cropped views keep their row stride (no copy)."""
+    _req(input, "input"); _req(target, "target")
+    if input.shape != target.shape:
+        raise ValueError(f"input {tuple(input.shape)} and target {tuple(target.shape)} differ in shape")
+    if input.dim() < 1 or input.shape[-1] < 1 or input.numel() == 0:
+        raise ValueError(f"time-domain losses need (..., L) with L >= 1 and at least one row (got {tuple(input.shape)})")
+    L = input.shape[-1]
+    x, t = input.reshape(-1, L), target.reshape(-1, L)
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    if t.stride(-1) != 1:
+        t = t.contiguous()
+    return x, t, x.shape[0], L
+
+
+class _TimeLossFn(torch.autograd.Function):
+    """The six time-domain losses: row sums (rfx_time_sums / rfx_logcosh_rows), the per-row kernel (rfx_time_loss_rows: losses,
+    gradient coefficients, reduced scalar), and in the backward ONE streaming launch (rfx_time_loss_grad / rfx_logcosh_grad) that
+    reads the upstream gradient on the device.  No gradient with respect to the target."""
+
+    @staticmethod
+    def forward(ctx, input, target, kind, zero_mean, eps, reduction, taps, a):
+        x, t, R, L = _rows(input, target)
+        dev, L_ = x.device, _lib.lib()
+        k, red = TIME_KINDS[kind], REDUCTIONS[reduction]
+        h = taps if taps is not None else (0.0, 1.0, 0.0)
+        need = ctx.needs_input_grad[0]
+        if kind == "logcosh":
+            s = torch.empty((R,), device=dev, dtype=torch.float64)
+            ws = torch.empty(int(L_.rfx_logcosh_ws(R, L)), device=dev, dtype=torch.float64)      # one slot per workgroup
+            check(L_.rfx_logcosh_rows(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), float(a), float(eps), _ptr(ws), _ptr(s),
+                                      _stream()), "rfx_logcosh_rows")
+            coef = None
+        else:
+            s = torch.empty((R, 5), device=dev, dtype=torch.float64)                            # written, not accumulated: no zero fill
+            ws = torch.empty(int(L_.rfx_time_sums_ws(R, L)), device=dev, dtype=torch.float64)
+            check(L_.rfx_time_sums(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), 1 if taps is not None else 0, h[0], h[1], h[2],
+                                   _ptr(ws), _ptr(s), _stream()), "rfx_time_sums")
+            coef = torch.empty((R, 3), device=dev, dtype=torch.float64) if need else None
+        rows = torch.empty((R,), device=dev, dtype=torch.float32)
+        out = torch.empty((), device=dev, dtype=torch.float32) if reduction != "none" else None
+        check(L_.rfx_time_loss_rows(_ptr(s), R, L, k, 1 if zero_mean else 0, float(eps), red, _ptr(rows), _ptr(coef), _ptr(out),
+                                    _stream()), "rfx_time_loss_rows")
+        if need:
+            ctx.save_for_backward(x, t, coef)
+            ctx.meta = (input.shape, R, L, kind, red, taps, h, float(a), float(eps))
+        return out if out is not None else rows.view(input.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, coef = ctx.saved_tensors
+        shape, R, L, kind, red, taps, h, a, eps = ctx.meta
+        gx = torch.empty((R, L), device=x.device, dtype=torch.float32)
+        gup = g.detach().reshape(-1).float().contiguous()                 # 1 value (mean / sum) or R (none); stays on the device
+        if kind == "logcosh":
+            check(_lib.lib().rfx_logcosh_grad(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), a, eps, _ptr(gup), red, _ptr(gx),
+                                              _stream()), "rfx_logcosh_grad")
+        else:
+            check(_lib.lib().rfx_time_loss_grad(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), _ptr(coef),
+                                                1 if taps is not None else 0, h[0], h[1], h[2], _ptr(gup), red, _ptr(gx), _stream()),
+                  "rfx_time_loss_grad")
+        return (gx.view(shape),) + (None,) * 7
+
+
+class _TimeLoss(nn.Module):
+    """Base of the time-domain losses: no parameters, no buffers; `forward(input, target)` on (..., L) fp32 GPU tensors."""
+    kind = None
+
+    def __init__(self, zero_mean=True, eps=1e-8, reduction="mean", prefilter=None, a=1.0):
         super().__init__()
-        self.zero_mean, self.eps = zero_mean, eps
+        self.zero_mean, self.eps, self.reduction = bool(zero_mean), float(eps), _check_reduction(reduction)
+        self.prefilter, self.a = _check_prefilter(prefilter), float(a)
 
-    @torch.no_grad()
     def forward(self, input, target):
+        return _TimeLossFn.apply(input, target, self.kind, self.zero_mean, self.eps, self.reduction, self.prefilter, self.a)
+
+
+class SISDRLoss(_TimeLoss):
+    """-SI-SDR (auraloss.time.SISDRLoss; the metric of models.py:227-255 and a training loss): per row, after removing the row means
+    when `zero_mean`, alpha = <x, t> / (|t|^2 + eps) and -10 log10(|alpha t|^2 / (|x - alpha t|^2 + eps) + eps).  `prefilter` is this
+    port's keyword (module docstring).  Without a gradient to compute and with reduction="mean", prefilter=None -- the metric path of
+    the training step -- it is the two launches rfx_sisdr_sums + rfx_sisdr_finish; the differentiable path returns the same bits."""
+    kind = "sisdr"
+
+    def __init__(self, zero_mean=True, eps=1e-8, reduction="mean", prefilter=None):
+        super().__init__(zero_mean, eps, reduction, prefilter)
+
+    def forward(self, input, target):
+        if self.reduction != "mean" or self.prefilter is not None or (torch.is_grad_enabled() and input.requires_grad):
+            return super().forward(input, target)
+        with torch.no_grad():
+            return self._metric(input, target)
+
+    def _metric(self, input, target):
         _req(input, "input"); _req(target, "target")
         L = input.shape[-1]
         x, t = input.reshape(-1, L), target.reshape(-1, L)
@@ -461,3 +580,63 @@ class SISDRLoss(nn.Module):
         check(_lib.lib().rfx_sisdr_finish(_ptr(s), R, L, 1 if self.zero_mean else 0, float(self.eps), _ptr(out), _stream()),
               "rfx_sisdr_finish")
         return out
+
+
+class SDSDRLoss(_TimeLoss):
+    """-SD-SDR (auraloss.time.SDSDRLoss): SI-SDR's scaled target alpha t over the UNSCALED residual x - t."""
+    kind = "sdsdr"
+
+    def __init__(self, zero_mean=True, eps=1e-8, reduction="mean", prefilter=None):
+        super().__init__(zero_mean, eps, reduction, prefilter)
+
+
+class SNRLoss(_TimeLoss):
+    """-SNR (auraloss.time.SNRLoss): -10 log10(|t|^2 / (|x - t|^2 + eps) + eps) per row, row means removed when `zero_mean`."""
+    kind = "snr"
+
+    def __init__(self, zero_mean=True, eps=1e-8, reduction="mean", prefilter=None):
+        super().__init__(zero_mean, eps, reduction, prefilter)
+
+
+class ESRLoss(_TimeLoss):
+    """Error-to-signal ratio (auraloss.time.ESRLoss): |t - x|^2 / (|t|^2 + eps) per row.  With prefilter=(-0.85, 1, 0) the
+    pre-emphasised ESR of audio-effect modelling."""
+    kind = "esr"
+
+    def __init__(self, eps=1e-8, reduction="mean", prefilter=None):
+        super().__init__(False, eps, reduction, prefilter)
+
+
+class DCLoss(_TimeLoss):
+    """DC loss (auraloss.time.DCLoss): (mean t - mean x)^2 / (mean t^2 + eps) per row."""
+    kind = "dc"
+
+    def __init__(self, eps=1e-8, reduction="mean", prefilter=None):
+        super().__init__(False, eps, reduction, prefilter)
+
+
+class LogCoshLoss(_TimeLoss):
+    """Log-cosh loss (auraloss.time.LogCoshLoss): mean_n log(cosh(a (x - t)) + eps) / a per row; elementwise, no prefilter."""
+    kind = "logcosh"
+
+    def __init__(self, a=1.0, eps=1e-8, reduction="mean"):
+        a = float(a)
+        if not (np.isfinite(a) and a > 0.0):
+            raise ValueError(f"a={a!r}: a finite positive number")
+        super().__init__(False, eps, reduction, None, a)
+
+
+TIME_LOSSES = {"sisdr": SISDRLoss, "sdsdr": SDSDRLoss, "snr": SNRLoss, "esr": ESRLoss, "dc": DCLoss, "logcosh": LogCoshLoss}
+
+
+def time_loss(time_loss_kwargs):
+    """(module, weight) from the wrappers' `time_loss_kwargs`: a mapping with `name` (one of TIME_LOSSES), `weight` (default 1.0) and
+    the class's own keywords -- e.g. `+model.network.time_loss_kwargs.name=sisdr +model.network.time_loss_kwargs.weight=0.1`."""
+    kw = dict(time_loss_kwargs)
+    name = kw.pop("name", None)
+    if name not in TIME_LOSSES:
+        raise ValueError(f"time_loss_kwargs.name={name!r}: one of {', '.join(TIME_LOSSES)}")
+    weight = float(kw.pop("weight", 1.0))
+    if "prefilter" in kw and kw["prefilter"] is not None:
+        kw["prefilter"] = tuple(kw["prefilter"])                           # an OmegaConf list from the command line
+    return TIME_LOSSES[name](**kw), weight

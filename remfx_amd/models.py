@@ -14,7 +14,8 @@ import random
 import torch
 from torch import Tensor, nn
 
-from .losses import L1Loss, MultiResolutionSTFTLoss, SISDRLoss, stft_memo
+from .losses import (DCLoss, ESRLoss, L1Loss, LogCoshLoss, MultiResolutionSTFTLoss, SDSDRLoss, SISDRLoss, SNRLoss,  # noqa: F401
+                     stft_memo, time_loss)                     # the loss classes are re-exported through remfx.models
 from .tcn import TCN
 from .utils import causal_crop
 
@@ -137,18 +138,27 @@ def _mrstft(num_bins, sample_rate, mrstft_kwargs=None):
 
 
 class _RemovalWrapper(nn.Module):
-    """forward((x, target)) -> (loss, output); sample(x) -> output; loss = MRSTFT + 100 * L1."""
+    """forward((x, target)) -> (loss, output); sample(x) -> output; loss = MRSTFT + 100 * L1, plus `weight` times one of the
+    time-domain losses (losses.TIME_LOSSES) when the wrapper was built with `time_loss_kwargs` = {name, weight=1.0, **its keywords}
+    -- e.g. `+model.network.time_loss_kwargs.name=sisdr +model.network.time_loss_kwargs.weight=0.1` on the command line."""
+
+    def _set_time_loss(self, time_loss_kwargs):
+        self.timeloss, self.time_loss_weight = time_loss(time_loss_kwargs) if time_loss_kwargs is not None else (None, 0.0)
 
     def _loss(self, output, target):
-        return self.mrstftloss(output, target) + self.l1loss(output, target) * 100
+        if self.timeloss is None:
+            return self.mrstftloss(output, target) + self.l1loss(output, target) * 100
+        return (self.mrstftloss(output, target) + self.l1loss(output, target) * 100
+                + self.timeloss(output, target) * self.time_loss_weight)
 
 
 class TCNModel(_RemovalWrapper):
-    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs):
         super().__init__()
         self.model = TCN(**kwargs)
         self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
+        self._set_time_loss(time_loss_kwargs)
 
     def forward(self, batch):
         x, target = batch
@@ -162,13 +172,14 @@ class TCNModel(_RemovalWrapper):
 
 
 class DemucsModel(_RemovalWrapper):
-    def __init__(self, sample_rate, mrstft_kwargs=None, **kwargs) -> None:
+    def __init__(self, sample_rate, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs) -> None:
         super().__init__()
         from .hdemucs import HDemucs
         self.model = HDemucs(**kwargs)
         self.num_bins = kwargs["nfft"] // 2 + 1
         self.mrstftloss = _mrstft(self.num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
+        self._set_time_loss(time_loss_kwargs)
 
     def forward(self, batch):
         x, target = batch
@@ -181,7 +192,7 @@ class DemucsModel(_RemovalWrapper):
 
 class OpenUnmixModel(_RemovalWrapper):
     def __init__(self, n_fft: int = 2048, hop_length: int = 512, n_channels: int = 1, alpha: float = 0.3,
-                 sample_rate: int = 22050, mrstft_kwargs=None):
+                 sample_rate: int = 22050, mrstft_kwargs=None, time_loss_kwargs=None):
         super().__init__()
         from .umx import OpenUnmix, Separator
         from .utils import spectrogram
@@ -195,6 +206,7 @@ class OpenUnmixModel(_RemovalWrapper):
                                    sample_rate=sample_rate, n_fft=n_fft, n_hop=hop_length)
         self.mrstftloss = _mrstft(self.num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
+        self._set_time_loss(time_loss_kwargs)
 
     def forward(self, batch):
         x, target = batch
@@ -208,12 +220,13 @@ class OpenUnmixModel(_RemovalWrapper):
 
 
 class DCUNetModel(_RemovalWrapper):
-    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs):
         super().__init__()
         from .dcunet import DCUNet
         self.model = DCUNet(**kwargs)          # asteroid keeps its own sample_rate default (wrapper swallows it)
         self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
+        self._set_time_loss(time_loss_kwargs)
 
     def forward(self, batch):
         x, target = batch
@@ -230,13 +243,14 @@ class DPTNetModel(_RemovalWrapper):
     """models.py:327-344: asteroid DPTNet (cfg/model/dptnet.yaml) + MRSTFT + 100 L1; no target crop (the network pads / crops
     its output to the input length)."""
 
-    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs):
         super().__init__()
         from .dptnet import DPTNet
         self.model = DPTNet(**kwargs)
         self.num_bins = num_bins
         self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
+        self._set_time_loss(time_loss_kwargs)
 
     def forward(self, batch):
         x, target = batch
