@@ -45,6 +45,8 @@ def _run(H, Cin, T, Bn, layers, seed=0):
     (384, 384, 12, 20, 1),      # HDemucs layer 5 width: 16-sequence backward tiles
     (256, 512, 9, 4, 3),        # Open-Unmix (hidden 512 -> 256 per direction, 3 layers)
     (64, 16, 3, 8200, 1),       # more sequence tiles than one co-resident launch holds (chunked launches)
+    (192, 192, 6, 70, 1),       # more than RFX_LSTM_LOCAL sequences: the bf16 cluster form, forward and backward (what a 64-clip step runs)
+    (128, 64, 5, 33, 1),        # a generic form whose weight ring wraps within a time step (tests/test_gpu_lstm_kernel.py has them all)
 ])
 def test_blstm_matches_torch(H, Cin, T, Bn, layers):
     _run(H, Cin, T, Bn, layers)
