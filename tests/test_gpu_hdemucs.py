@@ -176,7 +176,7 @@ def test_hdemucs_full_config_gradients_golden(golden_dir):
 
 @pytest.mark.one_mode
 @pytest.mark.parametrize("B,heads,ch,T,nd", [(3, 4, 48, 256, 4), (2, 4, 96, 200, 4), (2, 4, 96, 64, 4), (2, 2, 16, 37, 3),
-                                             (1, 2, 64, 130, 4), (2, 1, 32, 256, 1),
+                                             (1, 2, 64, 130, 4), (2, 1, 32, 256, 1), (2, 4, 48, 129, 4), (1, 2, 16, 1, 1),
                                              # more than 256 frames = longer than one 262144-sample clip (whole files): the
                                              # streaming any-T kernels (rfx_localstate_gen_*), both session modes
                                              (2, 4, 48, 300, 4), (1, 4, 96, 705, 4), (1, 2, 16, 1030, 9)])
@@ -186,23 +186,12 @@ def test_localstate_mfma_vs_exact(B, heads, ch, T, nd):
     fp64, forward and all four gradients.  bf16 bound: operand rounding of q, k, content, P and dS (2^-9 relative each) --
     2 % of the RMS of each tensor; exact kernels: 2e-5."""
     from remfx_amd import nnops, ops
+    from tests.attention_ref import localstate_autograd
     g = torch.Generator().manual_seed(B * 1000 + T)
     mk = lambda c: (torch.randn(B, heads * c, T, generator=g) * 0.8).to(DEV).requires_grad_(True)
     q, k, cont, qd = mk(ch), mk(ch), mk(ch), mk(nd)
     gy = torch.randn(B, heads * ch, T, generator=g).to(DEV)
-    qq, kk, cc, dd = (t.detach().double().cpu().requires_grad_(True) for t in (q, k, cont, qd))
-    qh, kh, chh = (t.view(B, heads, ch, T) for t in (qq, kk, cc))
-    dots = torch.einsum("bhct,bhcs->bhts", kh, qh) / ch ** 0.5
-    idx = torch.arange(T, dtype=torch.float64)
-    delta = (idx[:, None] - idx[None, :]).abs()
-    dec = torch.sigmoid(dd.view(B, heads, nd, T)) / 2
-    pen = -torch.arange(1, nd + 1, dtype=torch.float64).view(-1, 1, 1) * delta / nd ** 0.5
-    dots = dots + torch.einsum("fts,bhfs->bhts", pen, dec)
-    dots = dots.masked_fill(torch.eye(T, dtype=torch.bool), -100.0)
-    w = torch.softmax(dots, dim=2)
-    yr = torch.einsum("bhts,bhct->bhcs", w, chh).reshape(B, heads * ch, T)
-    yr.backward(gy.double().cpu())
-    ref = [yr.detach(), qq.grad, kk.grad, cc.grad, dd.grad]
+    ref = localstate_autograd(q, k, cont, qd, gy, heads, nd)
     prev = ops.gemm_precision()
     try:
         for m, bound in (("f32", 2e-5), ("bf16", 2e-2)):
