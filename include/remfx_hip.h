@@ -874,6 +874,24 @@ int rfx_segment_split(const float* x, float* out, int32_t rows, int64_t T, int32
 int rfx_segment_merge(const float* y, float* out, int32_t rows, int64_t T, int32_t L, int32_t hop, int32_t lead, int32_t trail,
                       int32_t S, void* stream);
 
+/* 'Same'-padded K-tap FIR over R rows of L samples (csrc/fir.hip).  The call it replaces is
+ * F.conv1d(x, w, padding=K//2) on (R, 1, L), which auraloss.perceptual.FIRFilter.forward runs once per signal:
+ *   y[r][n] = sum_{k < K} h[flip ? K-1-k : k] * x[r][n + k - K/2],   x = 0 outside [0, L)
+ * K odd, 1 <= K <= 1025 (anything else: -1); h = K fp32 taps on the device; x_stride / y_stride = row strides in samples (>= L:
+ * cropped views are read in place; y must not alias x).  (x2, y2) is an optional second signal of the same R, L filtered in the same
+ * launch (both NULL = one signal).  flip = 1 is the adjoint of flip = 0 -- the backward of the call above is the same entry point on
+ * the output gradient.  fp32 FMA chain in k order per sample, every output stored once: no atomics, no zero fill, bit-reproducible.
+ * A row never reads another row's samples.  L < 2^31 - 5121. */
+int rfx_fir_same(const float* x, float* y, const float* x2, float* y2, int32_t R, int64_t L, int64_t x_stride, int64_t y_stride,
+                 int64_t x2_stride, int64_t y2_stride, const float* h, int32_t K, int32_t flip, void* stream);
+/* Sum / difference of a stereo pair, the two adds of auraloss.freq.SumAndDifferenceSTFTLoss (x[:, 0] + x[:, 1], x[:, 0] - x[:, 1]):
+ * x (B, 2, T) with batch / channel strides in samples -> s, d contiguous (B, T); (x2, s2, d2) an optional second signal in the same
+ * launch.  The adjoint: gs, gd contiguous (B, T) -> gx contiguous (B, 2, T), gx[:, 0] = gs + gd, gx[:, 1] = gs - gd.  One fp32
+ * rounding per output. */
+int rfx_sum_diff(const float* x, float* s, float* d, const float* x2, float* s2, float* d2, int32_t B, int64_t T, int64_t x_bstride,
+                 int64_t x_cstride, int64_t x2_bstride, int64_t x2_cstride, void* stream);
+int rfx_sum_diff_adj(const float* gs, const float* gd, float* gx, int32_t B, int64_t T, void* stream);
+
 int rfx_abi_version(void);
 /* channel tiles per wave the MFMA forward kernel should use for M output rows and reduction length K
  * (0 = thin path; short-K, output-bound problems get R = 1 for occupancy);

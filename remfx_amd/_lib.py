@@ -267,6 +267,9 @@ SIGNATURES = {
     "rfx_cl_dconv_bwd": [_P, _P, _P],
     "rfx_segment_split": [_P, _P, _I32, _I64, _I32, _I32, _I32, _P],
     "rfx_segment_merge": [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _P],
+    "rfx_fir_same": [_P, _P, _P, _P, _I32, _I64, _I64, _I64, _I64, _I64, _P, _I32, _I32, _P],
+    "rfx_sum_diff": [_P, _P, _P, _P, _P, _P, _I32, _I64, _I64, _I64, _I64, _I64, _P],
+    "rfx_sum_diff_adj": [_P, _P, _P, _I32, _I64, _P],
 }
 
 _RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_stft_scaled_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",

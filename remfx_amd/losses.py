@@ -26,8 +26,18 @@ numbers per row: rfx_time_sums, rfx_time_loss_rows, and ONE rfx_time_loss_grad l
 `prefilter=(h_prev, h_cur, h_next)` is a keyword this port adds (auraloss applies its FIRFilter as a separate module): both signals are
 first replaced by h_prev s[n-1] + h_cur s[n] + h_next s[n+1], zeros outside the row -- conv1d with those weights and padding=1;
 pre-emphasis is (-0.85, 1, 0), and the three conv weights of an auraloss FIRFilter of the first-order kinds can be passed as they are
-(the A-weighting kind is not implemented).  Unknown `reduction`, a `prefilter` that is not three finite numbers, L < 1: ValueError.
+(the A-weighting kind is not a `prefilter`: it is the FIRFilter module below).  Unknown `reduction`, a `prefilter` that is not three
+finite numbers, L < 1: ValueError.
 SISDRLoss without a gradient to compute and with default keywords is the metric it always was: rfx_sisdr_sums + rfx_sisdr_finish.
+
+Perceptual prefilter and stereo term (auraloss.perceptual.FIRFilter, auraloss.freq.SumAndDifferenceSTFTLoss; PARITY UNPINNED; DESIGN.md
+4.3c):
+  FIRFilter(filter_type="hp" | "fd" | "aw", coef, fs, ntaps)   forward(input, target) -> both filtered: rfx_fir_same, a 'same'-padded
+                         K-tap FIR per row (K odd, <= 1025), both signals in one launch; the backward is the same kernel with the
+                         taps flipped.  `a_weighting_taps(fs, ntaps)` is auraloss's A-weighting design.  MultiResolutionSTFTLoss(
+                         perceptual_weighting=True) keeps raising: apply the module in front of the loss.
+  SumAndDifferenceSTFTLoss(..., w_sum, w_diff, **mrstft keywords)   (B, 2, T): rfx_sum_diff, then one inner MultiResolutionSTFTLoss
+                         on the sum and on the difference pair; (w_sum * sum + w_diff * diff) / 2.
 """
 import ctypes as C
 import os
@@ -345,7 +355,7 @@ def _check_honoured(scale, w_phs, perceptual_weighting, scale_invariance, output
     if w_phs != 0:
         bad.append(f"w_phs={w_phs!r} (the phase term)")
     if perceptual_weighting:
-        bad.append("perceptual_weighting=True (the A-weighting prefilter)")
+        bad.append("perceptual_weighting=True (apply FIRFilter(\"aw\", fs=...) to both signals in front of the loss instead)")
     if scale_invariance:
         bad.append("scale_invariance=True")
     if output != "loss":
@@ -640,3 +650,189 @@ def time_loss(time_loss_kwargs):
     if "prefilter" in kw and kw["prefilter"] is not None:
         kw["prefilter"] = tuple(kw["prefilter"])                           # an OmegaConf list from the command line
     return TIME_LOSSES[name](**kw), weight
+
+
+# ---- perceptual FIR prefilter and the sum / difference stereo loss ---------------------------------------------------
+FIR_MAX_TAPS = 1025                                                      # FIR_KMAX of csrc/fir.hip
+
+
+def a_weighting_taps(fs, ntaps=101):
+    """The `ntaps` float64 FIR taps auraloss.perceptual.FIRFilter("aw") builds at sample rate `fs`: the IEC/CD 1672 analog A-weighting
+    prototype (poles at f1..f4 = 20.598997, 107.65265, 737.86223, 12194.217 Hz, numerator (2 pi f4)^2 10^(A1000 / 20) s^4 with
+    A1000 = 1.9997), scipy.signal.bilinear to a digital IIR, its response at freqz(worN=512), and a least-squares linear-phase fit
+    firls(ntaps, w, |h|, fs=fs).  auraloss is not available to pin it: PARITY UNPINNED (the construction is restated from its source).
+    The taps are exactly symmetric.  With 101 taps the fit follows the curve to ~0.2 dB from 500 Hz up; BELOW that it cannot: at 100 Hz
+    it sits at -16.6 dB against the curve's -19.1 dB.  That is a property of auraloss's design (101 taps span 2 ms), not a defect here."""
+    import scipy.signal
+    if int(ntaps) != ntaps or ntaps < 1 or ntaps % 2 == 0:
+        raise ValueError(f"ntaps={ntaps!r}: an odd positive integer")
+    f1, f2, f3, f4, a1000 = 20.598997, 107.65265, 737.86223, 12194.217, 1.9997
+    nums = [(2 * np.pi * f4) ** 2 * (10 ** (a1000 / 20)), 0, 0, 0, 0]
+    dens = np.polymul([1, 4 * np.pi * f4, (2 * np.pi * f4) ** 2], [1, 4 * np.pi * f1, (2 * np.pi * f1) ** 2])
+    dens = np.polymul(np.polymul(dens, [1, 2 * np.pi * f3]), [1, 2 * np.pi * f2])
+    b, a = scipy.signal.bilinear(nums, dens, fs=fs)
+    w_iir, h_iir = scipy.signal.freqz(b, a, worN=512, fs=fs)
+    return np.asarray(scipy.signal.firls(int(ntaps), w_iir, np.abs(h_iir), fs=fs), dtype=np.float64)
+
+
+def _check_taps(taps):
+    """An odd number (1 .. FIR_MAX_TAPS) of numbers that are finite in fp32, as a float64 array."""
+    try:
+        h = np.asarray([float(v) for v in taps], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"taps={taps!r}: an odd-length sequence of finite numbers") from None
+    if h.size < 1 or h.size % 2 == 0 or h.size > FIR_MAX_TAPS:
+        raise ValueError(f"{h.size} taps: rfx_fir_same takes an odd number of taps, 1 to {FIR_MAX_TAPS}")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(h.astype(np.float32)).all():
+            raise ValueError("taps: every tap must be finite in fp32")
+    return h
+
+
+def _fir_rows(t, name):
+    """(..., L) -> R rows of L samples with unit sample stride; a cropped view keeps its row stride (no copy)."""
+    _req(t, name)
+    if t.dim() < 1 or t.shape[-1] < 1 or t.numel() == 0:
+        raise ValueError(f"{name}: the FIR filter needs (..., L) with L >= 1 and at least one row (got {tuple(t.shape)})")
+    L = t.shape[-1]
+    r = t.reshape(-1, L)
+    if r.stride(-1) != 1 or (r.shape[0] > 1 and r.stride(0) < L):
+        r = r.contiguous()
+    return r
+
+
+def _fir_launch(sigs, h, flip):
+    rows = [_fir_rows(s, "signal") for s in sigs]
+    R, L = rows[0].shape
+    outs = [torch.empty((R, L), device=r.device, dtype=torch.float32) for r in rows]
+    x2, y2 = (rows[1], outs[1]) if len(rows) == 2 else (None, None)
+    check(_lib.lib().rfx_fir_same(_ptr(rows[0]), _ptr(outs[0]), _ptr(x2), _ptr(y2), R, L, rows[0].stride(0), L,
+                                  x2.stride(0) if x2 is not None else 0, L, _ptr(h), h.numel(), 1 if flip else 0, _stream()),
+          "rfx_fir_same")
+    return [o.view(s.shape) for o, s in zip(outs, sigs)]
+
+
+def fir_same(sigs, h, flip=False):
+    """rfx_fir_same on one or two (..., L) fp32 device tensors: y[n] = sum_k h[k] x[n + k - K/2] per row, zeros outside the row --
+    F.conv1d(x, h, padding=K // 2) on (R, 1, L); flip=True uses h[K-1-k], the adjoint.  `h`: K fp32 taps on the device, K odd,
+    1 <= K <= 1025.  Two signals of one shape share a launch.  Returns new contiguous tensors of the inputs' shapes."""
+    sigs = list(sigs)
+    if any(s.device != h.device for s in sigs):
+        raise ValueError(f"taps on {h.device}, signal on {sigs[0].device}: move the filter with .to(device)")
+    if not (h.dtype == torch.float32 and h.dim() == 1 and h.is_contiguous()):
+        raise ValueError("taps: a contiguous 1-D fp32 tensor")
+    if h.numel() < 1 or h.numel() % 2 == 0 or h.numel() > FIR_MAX_TAPS:
+        raise ValueError(f"{h.numel()} taps: rfx_fir_same takes an odd number of taps, 1 to {FIR_MAX_TAPS}")
+    if len(sigs) == 2 and sigs[0].shape != sigs[1].shape:
+        return _fir_launch(sigs[:1], h, flip) + _fir_launch(sigs[1:], h, flip)
+    return _fir_launch(sigs, h, flip)
+
+
+class _FIRFn(torch.autograd.Function):
+    """(input, target) -> (fir(input), fir(target)) in one launch; the backward is the same kernel with flip = 1 on the output
+    gradients of the arguments that need one (one launch again when both do)."""
+
+    @staticmethod
+    def forward(ctx, input, target, h):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(h)
+        return tuple(fir_same((input, target), h))
+
+    @staticmethod
+    def backward(ctx, g_input, g_target):
+        (h,) = ctx.saved_tensors
+        want = [g if need else None for g, need in zip((g_input, g_target), ctx.needs_input_grad[:2])]
+        done = iter(fir_same([g for g in want if g is not None], h, flip=True)) if any(g is not None for g in want) else None
+        return tuple(next(done) if g is not None else None for g in want) + (None,)
+
+
+class FIRFilter(nn.Module):
+    """auraloss.perceptual.FIRFilter with auraloss's keywords: `forward(input, target)` returns both signals filtered, on (..., L)
+    fp32 device tensors, differentiable in both.  The conv weights, as upstream (cross-correlation, padding = K // 2):
+      "hp"  first-order pre-emphasis   (1, -coef, 0)
+      "fd"  folded differentiator      (1, 0, -coef)
+      "aw"  A-weighting                a_weighting_taps(fs, ntaps)
+    An even `ntaps` or an unknown kind is a ValueError.  `taps=` is this port's keyword: any odd-length (<= 1025) finite sequence, for
+    filters auraloss does not name (`filter_type`, `coef`, `ntaps` are then unused).  The taps are a NON-persistent buffer (`.to(device)`
+    moves them, checkpoints keep their keys).  One rfx_fir_same launch per call and one per backward.  PARITY UNPINNED (auraloss
+    absent); the fp64 reference is tests/fir_ref.py."""
+
+    def __init__(self, filter_type="hp", coef=0.85, fs=44100, ntaps=101, taps=None):
+        super().__init__()
+        self.filter_type, self.coef, self.fs, self.ntaps = filter_type, coef, fs, ntaps
+        if ntaps % 2 == 0:
+            raise ValueError(f"ntaps={ntaps!r} must be odd")
+        if taps is not None:
+            h = _check_taps(taps)
+        elif filter_type == "hp":
+            h = _check_taps((1.0, -coef, 0.0))
+        elif filter_type == "fd":
+            h = _check_taps((1.0, 0.0, -coef))
+        elif filter_type == "aw":
+            h = _check_taps(a_weighting_taps(fs, ntaps))
+        else:
+            raise ValueError(f"filter_type={filter_type!r}: one of 'hp', 'fd', 'aw'")
+        self.register_buffer("taps", torch.from_numpy(h.astype(np.float32)), persistent=False)
+
+    def forward(self, input, target):
+        return _FIRFn.apply(input, target, self.taps)
+
+
+class _SumDiffFn(torch.autograd.Function):
+    """(B, 2, T) input and target -> (s_in, d_in, s_tg, d_tg), each (B, 1, T), in one rfx_sum_diff launch; the gradient goes to the
+    input only (rfx_sum_diff_adj), as with the MR-STFT loss the four feed."""
+
+    @staticmethod
+    def forward(ctx, input, target):
+        _req(input, "input"); _req(target, "target")
+        x = input if input.stride(-1) == 1 else input.contiguous()
+        t = target if target.stride(-1) == 1 else target.contiguous()
+        B, _, T = x.shape
+        s_in, d_in, s_tg, d_tg = (torch.empty((B, 1, T), device=x.device, dtype=torch.float32) for _ in range(4))
+        check(_lib.lib().rfx_sum_diff(_ptr(x), _ptr(s_in), _ptr(d_in), _ptr(t), _ptr(s_tg), _ptr(d_tg), B, T, x.stride(0), x.stride(1),
+                                      t.stride(0), t.stride(1), _stream()), "rfx_sum_diff")
+        ctx.mark_non_differentiable(s_tg, d_tg)
+        return s_in, d_in, s_tg, d_tg
+
+    @staticmethod
+    def backward(ctx, gs, gd, _gs_tg, _gd_tg):
+        B, _, T = gs.shape
+        gx = torch.empty((B, 2, T), device=gs.device, dtype=torch.float32)
+        check(_lib.lib().rfx_sum_diff_adj(_ptr(gs.contiguous()), _ptr(gd.contiguous()), _ptr(gx), B, T, _stream()), "rfx_sum_diff_adj")
+        return gx, None
+
+
+class SumAndDifferenceSTFTLoss(nn.Module):
+    """auraloss.freq.SumAndDifferenceSTFTLoss: on (B, 2, T) input and target (anything else: ValueError),
+        loss = (w_sum * mrstft(L_in + R_in, L_tg + R_tg) + w_diff * mrstft(L_in - R_in, L_tg - R_tg)) / 2
+    through ONE inner MultiResolutionSTFTLoss (`self.mrstft`), which takes the remaining keywords: scale="mel" and the term weights
+    work through it.  The `/ 2` follows recent auraloss releases (older ones return the unhalved sum); auraloss is absent: PARITY
+    UNPINNED.  The gradient goes to the input only."""
+
+    def __init__(self, fft_sizes=FFT_SIZES, hop_sizes=HOP_SIZES, win_lengths=WIN_LENGTHS, w_sum=1.0, w_diff=1.0, **mrstft_kwargs):
+        super().__init__()
+        self.w_sum, self.w_diff = float(w_sum), float(w_diff)
+        self.mrstft = MultiResolutionSTFTLoss(fft_sizes, hop_sizes, win_lengths, **mrstft_kwargs)
+
+    def forward(self, input, target):
+        if input.dim() != 3 or input.shape[1] != 2 or input.shape != target.shape:
+            raise ValueError(f"SumAndDifferenceSTFTLoss needs (B, 2, T) input and target (got {tuple(input.shape)}, "
+                             f"{tuple(target.shape)})")
+        s_in, d_in, s_tg, d_tg = _SumDiffFn.apply(input, target)
+        return (self.w_sum * self.mrstft(s_in, s_tg) + self.w_diff * self.mrstft(d_in, d_tg)) / 2
+
+
+def perceptual_filter(perceptual_kwargs, sample_rate):
+    """FIRFilter from the wrappers' `perceptual_kwargs` = {filter_type, coef, ntaps}; `fs` is the wrapper's sample rate -- e.g.
+    `+model.network.perceptual_kwargs.filter_type=aw` on the command line."""
+    return FIRFilter(fs=sample_rate, **dict(perceptual_kwargs))
+
+
+def sum_diff_loss(sum_diff_kwargs, channels, **mrstft_kwargs):
+    """(module, weight) from the wrappers' `sum_diff_kwargs` = {w_sum, w_diff, weight=1.0}; `channels` = the network's output
+    channels."""
+    kw = dict(sum_diff_kwargs)
+    weight = float(kw.pop("weight", 1.0))
+    if channels != 2:
+        raise ValueError(f"sum_diff_kwargs needs a two-channel network (this one has {channels} output channel(s))")
+    return SumAndDifferenceSTFTLoss(**kw, **mrstft_kwargs), weight

@@ -14,8 +14,9 @@ import random
 import torch
 from torch import Tensor, nn
 
-from .losses import (DCLoss, ESRLoss, L1Loss, LogCoshLoss, MultiResolutionSTFTLoss, SDSDRLoss, SISDRLoss, SNRLoss,  # noqa: F401
-                     stft_memo, time_loss)                     # the loss classes are re-exported through remfx.models
+from .losses import (DCLoss, ESRLoss, FIRFilter, L1Loss, LogCoshLoss, MultiResolutionSTFTLoss, SDSDRLoss, SISDRLoss,  # noqa: F401
+                     SNRLoss, SumAndDifferenceSTFTLoss, perceptual_filter, stft_memo, sum_diff_loss,
+                     time_loss)                                # the loss classes are re-exported through remfx.models
 from .tcn import TCN
 from .utils import causal_crop
 
@@ -140,12 +141,36 @@ def _mrstft(num_bins, sample_rate, mrstft_kwargs=None):
 class _RemovalWrapper(nn.Module):
     """forward((x, target)) -> (loss, output); sample(x) -> output; loss = MRSTFT + 100 * L1, plus `weight` times one of the
     time-domain losses (losses.TIME_LOSSES) when the wrapper was built with `time_loss_kwargs` = {name, weight=1.0, **its keywords}
-    -- e.g. `+model.network.time_loss_kwargs.name=sisdr +model.network.time_loss_kwargs.weight=0.1` on the command line."""
+    -- e.g. `+model.network.time_loss_kwargs.name=sisdr +model.network.time_loss_kwargs.weight=0.1` on the command line.
+    `perceptual_kwargs` = {filter_type, coef, ntaps} puts a losses.FIRFilter (fs = the wrapper's sample rate) in front of the MRSTFT
+    term only -- where auraloss's `perceptual_weighting` sits; L1 and the time-domain term see the unfiltered signals -- e.g.
+    `+model.network.perceptual_kwargs.filter_type=aw`.  `sum_diff_kwargs` = {w_sum, w_diff, weight=1.0} adds `weight` times
+    losses.SumAndDifferenceSTFTLoss (the wrapper's MRSTFT keywords inside) on a two-channel output; a one-channel network is a
+    ValueError at construction."""
 
     def _set_time_loss(self, time_loss_kwargs):
         self.timeloss, self.time_loss_weight = time_loss(time_loss_kwargs) if time_loss_kwargs is not None else (None, 0.0)
 
+    def _set_perceptual(self, perceptual_kwargs, sum_diff_kwargs, sample_rate, num_bins, mrstft_kwargs, channels):
+        self.perceptual = perceptual_filter(perceptual_kwargs, sample_rate) if perceptual_kwargs is not None else None
+        self.sumdiff, self.sum_diff_weight = None, 0.0
+        if sum_diff_kwargs is not None:
+            kw = dict(n_bins=num_bins, sample_rate=sample_rate)
+            kw.update(dict(mrstft_kwargs) if mrstft_kwargs else {})
+            self.sumdiff, self.sum_diff_weight = sum_diff_loss(sum_diff_kwargs, channels, **kw)
+
+    def _loss_perceptual(self, output, target):
+        f_out, f_tgt = self.perceptual(output, target) if self.perceptual is not None else (output, target)
+        loss = self.mrstftloss(f_out, f_tgt) + self.l1loss(output, target) * 100
+        if self.timeloss is not None:
+            loss = loss + self.timeloss(output, target) * self.time_loss_weight
+        if self.sumdiff is not None:
+            loss = loss + self.sumdiff(output, target) * self.sum_diff_weight
+        return loss
+
     def _loss(self, output, target):
+        if self.perceptual is not None or self.sumdiff is not None:
+            return self._loss_perceptual(output, target)
         if self.timeloss is None:
             return self.mrstftloss(output, target) + self.l1loss(output, target) * 100
         return (self.mrstftloss(output, target) + self.l1loss(output, target) * 100
@@ -153,12 +178,14 @@ class _RemovalWrapper(nn.Module):
 
 
 class TCNModel(_RemovalWrapper):
-    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, perceptual_kwargs=None, sum_diff_kwargs=None,
+                 **kwargs):
         super().__init__()
         self.model = TCN(**kwargs)
         self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
         self._set_time_loss(time_loss_kwargs)
+        self._set_perceptual(perceptual_kwargs, sum_diff_kwargs, sample_rate, num_bins, mrstft_kwargs, self.model.noutputs)
 
     def forward(self, batch):
         x, target = batch
@@ -172,7 +199,8 @@ class TCNModel(_RemovalWrapper):
 
 
 class DemucsModel(_RemovalWrapper):
-    def __init__(self, sample_rate, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs) -> None:
+    def __init__(self, sample_rate, mrstft_kwargs=None, time_loss_kwargs=None, perceptual_kwargs=None, sum_diff_kwargs=None,
+                 **kwargs) -> None:
         super().__init__()
         from .hdemucs import HDemucs
         self.model = HDemucs(**kwargs)
@@ -180,6 +208,7 @@ class DemucsModel(_RemovalWrapper):
         self.mrstftloss = _mrstft(self.num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
         self._set_time_loss(time_loss_kwargs)
+        self._set_perceptual(perceptual_kwargs, sum_diff_kwargs, sample_rate, self.num_bins, mrstft_kwargs, self.model.audio_channels)
 
     def forward(self, batch):
         x, target = batch
@@ -192,7 +221,7 @@ class DemucsModel(_RemovalWrapper):
 
 class OpenUnmixModel(_RemovalWrapper):
     def __init__(self, n_fft: int = 2048, hop_length: int = 512, n_channels: int = 1, alpha: float = 0.3,
-                 sample_rate: int = 22050, mrstft_kwargs=None, time_loss_kwargs=None):
+                 sample_rate: int = 22050, mrstft_kwargs=None, time_loss_kwargs=None, perceptual_kwargs=None, sum_diff_kwargs=None):
         super().__init__()
         from .umx import OpenUnmix, Separator
         from .utils import spectrogram
@@ -207,6 +236,7 @@ class OpenUnmixModel(_RemovalWrapper):
         self.mrstftloss = _mrstft(self.num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
         self._set_time_loss(time_loss_kwargs)
+        self._set_perceptual(perceptual_kwargs, sum_diff_kwargs, sample_rate, self.num_bins, mrstft_kwargs, n_channels)
 
     def forward(self, batch):
         x, target = batch
@@ -220,13 +250,15 @@ class OpenUnmixModel(_RemovalWrapper):
 
 
 class DCUNetModel(_RemovalWrapper):
-    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, perceptual_kwargs=None, sum_diff_kwargs=None,
+                 **kwargs):
         super().__init__()
         from .dcunet import DCUNet
         self.model = DCUNet(**kwargs)          # asteroid keeps its own sample_rate default (wrapper swallows it)
         self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
         self._set_time_loss(time_loss_kwargs)
+        self._set_perceptual(perceptual_kwargs, sum_diff_kwargs, sample_rate, num_bins, mrstft_kwargs, 1)      # (B, 1, T) output
 
     def forward(self, batch):
         x, target = batch
@@ -243,7 +275,8 @@ class DPTNetModel(_RemovalWrapper):
     """models.py:327-344: asteroid DPTNet (cfg/model/dptnet.yaml) + MRSTFT + 100 L1; no target crop (the network pads / crops
     its output to the input length)."""
 
-    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, **kwargs):
+    def __init__(self, sample_rate, num_bins, mrstft_kwargs=None, time_loss_kwargs=None, perceptual_kwargs=None, sum_diff_kwargs=None,
+                 **kwargs):
         super().__init__()
         from .dptnet import DPTNet
         self.model = DPTNet(**kwargs)
@@ -251,6 +284,7 @@ class DPTNetModel(_RemovalWrapper):
         self.mrstftloss = _mrstft(num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
         self._set_time_loss(time_loss_kwargs)
+        self._set_perceptual(perceptual_kwargs, sum_diff_kwargs, sample_rate, num_bins, mrstft_kwargs, 1)      # (B, 1, T) output
 
     def forward(self, batch):
         x, target = batch
