@@ -112,38 +112,102 @@ def _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale):
     return d
 
 
+def _empty(name, shape, dtype, device):
+    return torch.empty(shape, device=device, dtype=dtype)
+
+
+def layer_forward(x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps, train, alloc=_empty):
+    """One fused layer on x (Bn, A, 256 k, C) channels-last bf16: y, and what the backward pass reads -- a, hpre (Bn, A, 256 k, HP) bf16
+    and stats (Bn * A, 4) fp32 (mean1, rstd1, mean2, rstd2); a / hpre are None without `train`, stats too where a sample is one tile.
+    alloc(name, shape, dtype, device) provides every buffer the kernels write (the kernel tests hand out guarded ones)."""
+    Bn, A, Tt, Cc = x.shape
+    H = w1.shape[0]
+    if Tt % T or not x.is_contiguous() or x.dtype != torch.bfloat16:
+        raise ValueError("ClDconvLayerFn: dense (N, A, 256 k, C) bf16 input")
+    tb = tables(Cc, H)
+    TPS = Tt // T                                   # tiles per sample: 1 = frequency branch, > 1 = a time-branch clip
+    HP, S, dev = tb["HP"], Bn * A * TPS, x.device
+    y = alloc("y", x.shape, x.dtype, dev)
+    d = _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale)
+    d.TPS = TPS
+    d.grid = GRID_FWD
+    d.x, d.y = x.data_ptr(), y.data_ptr()
+    d.w1p = clchain.packed(tb["w1p"], w1).data_ptr()
+    d.w2p = clchain.packed(tb["w2p"], w2).data_ptr()
+    a = hpre = stats = part = None
+    if train or TPS > 1:
+        stats = alloc("stats", (Bn * A, 4), torch.float32, dev)
+        d.stats = stats.data_ptr()
+    if TPS > 1:
+        part = alloc("part", (S, 2), torch.float32, dev)
+        d.partial = part.data_ptr()
+    if train:
+        a = alloc("a", (Bn, A, Tt, HP), torch.bfloat16, dev)
+        hpre = alloc("hpre", (Bn, A, Tt, HP), torch.bfloat16, dev)
+        d.a, d.hpre = a.data_ptr(), hpre.data_ptr()
+    check(_lib.lib().rfx_cl_dconv_fwd(C.byref(d), C.c_void_p(ops.raw_stream())), "rfx_cl_dconv_fwd")
+    return y, a, hpre, stats
+
+
+def layer_backward(gy, x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps, alloc=_empty):
+    """The backward pass of layer_forward from what it saved: dx, dz (.., 2 C) and dh (.., HP) (bf16, the operands of the two
+    weight-gradient GEMMs and of the dx convolution), pg (5 C + 2 H fp32: dscale | dgn2w | dgn2b | dgn1w | dgn1b; None when an armed
+    GradSink took the five sums), dw1, db1, dw2, db2 (None when the sink took them)."""
+    Bn, A, Tt, Cc = x.shape
+    H = w1.shape[0]
+    tb = tables(Cc, H)
+    TPS = Tt // T
+    HP, S, dev = tb["HP"], Bn * A * TPS, x.device
+    passes = TPS > 1 or Cc != 48                    # several tiles per sample, or images too large for the one-pass kernel's LDS
+    if not gy.is_contiguous():
+        gy = gy.contiguous()
+    dx = alloc("dx", x.shape, x.dtype, dev)
+    dz = alloc("dz", (Bn, A, Tt, 2 * Cc), torch.bfloat16, dev)
+    dh = alloc("dh", (Bn, A, Tt, HP), torch.bfloat16, dev)
+    npg = 5 * Cc + 2 * H
+    partial = alloc("partial", (min(GRID, S), npg), torch.float32, dev)
+    # the five small gradients go straight into the parameters' slices of the flat gradient buffer when a GradSink is armed
+    # (autograd would add each returned tensor into .grad with a launch of its own)
+    sink = ops.SINK
+    tgt = [sink.lookup(p) for p in (scale, g2w, g2b, g1w, g1b)] if sink is not None else [None]
+    direct = all(t is not None for t in tgt)
+    pg = None if direct else alloc("pg", (npg,), torch.float32, dev)
+    d = _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale)
+    d.TPS = TPS
+    d.gy, d.y, d.a, d.hpre, d.stats = gy.data_ptr(), dx.data_ptr(), a.data_ptr(), hpre.data_ptr(), stats.data_ptr()
+    d.dz, d.dh, d.partial = dz.data_ptr(), dh.data_ptr(), partial.data_ptr()
+    d.w2p = clchain.packed(tb["w2p"], w2).data_ptr()
+    d.w2dp = clchain.packed(tb["w2dp"], w2).data_ptr()
+    if passes:
+        tsum = alloc("tsum", (S, 2), torch.float32, dev)
+        sums = alloc("sums", (Bn * A, 4), torch.float32, dev)
+        d.tsum, d.sums = tsum.data_ptr(), sums.data_ptr()
+    else:
+        d.w1dp = clchain.packed(tb["w1dp"], w1).data_ptr()
+    if direct:
+        for q, t in enumerate(tgt):
+            d.pg_dst[q] = t[1].data_ptr()
+    check(_lib.lib().rfx_cl_dconv_bwd(C.byref(d), C.c_void_p(pg.data_ptr() if pg is not None else None), C.c_void_p(ops.raw_stream())),
+          "rfx_cl_dconv_bwd")
+    if direct:
+        for t in tgt:
+            sink.wrote(t[0])
+    if passes:                                      # dx = gy + the transposed 3-tap convolution of dh (taps cross tile edges)
+        fx = _dx_form(Cc, H, dil)
+        clast.conv(fx, clchain.packed(fx, w1), dh, Bn, A, Tt, A, "store", out0=dx, res=gy)
+    f1, f2 = _wforms(Cc, H, dil)
+    dw2, db2 = clchain._wgrad(f2, dz, a, Bn, A, A, Tt, w2, b2)
+    dw1, db1 = clchain._wgrad(f1, dh, x, Bn, A, A, Tt, w1, b1)
+    return dx, dz, dh, pg, dw1, db1, dw2, db2
+
+
 class ClDconvLayerFn(torch.autograd.Function):
     """x (Bn, A, 256, C) channels-last bf16 -> y of the same shape; parameters as the upstream modules hold them."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps):
-        Bn, A, Tt, Cc = x.shape
-        H = w1.shape[0]
-        if Tt % T or not x.is_contiguous() or x.dtype != torch.bfloat16:
-            raise ValueError("ClDconvLayerFn: dense (N, A, 256 k, C) bf16 input")
-        tb = tables(Cc, H)
-        TPS = Tt // T                                   # tiles per sample: 1 = frequency branch, > 1 = a time-branch clip
-        HP, S, dev = tb["HP"], Bn * A * TPS, x.device
         train = any(ctx.needs_input_grad)
-        y = torch.empty_like(x)
-        d = _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale)
-        d.TPS = TPS
-        d.grid = GRID_FWD
-        d.x, d.y = x.data_ptr(), y.data_ptr()
-        d.w1p = clchain.packed(tb["w1p"], w1).data_ptr()
-        d.w2p = clchain.packed(tb["w2p"], w2).data_ptr()
-        a = hpre = stats = part = None
-        if train or TPS > 1:
-            stats = torch.empty((Bn * A, 4), device=dev, dtype=torch.float32)
-            d.stats = stats.data_ptr()
-        if TPS > 1:
-            part = torch.empty((S, 2), device=dev, dtype=torch.float32)
-            d.partial = part.data_ptr()
-        if train:
-            a = torch.empty((Bn, A, Tt, HP), device=dev, dtype=torch.bfloat16)
-            hpre = torch.empty_like(a)
-            d.a, d.hpre = a.data_ptr(), hpre.data_ptr()
-        check(_lib.lib().rfx_cl_dconv_fwd(C.byref(d), C.c_void_p(ops.raw_stream())), "rfx_cl_dconv_fwd")
+        y, a, hpre, stats = layer_forward(x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps, train)
         if train:
             ctx.save_for_backward(x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale)
             ctx.cfg = (dil, eps)
@@ -153,52 +217,9 @@ class ClDconvLayerFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale = ctx.saved_tensors
         dil, eps = ctx.cfg
-        Bn, A, Tt, Cc = x.shape
-        H = w1.shape[0]
-        tb = tables(Cc, H)
-        TPS = Tt // T
-        HP, S, dev = tb["HP"], Bn * A * TPS, x.device
-        passes = TPS > 1 or Cc != 48                    # several tiles per sample, or images too large for the one-pass kernel's LDS
-        if not gy.is_contiguous():
-            gy = gy.contiguous()
-        dx = torch.empty_like(x)
-        dz = torch.empty((Bn, A, Tt, 2 * Cc), device=dev, dtype=torch.bfloat16)
-        dh = torch.empty((Bn, A, Tt, HP), device=dev, dtype=torch.bfloat16)
-        npg = 5 * Cc + 2 * H
-        partial = torch.empty((min(GRID, S), npg), device=dev, dtype=torch.float32)
-        # the five small gradients go straight into the parameters' slices of the flat gradient buffer when a GradSink is armed
-        # (autograd would add each returned tensor into .grad with a launch of its own)
-        sink = ops.SINK
-        tgt = [sink.lookup(p) for p in (scale, g2w, g2b, g1w, g1b)] if sink is not None else [None]
-        direct = all(t is not None for t in tgt)
-        pg = None if direct else torch.empty(npg, device=dev, dtype=torch.float32)
-        d = _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale)
-        d.TPS = TPS
-        d.gy, d.y, d.a, d.hpre, d.stats = gy.data_ptr(), dx.data_ptr(), a.data_ptr(), hpre.data_ptr(), stats.data_ptr()
-        d.dz, d.dh, d.partial = dz.data_ptr(), dh.data_ptr(), partial.data_ptr()
-        d.w2p = clchain.packed(tb["w2p"], w2).data_ptr()
-        d.w2dp = clchain.packed(tb["w2dp"], w2).data_ptr()
-        if passes:
-            tsum = torch.empty((S, 2), device=dev, dtype=torch.float32)
-            sums = torch.empty((Bn * A, 4), device=dev, dtype=torch.float32)
-            d.tsum, d.sums = tsum.data_ptr(), sums.data_ptr()
-        else:
-            d.w1dp = clchain.packed(tb["w1dp"], w1).data_ptr()
-        if direct:
-            for q, t in enumerate(tgt):
-                d.pg_dst[q] = t[1].data_ptr()
-        check(_lib.lib().rfx_cl_dconv_bwd(C.byref(d), C.c_void_p(pg.data_ptr() if pg is not None else None), C.c_void_p(ops.raw_stream())),
-              "rfx_cl_dconv_bwd")
-        if direct:
-            for t in tgt:
-                sink.wrote(t[0])
-        if passes:                                      # dx = gy + the transposed 3-tap convolution of dh (taps cross tile edges)
-            fx = _dx_form(Cc, H, dil)
-            clast.conv(fx, clchain.packed(fx, w1), dh, Bn, A, Tt, A, "store", out0=dx, res=gy)
-        f1, f2 = _wforms(Cc, H, dil)
-        dw2, db2 = clchain._wgrad(f2, dz, a, Bn, A, A, Tt, w2, b2)
-        dw1, db1 = clchain._wgrad(f1, dh, x, Bn, A, A, Tt, w1, b1)
-        if direct:
+        Cc, H = x.shape[3], w1.shape[0]
+        dx, dz, dh, pg, dw1, db1, dw2, db2 = layer_backward(gy, x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps)
+        if pg is None:
             dscale = dg2w = dg2b = dg1w = dg1b = None
         else:
             dscale, dg2w, dg2b = pg[:Cc], pg[Cc:3 * Cc], pg[3 * Cc:5 * Cc]
