@@ -197,7 +197,12 @@ int rfx_gemm_wgrad(const rfx_gemm_desc* d, const rfx_ktab_entry* ktab, const flo
  *   torch.istft (HDemucs _ispec, Separator); with herm=0 / in_mode=0 it is the
  *   backward (adjoint) of the STFT.
  * x: [R][T]; frame f covers padded samples [f*hop, f*hop + n_fft); the hann window
- * of `win` samples is centred in n_fft.  n_fft in {512, 1024, 2048, 4096}.
+ * of `win` samples is centred in n_fft.  n_fft = 2^k, 16 <= n_fft <= 32768.  512 / 1024 / 2048 / 4096 run on the
+ * register-pass kernels described above (csrc/fft.hip); every other size on a generic LDS radix-4 family
+ * (csrc/fft_any.hip) with the same descriptor semantics, whose synthesis is two launches by ownership: the windowed
+ * time-domain frames go to scratch, then one thread per output sample adds the frames that cover the padded
+ * positions mapping to it (the position itself, its mirror images under the reflect padding, or the offset position
+ * times `mul`) in a fixed order and stores once -- no atomic form, no zero fill, for any geometry.
  */
 enum rfx_stft_out {
   RFX_STFT_COMPLEX = 0, /* [R][bins][frames_out][2] (torch view_as_real layout) */
@@ -228,8 +233,9 @@ typedef struct rfx_stft_desc {
 
 int rfx_fft_analysis(const rfx_stft_desc* d, const float* x, const float* window, const float* mul,
                      float* out, void* stream);
-/* ws: rfx_fft_synthesis_ws(d) floats of scratch (no initialisation needed): the running sums a workgroup carries from one frame
- * batch to the next and the padded edge zones of the reflect-padded adjoint */
+/* ws: rfx_fft_synthesis_ws(d) floats of scratch (no initialisation needed).  n_fft 512 / 1024 / 2048 / 4096: the running sums a
+ * workgroup carries from one frame batch to the next and the padded edge zones of the reflect-padded adjoint.  Every other size:
+ * the windowed frames, R * frames_out * n_fft floats.  -1: a descriptor no kernel covers. */
 int64_t rfx_fft_synthesis_ws(const rfx_stft_desc* d);
 int rfx_fft_synthesis(const rfx_stft_desc* d, const float* spec, const float* window, const float* mul,
                       float* ws, float* out, void* stream);

@@ -26,6 +26,7 @@
 //     two LDS reads; workgroups that write the same (row, bin) lines are placed on the same XCD (block b runs on XCD b % 8) so
 //     partial-line stores merge in one L2.
 #include "common.h"
+#include "fft_any.h"
 #include <algorithm>
 #include <climits>
 #include <math.h>
@@ -752,6 +753,7 @@ static SynOwn syn_own_geometry(const rfx_stft_desc* d) {
   return o;
 }
 extern "C" int64_t rfx_fft_synthesis_ws(const rfx_stft_desc* d) {
+  if (fft_any_covers(d)) return fft_any_synthesis_ws(d);      // every other power of two from 16 to 32768: csrc/fft_any.hip
   if (!stft_desc_ok(d)) return -1;
   const int64_t n = syn_own_geometry(d).ws_floats;
   return n > 0 ? n : 1;
@@ -1079,10 +1081,12 @@ extern "C" int rfx_stft_pair_loss(const rfx_stft_desc* d, const float* x, const 
 
 extern "C" int rfx_fft_analysis(const rfx_stft_desc* d, const float* x, const float* window,
                                 const float* mul, float* out, void* stream) {
+  if (fft_any_covers(d)) return fft_any_analysis(d, x, window, mul, out, stream);
   return launch_fft<false>(d, x, window, mul, out, stream);
 }
 extern "C" int rfx_fft_synthesis(const rfx_stft_desc* d, const float* spec, const float* window,
                                  const float* mul, float* ws, float* out, void* stream) {
+  if (fft_any_covers(d)) return fft_any_synthesis(d, spec, window, mul, ws, out, stream);
   if (d && d->mode != RFX_STFT_COMPLEX && d->mode != RFX_STFT_CAC && d->mode != RFX_STFT_COMPLEX_FM) return -1;
   return launch_fft<true>(d, spec, window, mul, out, stream, nullptr, ws);
 }

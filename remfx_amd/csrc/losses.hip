@@ -418,7 +418,16 @@ extern "C" int rfx_stft_scaled_loss_grad(const float* xc, const float* mx, const
   if (!xc || !mx || !my || !sums || !gxc || R <= 0 || frames <= 0 || bins <= 0 || n_out <= 0) return -1;
   if (fbt_idx ? !fbt_w : (n_out != bins)) return -1;
   const size_t lds = (size_t)n_out * sizeof(float);
-  if (lds > RFX_SCALED_LDS_MAX) return -1;
+  if (lds > RFX_SCALED_LDS_MAX) {
+    // the linear scale at n_fft = 32768: a frame's 16385 dM values are four bytes more than the default dynamic LDS limit
+    if (lds > 160 * 1024) return -1;
+    static size_t attr_lds = 0;
+    if (lds > attr_lds) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_scaled_loss_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds) != hipSuccess) return -3;
+      attr_lds = lds;
+    }
+  }
   const int g = frames > 512 ? 512 : frames;
   hipLaunchKernelGGL(stft_scaled_loss_grad_kernel, dim3(g, R), dim3(256), lds, (hipStream_t)stream, (const float2*)xc, mx, my, R,
                      frames, bins, n_out, fbt_idx, fbt_w, eps, sums, per_example_sc, w_sc, w_lm, w_lin, gup, (float2*)gxc);

@@ -17,6 +17,12 @@ builds -- `n_bins` / `sample_rate` are inert, as upstream, an
 One deliberate difference: a mel filter without a non-zero weight (more filters than the low bins can carry) makes auraloss return
 NaN (log 0 - log 0); here the constructor raises ValueError naming the resolution and the count.
 `STFTLoss` is the single-resolution class auraloss exports, over the same function.
+Resolutions: every power of two from 16 to 32768 (stft._desc), e.g. micro-tcn's (32, 128, 512, 2048, 8192, 32768).  512 / 1024 / 2048
+take the paired one-launch forward and the fused gradient; every other size goes through two analyses + rfx_stft_loss_reduce /
+rfx_stft_loss_grad + rfx_fft_synthesis (there is no paired or fused form for them).  scale="mel" stages a frame's magnitudes and the
+bank in 64 KiB of LDS, which n_fft = 8192 and above do not fit: scale="mel" with any n_fft > 4096 raises NotImplementedError at
+construction, naming the resolution.  The linear scale has no such limit, with default and non-default term weights.
+`RandomResolutionSTFTLoss` is not ported.
 
 Time-domain losses (auraloss.time; auraloss is not available to pin them: PARITY UNPINNED, restated in tests/time_loss_ref.py), on
 (..., L) inputs taken as R rows of L samples, reduction "mean" / "sum" / "none" over the rows, differentiable in the prediction:
@@ -53,6 +59,7 @@ from .ops import _ptr, _req, _stream, zeros
 FFT_SIZES = (1024, 2048, 512)
 HOP_SIZES = (120, 240, 50)
 WIN_LENGTHS = (600, 1200, 240)
+MEL_MAX_N_FFT = 4096                                              # rfx_stft_scaled_loss with a bank: 64 KiB of LDS per frame
 
 
 FUSED_GRAD = os.environ.get("RFX_LOSS_FUSED_GRAD", "1") != "0"    # A/B: 0 = rfx_stft_loss_grad_m + rfx_fft_synthesis as two launches
@@ -393,6 +400,10 @@ class MultiResolutionSTFTLoss(nn.Module):
             if n_bins is None or sample_rate is None:
                 raise ValueError('scale="mel" needs n_bins (the number of mel filters) and sample_rate')
             for k, n_fft in enumerate(self.fft_sizes):
+                if n_fft > MEL_MAX_N_FFT:
+                    raise NotImplementedError(f'scale="mel" at resolution {k} (n_fft={n_fft}): the mel reduction kernel holds a frame\'s '
+                                              f"magnitudes and the bank in LDS and covers n_fft <= {MEL_MAX_N_FFT}; use the linear "
+                                              "scale (scale=None) for larger resolutions")
                 fb = mel_filterbank(sample_rate, n_fft, n_bins)
                 empty = int((fb.abs().sum(1) == 0).sum())
                 if empty:

@@ -1,4 +1,6 @@
-"""STFT / iSTFT on the framed-FFT HIP kernels (csrc/fft.hip), with autograd.
+"""STFT / iSTFT on the framed-FFT HIP kernels, with autograd: n_fft = any power of two from 16 to 32768 (512 / 1024 / 2048 /
+4096, the lengths of the RemFX configs, on the register-pass kernels of csrc/fft.hip; the others on the generic LDS kernels of
+csrc/fft_any.hip, behind the same three entry points).  Other lengths raise ValueError.
 
 Semantics follow torch.stft(center=True, pad_mode="reflect", onesided=True) and
 torch.istft(center=True), the ops behind utils.py:148-154, HDemucs _spec/_ispec,
@@ -14,6 +16,7 @@ from ._lib import StftDesc, check
 from .ops import _ptr, _req, _stream, zeros
 
 MODES = {"complex": 0, "cac": 1, "mag": 2, "pow": 3, "magpow": 4, "complex_fm": 5}
+N_FFT_MIN, N_FFT_MAX = 16, 32768
 _WINDOWS = {}
 
 
@@ -28,8 +31,9 @@ def hann(win, device):
 
 def _desc(R, T, n_fft, hop, win, bins, frame0, frames_out, mode, extra_pad=(0, 0), in_mode=0,
           in_offset=0, herm=0, scale=1.0, eps=0.0, alpha=1.0, accum=0):
-    if n_fft not in (512, 1024, 2048, 4096):
-        raise ValueError(f"n_fft={n_fft}: the HIP FFT kernels cover 512/1024/2048/4096")
+    n = int(n_fft) if int(n_fft) == n_fft else 0
+    if not (N_FFT_MIN <= n <= N_FFT_MAX and n & (n - 1) == 0):
+        raise ValueError(f"n_fft={n_fft}: the HIP FFT kernels cover the powers of two from {N_FFT_MIN} to {N_FFT_MAX}")
     d = StftDesc()
     d.R, d.T, d.n_fft, d.hop, d.win = R, T, n_fft, hop, win
     d.bins, d.frame0, d.frames_out, d.mode = bins, frame0, frames_out, mode
@@ -40,7 +44,8 @@ def _desc(R, T, n_fft, hop, win, bins, frame0, frames_out, mode, extra_pad=(0, 0
 
 
 def syn_ws(d, device):
-    """Scratch of one rfx_fft_synthesis launch (uninitialised): carried sums + padded edge zones (include/remfx_hip.h)."""
+    """Scratch of one rfx_fft_synthesis launch (uninitialised): carried sums + padded edge zones, or the windowed frames of the
+    generic sizes (include/remfx_hip.h)."""
     return torch.empty(int(_lib.lib().rfx_fft_synthesis_ws(C.byref(d))), device=device, dtype=torch.float32)
 
 
