@@ -332,6 +332,17 @@ int rfx_row_moments_slots(int64_t L);
 int rfx_row_moments(const float* x, int32_t R, int64_t L, double* sums, float* mean, float* stdv, float eps, float* coef_a,
                     float* coef_b, void* stream);
 int rfx_row_affine(const float* x, const float* a, const float* b, float* out, int32_t R, int64_t L, void* stream);
+/* Multi-source Hybrid Demucs (S >= 2 sources; the tail of remfx_amd/hdemucs.py forward, torchaudio HDemucs.forward
+ * `x = x * std[:, None] + mean[:, None]` ... `xt = xt * stdt[:, None] + meant[:, None]; x = xt + x`): the `group` = S * Cin rows of a clip
+ * share the clip's coefficient pair, a and b hold R / group (N / group) values.
+ * rfx_row_affine_add: out[r][i] = x[r][i] * a[r / group] + b[r / group] + y[r][i] over R rows of L samples: the time branch's
+ *   de-standardisation and the add of the inverse STFT in one pass (replaces a rfx_row_affine followed by a rfx_add_bcast).
+ * rfx_fm_cm_affine_g: rfx_fm_cm_affine (below) with row n taking coef_a[n / group], coef_b[n / group]; group == 1 returns its bits.
+ *   to_fm = 1: out[n][f][bin][c] = in[n][c][bin][f] a + b; to_fm = 0 (the backward, coef_b may be NULL): the transposed copy times a. */
+int rfx_row_affine_add(const float* x, const float* a, const float* b, const float* y, float* out, int32_t R, int32_t group, int64_t L,
+                       void* stream);
+int rfx_fm_cm_affine_g(const float* in, float* out, const float* coef_a, const float* coef_b, int32_t N, int32_t group, int32_t bins,
+                       int32_t F, int32_t to_fm, void* stream);
 
 /* Inverted dropout with a counter-based mask (keep(i) = u24(splitmix64(seed, i)) >= p; out = x / (1 - p) or 0); the backward pass
  * is the same call on the gradient with the same seed.  Replaces F.dropout(train=True) in Cnn14 (classifier.py:211-284) and the
@@ -879,6 +890,14 @@ int rfx_cl_rowsum(const rfx_cl_tensor* x, int32_t N, int32_t A, int32_t B, int32
 int rfx_segment_split(const float* x, float* out, int32_t rows, int64_t T, int32_t L, int32_t hop, int32_t S, void* stream);
 int rfx_segment_merge(const float* y, float* out, int32_t rows, int64_t T, int32_t L, int32_t hop, int32_t lead, int32_t trail,
                       int32_t S, void* stream);
+/* The same plan for networks that take multi-channel clips (HDemucs.separate through segment.apply(group_channels=True)): the channels
+ * of a clip stay together.
+ *   split_c: x (B, C, T) -> out (B * S, C, L), out[(b * S + i) * C + c][j] = x[b][c][s_i + j].
+ *   merge_c: y (B * S, Co, Lp) -> out (B, Co, T - lead - trail), row (b, c) blended from y[(b * S + i) * Co + c] with the weights and the
+ *            store-once ownership of rfx_segment_merge; Co is the network's output channel count and need not equal C. */
+int rfx_segment_split_c(const float* x, float* out, int32_t B, int32_t C, int64_t T, int32_t L, int32_t hop, int32_t S, void* stream);
+int rfx_segment_merge_c(const float* y, float* out, int32_t B, int32_t Co, int64_t T, int32_t L, int32_t hop, int32_t lead, int32_t trail,
+                        int32_t S, void* stream);
 
 /* 'Same'-padded K-tap FIR over R rows of L samples (csrc/fir.hip).  The call it replaces is
  * F.conv1d(x, w, padding=K//2) on (R, 1, L), which auraloss.perceptual.FIRFilter.forward runs once per signal:

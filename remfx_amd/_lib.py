@@ -236,6 +236,8 @@ SIGNATURES = {
     "rfx_row_moments_slots": [_I64],
     "rfx_row_moments": [_P, _I32, _I64, _P, _P, _P, C.c_float, _P, _P, _P],
     "rfx_row_affine": [_P, _P, _P, _P, _I32, _I64, _P],
+    "rfx_row_affine_add": [_P, _P, _P, _P, _P, _I32, _I32, _I64, _P],
+    "rfx_fm_cm_affine_g": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],
     "rfx_lstm_pack_bytes": [_I32],
     "rfx_lstm_pack": [_P, _I32, _P, _P],
     "rfx_lstm_cat_params": [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P],
@@ -267,6 +269,8 @@ SIGNATURES = {
     "rfx_cl_dconv_bwd": [_P, _P, _P],
     "rfx_segment_split": [_P, _P, _I32, _I64, _I32, _I32, _I32, _P],
     "rfx_segment_merge": [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _P],
+    "rfx_segment_split_c": [_P, _P, _I32, _I32, _I64, _I32, _I32, _I32, _P],
+    "rfx_segment_merge_c": [_P, _P, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _P],
     "rfx_fir_same": [_P, _P, _P, _P, _I32, _I64, _I64, _I64, _I64, _I64, _P, _I32, _I32, _P],
     "rfx_sum_diff": [_P, _P, _P, _P, _P, _P, _I32, _I64, _I64, _I64, _I64, _I64, _P],
     "rfx_sum_diff_adj": [_P, _P, _P, _I32, _I64, _P],

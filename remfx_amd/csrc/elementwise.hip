@@ -551,6 +551,73 @@ extern "C" int rfx_row_affine(const float* x, const float* a, const float* b, fl
   return 0;
 }
 
+// Multi-source tails of Hybrid Demucs (hdemucs.py forward, S >= 2 sources): one (std, mean) pair per clip is shared by the clip's
+// `group` = S * Cin rows.
+// out[r][i] = x[r][i] * a[r / group] + b[r / group] + y[r][i]: the time branch's de-standardisation and the add of the inverse STFT in
+// one pass.  The rows of a group are contiguous, so the coefficient index is i / (group * L).
+__global__ void row_affine_add_kernel(const float* __restrict__ x, const float* __restrict__ a, const float* __restrict__ b,
+                                      const float* __restrict__ y, float* __restrict__ out, int64_t GL, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t q = i / GL;
+    out[i] = fmaf(x[i], a[q], b[q]) + y[i];
+  }
+}
+extern "C" int rfx_row_affine_add(const float* x, const float* a, const float* b, const float* y, float* out, int32_t R, int32_t group,
+                                  int64_t L, void* stream) {
+  if (!x || !a || !b || !y || !out || R <= 0 || group <= 0 || R % group || L <= 0) return -1;
+  hipLaunchKernelGGL(row_affine_add_kernel, dim3(grid_for((int64_t)R * L)), dim3(256), 0, (hipStream_t)stream, x, a, b, y, out,
+                     (int64_t)group * L, (int64_t)R * L);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+
+// rfx_fm_cm_affine (cl_elem.hip) with row n taking the coefficients of clip n / group: the layout change between the channel-major
+// spectrum of the last transposed convolution, x[n][c][bin][frame], and the frame-major one the inverse STFT reads,
+// y[n][frame][bin][c], fused with the de-standardisation (to_fm = 1: y = x a + b; to_fm = 0, the backward: x = y a, b == NULL).
+// Same tiling and the same fmaf per element, so group == 1 returns that kernel's bits: 32 x 32 x 2 tiles through LDS, both sides move
+// full 128 / 256-byte runs.  Dword LDS accesses bank by (address / 4) mod 32 within each 32-lane half.  [c][k][f] order: a half is one
+// k and 32 consecutive f, 32 banks.  [f][k][c] order: a half is one f, 16 consecutive k and both c; the row pitch of 33 words puts the
+// 16 k on 16 consecutive banks, and the plane pitch of 32 * 33 + 16 words puts c = 1 on the other 16.
+__global__ __launch_bounds__(256) void fm_cm_affine_g_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                             const float* __restrict__ ca, const float* __restrict__ cb, int group, int bins,
+                                                             int F, int to_fm) {
+  __shared__ float tile[2][32 * 33 + 16];
+  const int n = blockIdx.z, k0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
+  const int q = n / group;
+  const float a = ca[q], b = cb ? cb[q] : 0.f;
+  const int64_t cm_n = (int64_t)n * 2 * bins * F, fm_n = (int64_t)n * F * bins * 2;
+  if (to_fm) {
+    for (int i = threadIdx.x; i < 2048; i += 256) {
+      const int c = i >> 10, k = (i >> 5) & 31, f = i & 31;
+      tile[c][k * 33 + f] = (k0 + k < bins && f0 + f < F) ? fmaf(in[cm_n + ((int64_t)c * bins + k0 + k) * F + f0 + f], a, b) : 0.f;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2048; i += 256) {
+      const int f = i >> 6, k = (i >> 1) & 31, c = i & 1;
+      if (k0 + k < bins && f0 + f < F) out[fm_n + ((int64_t)(f0 + f) * bins + k0 + k) * 2 + c] = tile[c][k * 33 + f];
+    }
+  } else {
+    for (int i = threadIdx.x; i < 2048; i += 256) {
+      const int f = i >> 6, k = (i >> 1) & 31, c = i & 1;
+      tile[c][k * 33 + f] = (k0 + k < bins && f0 + f < F) ? fmaf(in[fm_n + ((int64_t)(f0 + f) * bins + k0 + k) * 2 + c], a, b) : 0.f;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2048; i += 256) {
+      const int c = i >> 10, k = (i >> 5) & 31, f = i & 31;
+      if (k0 + k < bins && f0 + f < F) out[cm_n + ((int64_t)c * bins + k0 + k) * F + f0 + f] = tile[c][k * 33 + f];
+    }
+  }
+}
+extern "C" int rfx_fm_cm_affine_g(const float* in, float* out, const float* coef_a, const float* coef_b, int32_t N, int32_t group,
+                                  int32_t bins, int32_t F, int32_t to_fm, void* stream) {
+  if (!in || !out || !coef_a || N <= 0 || N > 65535 || group <= 0 || N % group || bins <= 0 || F <= 0) return -1;
+  if (((int64_t)F + 31) / 32 > 65535) return -1;
+  hipLaunchKernelGGL(fm_cm_affine_g_kernel, dim3((bins + 31) / 32, (F + 31) / 32, N), dim3(256), 0, (hipStream_t)stream, in, out, coef_a,
+                     coef_b, group, bins, F, to_fm);
+  RFX_CHECK_LAUNCH();
+  return 0;
+}
+
 // Inverted dropout, out[i] = keep(i) ? x[i] / (1 - p) : 0, with a COUNTER-BASED mask: keep(i) = u(seed, i) >= p where u is
 // the top 24 bits of splitmix64(seed + i).  No mask tensor: the backward pass is the same launch on the gradient with the
 // same seed.  (nn.LSTM inter-layer dropout of Open-Unmix, F.dropout in Cnn14 with train=True: classifier.py:211-284 /

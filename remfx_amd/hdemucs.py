@@ -11,6 +11,14 @@ arithmetic goes through remfx_amd.ops / stft / nnops (HIP kernels behind the C A
 Data layout in HBM: spectrogram branch (B, C, Fr, T) with T (256 frames) contiguous,
 time branch (B, C, L) with L contiguous -- the gather-GEMM kernels take the position
 axis from the contiguous dimension, so both branches are read coalesced.
+
+Sources: RemFX trains one source ("mixture" in, the clean signal out) and every fused or frame-major path above is
+conditioned on that.  With S >= 2 sources (the separation configuration the upstream class is known for, e.g. 4 sources,
+stereo) the U-Net is the same up to its last two transposed convolutions, which then give S * audio_channels (* 2 for
+re / im) channels in (source, channel, re / im) order through the generic kernels; the tail de-standardises all
+S * audio_channels rows of a clip with the clip's one (std, mean) pair while changing to the frame-major spectrum the
+inverse STFT reads (rfx_fm_cm_affine_g), and adds the time branch in one pass (rfx_row_affine_add).  forward returns
+(B, S, audio_channels, T); HDemucs.separate runs files of any length through overlapping clips (segment.py).
 """
 import math
 import os
@@ -20,6 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import clchain, cldconv, lstm, nnops, ops, stft
+from . import segment as _segment
 
 # bf16 mode: the norm-free frequency layers run on the channels-last bf16 trunk (remfx_amd/clchain.py); RFX_CL_TRUNK=0 keeps the
 # channel-major kernels of rounds 1-4 for same-box A/B runs
@@ -503,6 +512,25 @@ class HDemucs(nn.Module):
         seen = {id(p) for p in out}
         return out + [p for p in self.parameters() if id(p) not in seen]
 
+    def separate(self, mix, segment=None, overlap=0.25, batch=64):
+        """Inference on a mixture (B, audio_channels, T) of any length -> (B, len(sources), audio_channels, T), in eval mode without
+        gradients.  `segment` (samples) cuts a longer file into overlapping clips whose channels stay together, runs at most `batch`
+        of them per forward and cross-fades the results (segment.apply(group_channels=True)); None, or a file no longer than one
+        segment, is one forward.  `overlap`: a fraction of the segment or a sample count."""
+        if mix.ndim != 3 or mix.shape[1] != self.audio_channels:
+            raise ValueError(f"expected (batch, {self.audio_channels}, frames), got {tuple(mix.shape)}")
+        B, Cin, T = mix.shape
+        training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                if segment is None or T <= segment:
+                    return self(mix)
+                out = _segment.apply(self, mix, segment=int(segment), overlap=overlap, batch=batch, group_channels=True)
+                return out.view(B, len(self.sources), Cin, T)
+        finally:
+            self.train(training)
+
     def _cl_layers(self, le, device):
         """How many leading frequency layers take the channels-last bf16 trunk (0: none).  Conditions: bf16 arithmetic mode, whole
         256-frame tiles, norm-free layers of the standard geometry (conv (8, 1) / 4 pad 2, 1x1 encoder rewrite, 3x3 decoder rewrite),
@@ -735,7 +763,14 @@ class HDemucs(nn.Module):
                 torch.cuda.synchronize()
         S = len(self.sources)
         if S != 1:
-            raise NotImplementedError("multi-source de-standardisation")
+            # Several sources: the last transposed convolutions are the generic ones (out_channels > 2) and leave x as
+            # (B, S * Cin * 2, Fq, le) in (source, channel, re / im) order, xt as (B, S * Cin, length).  The G = S * Cin rows of a clip
+            # share the clip's (std, mean): de-standardisation fused with the layout change to the frame-major spectrum _ispec stores
+            # whole lines from, then the time branch's de-standardisation and the add of the two branches in one pass.
+            G = S * Cin
+            spec = nnops.cm_to_fm_affine(x.reshape(B * G, 2, Fq, le), std, mean, group=G)           # (B * S * Cin, le, Fq, 2)
+            xo = stft.istft(spec, self.nfft, hl, mode="complex_fm", normalized=True, frames=le + 4, frame0=2, crop=pad, length=length)
+            return nnops.row_affine_add(xt.reshape(B * G, length), stdt, meant, xo, group=G).view(B, S, Cin, length)
         if fm and x.shape == (B, 2, Fq, le):
             # de-standardisation + _mask's layout change in one pass, then _ispec on the frame-major spectrum
             spec = nnops.cm_to_fm_affine(x, std, mean)                 # (B, le, Fq, 2)

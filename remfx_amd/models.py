@@ -104,8 +104,11 @@ class RemFX(_Base):
             # The Input_* metrics depend on the batch only: on the GPU they are enqueued on their own stream BEFORE the network, so
             # their analyses (three MRSTFT resolutions + the SI-SDR sums, ~1.4 ms at 64 clips, HBM-class) run beside the forward pass
             # instead of after it.  Values and logging order are unchanged.
+            # A multi-source network (Hybrid Demucs with several sources) takes a mixture (B, C, T) against targets (B, S, C, T): the input
+            # is no estimate of any one target, so the Input_* metrics exist only where the two shapes agree.
+            log_input = x.shape == y.shape
             early = None
-            if METRIC_STREAM and x.is_cuda and len(self.metrics):
+            if log_input and METRIC_STREAM and x.is_cuda and len(self.metrics):
                 main_s, met_s = torch.cuda.current_stream(), _metric_stream(x.device)
                 met_s.wait_stream(main_s)
                 with torch.cuda.stream(met_s), torch.no_grad():
@@ -124,8 +127,9 @@ class RemFX(_Base):
                     negate = -1 if metric == "SISDR" else 1    # SISDR loss is -SI-SDR
                     self.log(f"{mode}_{metric}", negate * self.metrics[metric](output.detach(), target),
                              on_step=False, on_epoch=True, logger=True, prog_bar=True, sync_dist=True)
-                    self.log(f"Input_{metric}", early[metric] if early is not None else negate * self.metrics[metric](x, y),
-                             on_step=False, on_epoch=True, logger=True, prog_bar=True, sync_dist=True)
+                    if log_input:
+                        self.log(f"Input_{metric}", early[metric] if early is not None else negate * self.metrics[metric](x, y),
+                                 on_step=False, on_epoch=True, logger=True, prog_bar=True, sync_dist=True)
         return loss
 
 
@@ -211,6 +215,8 @@ class DemucsModel(_RemovalWrapper):
         self._set_perceptual(perceptual_kwargs, sum_diff_kwargs, sample_rate, self.num_bins, mrstft_kwargs, self.model.audio_channels)
 
     def forward(self, batch):
+        """x (B, C, T) and target (B, C, T) for one source; with S >= 2 sources target and output are (B, S, C, T) and the loss runs over
+        all B * S * C rows (the squeeze leaves them alone)."""
         x, target = batch
         output = self.model(x).squeeze(1)
         return self._loss(output, target), output

@@ -486,13 +486,82 @@ class _CmToFmAffineFn(torch.autograd.Function):
         return gx, None, None
 
 
-def cm_to_fm_affine(x, a, b):
-    return _CmToFmAffineFn.apply(x, a.contiguous(), b.contiguous())
+class _CmToFmAffineGroupFn(torch.autograd.Function):
+    """_CmToFmAffineFn with one (a, b) pair per `group` consecutive rows (rfx_fm_cm_affine_g): the S * Cin rows of a multi-source
+    HDemucs clip share the clip's statistics."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, group):
+        ops._req(x, "x")
+        x = x.contiguous()
+        N, Cc, bins, F = x.shape
+        if Cc != 2 or x.dtype != torch.float32 or N % group or a.numel() != N // group or b.numel() != N // group:
+            raise ValueError(f"cm_to_fm_affine: (N, 2, bins, frames) fp32 with N / group = {N} / {group} coefficient pairs")
+        y = torch.empty((N, F, bins, 2), device=x.device, dtype=torch.float32)
+        check(_lib.lib().rfx_fm_cm_affine_g(_ptr(x), _ptr(y), _ptr(a), _ptr(b), N, group, bins, F, 1, _stream()), "rfx_fm_cm_affine_g")
+        ctx.save_for_backward(a)
+        ctx.group = group
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (a,) = ctx.saved_tensors
+        g = g.contiguous()
+        N, F, bins, _ = g.shape
+        gx = torch.empty((N, 2, bins, F), device=g.device, dtype=torch.float32)
+        check(_lib.lib().rfx_fm_cm_affine_g(_ptr(g), _ptr(gx), _ptr(a), None, N, ctx.group, bins, F, 0, _stream()), "rfx_fm_cm_affine_g")
+        return gx, None, None, None
+
+
+def cm_to_fm_affine(x, a, b, group=1):
+    """(N, 2, bins, frames) -> (N, frames, bins, 2) times a plus b; `group` consecutive rows share one coefficient pair."""
+    if group == 1:
+        return _CmToFmAffineFn.apply(x, a.contiguous(), b.contiguous())
+    return _CmToFmAffineGroupFn.apply(x, a.contiguous(), b.contiguous(), int(group))
 
 
 def row_affine(x, a, b):
     """x * a[r] + b[r] per leading-dim row (de-standardisation); gradient flows to x only."""
     return _RowAffineFn.apply(x, a.contiguous(), b.contiguous())
+
+
+class _RowAffineAddFn(torch.autograd.Function):
+    """out[r] = x[r] * a[r / group] + b[r / group] + y[r] over rows of equal length (rfx_row_affine_add).  The gradient passes to y
+    unchanged and to x through rfx_row_affine with a; a and b are detached statistics."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, y, group):
+        ops._req(x, "x")
+        ops._req(y, "y")
+        x, y = x.contiguous(), y.contiguous()
+        Q = a.numel()
+        R = Q * group
+        if x.numel() != y.numel() or x.numel() % R or b.numel() != Q:
+            raise ValueError(f"row_affine_add: x {tuple(x.shape)}, y {tuple(y.shape)} against {Q} coefficient pairs for groups of {group} rows")
+        out = torch.empty_like(y)
+        check(_lib.lib().rfx_row_affine_add(_ptr(x), _ptr(a), _ptr(b), _ptr(y), _ptr(out), R, group, x.numel() // R, _stream()),
+              "rfx_row_affine_add")
+        ctx.save_for_backward(a)
+        ctx.xshape = x.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (a,) = ctx.saved_tensors
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gc = g.contiguous()
+            Q = a.numel()
+            gx = torch.empty(ctx.xshape, device=g.device, dtype=torch.float32)
+            # the rows of a group are contiguous: one row of group * L samples per coefficient
+            check(_lib.lib().rfx_row_affine(_ptr(gc), _ptr(a), None, _ptr(gx), Q, gc.numel() // Q, _stream()), "rfx_row_affine")
+        return gx, None, None, g, None
+
+
+def row_affine_add(x, a, b, y, group=1):
+    """x * a[r / group] + b[r / group] + y over a.numel() * group rows (every trailing dim flattened); the result takes y's shape.
+    Gradients flow to x and y."""
+    return _RowAffineAddFn.apply(x, a.contiguous(), b.contiguous(), y, int(group))
 
 
 class _LocalStateFn(torch.autograd.Function):

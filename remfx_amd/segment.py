@@ -1,5 +1,7 @@
 """Segmented long-file inference: cut a file into overlapping training-length clips on the device, run a network on batches
-of clips, cross-fade the results back into one signal (csrc/segment.hip).
+of clips, cross-fade the results back into one signal (csrc/segment.hip).  split / merge make every channel a
+mono clip of its own; split_c / merge_c keep a clip's channels together for networks that take (clips, C, L) and return
+(clips, Co, L') -- multi-source Hybrid Demucs (HDemucs.separate).
 
 The reference's single-file path (scripts/remfx_detect.py:44-55) hands the whole file to the chain as one clip of arbitrary
 length; the demucs family cuts it instead (`apply_model(split=True, overlap=...)`).  Here:
@@ -102,6 +104,33 @@ def merge(y, plan, channels=1, out=None):
     return out
 
 
+def split_c(x, plan):
+    """(B, C, T) -> (B * S, C, L): the channels of a clip stay together, clip i of signal b at index b * S + i."""
+    ops._req(x, "segment.split_c")
+    if x.dim() != 3 or x.shape[-1] != plan.T:
+        raise ValueError(f"segment.split_c: expected (B, C, {plan.T}), got {tuple(x.shape)}")
+    x = x.contiguous()
+    B, Cn = x.shape[0], x.shape[1]
+    out = torch.empty(B * plan.n_segments, Cn, plan.segment, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().rfx_segment_split_c(ops._ptr(x), ops._ptr(out), B, Cn, plan.T, plan.segment, plan.hop, plan.n_segments,
+                                              ops._stream()), "rfx_segment_split_c")
+    return out
+
+
+def merge_c(y, plan):
+    """(B * S, Co, L') -> (B, Co, T - lead - trail), the inverse layout of split_c(); Co is whatever the network returned."""
+    ops._req(y, "segment.merge_c")
+    S = plan.n_segments
+    if y.dim() != 3 or y.shape[-1] != plan.clip_len or y.shape[0] % S or y.numel() == 0:
+        raise ValueError(f"segment.merge_c: expected (B * {S}, Co, {plan.clip_len}) clips, got {tuple(y.shape)}")
+    y = y.contiguous()
+    B, Co = y.shape[0] // S, y.shape[1]
+    out = torch.empty(B, Co, plan.out_len, device=y.device, dtype=torch.float32)
+    _lib.check(_lib.lib().rfx_segment_merge_c(ops._ptr(y), ops._ptr(out), B, Co, plan.T, plan.segment, plan.hop, plan.lead,
+                                              plan.trail, S, ops._stream()), "rfx_segment_merge_c")
+    return out
+
+
 def _crop(segment, clip_len, align):
     drop = segment - clip_len
     if drop < 0:
@@ -118,13 +147,30 @@ def _crop(segment, clip_len, align):
     raise ValueError(f"segment.apply: align must be 'same', 'end' or 'center' (got {align!r})")
 
 
-def apply(fn, x, segment=262144, overlap=0.25, batch=64, align="same"):
+def apply(fn, x, segment=262144, overlap=0.25, batch=64, align="same", group_channels=False):
     """fn on a long (B, C, T) signal through clips of `segment` samples: split, fn on sub-batches of at most `batch` clips (each
     (n, 1, segment) -> (n, 1, L')), cross-fade merge.  L' is read off the first result; `align` says where those samples sit in
-    the clip: "same" (L' = segment), "end" (a causal network: the last L'), "center"."""
+    the clip: "same" (L' = segment), "end" (a causal network: the last L'), "center".
+
+    group_channels=True keeps the channels of a clip together for a network that mixes them: fn sees (n, C, segment) and returns
+    (n, Co, L') or (n, S, Cc, L') (flattened to Co = S * Cc); the result is (B, Co, T - lead - trail)."""
     ops._req(x, "segment.apply")
     B, Cn, T = x.shape
     ov = overlap_samples(segment, overlap)
+    if group_channels:
+        clips = split_c(x, SegmentPlan(T, segment, ov))
+        n = clips.shape[0]
+        res, plan = None, None
+        for k in range(0, n, max(1, int(batch))):
+            y = fn(clips[k:k + batch])
+            if res is None:
+                if y.dim() not in (3, 4):
+                    raise ValueError(f"segment.apply: with group_channels the network returns (n, Co, L') or (n, S, Cc, L'), got {tuple(y.shape)}")
+                lead, trail = _crop(segment, y.shape[-1], align)
+                plan = SegmentPlan(T, segment, ov, lead, trail)
+                res = torch.empty(n, y.numel() // (y.shape[0] * plan.clip_len), plan.clip_len, device=x.device, dtype=torch.float32)
+            res[k:k + batch].copy_(y.reshape(-1, res.shape[1], plan.clip_len))
+        return merge_c(res, plan)
     clips = split(x, SegmentPlan(T, segment, ov))
     n = clips.shape[0]
     res, plan = None, None
