@@ -492,6 +492,15 @@ int rfx_dconv_layer_bwd(const float* x, const float* g, float* gx, int32_t N, in
 
 /* Label of the kernel instantiation rfx_gemm_fwd would launch (measurement only; see csrc/gemm.hip). */
 int rfx_gemm_fwd_variant(const rfx_gemm_desc* d, const rfx_epilogue* epi, int32_t two_phase, int32_t prec);
+/* The same for rfx_gemm_wgrad(d, .., ws_floats, .., prec): which instantiation it launches and how it cuts the positions.
+ * Returns splits | xcd_grouped << 13 | g16 << 14 | shape << 16 | family << 20:
+ *   family 0 gemm_thin_wgrad_kernel<shape> (shape = 1 / 2 / 4 / 8), 1 gemm_wgrad_kernel<TM, TK> (exact fp32, shape = (TM-1)*2 + (TK-1)),
+ *          2 gemm_wgrad_bf_kernel (shape 0 = 96 x 128 tile, 1 = 32 x 256, 2 = 32 x 128, 3 = 128 x 128, 4 = 128 x 64, 5 = 64 x 128, 6 = 64 x 64),
+ *          3 gemm_wgrad_wide_kernel (shape 0 = 96 x 128, 1 = 32 x 256, 2 = 32 x 128, 3 = 128 x 128, 4 = 64 x 128, 5 = 96 x 256);
+ *   g16: the gradient operand is read as stored bf16; xcd_grouped: the 1-D XCD-grouped block order; splits: the value rfx_gemm_wgrad
+ *   writes to *splits_out.  -1 where rfx_gemm_wgrad refuses the arguments, 0 for K == 0 (nothing launched).  Both functions run
+ *   the same selection code.  Pure function of its arguments. */
+int rfx_gemm_wgrad_variant(const rfx_gemm_desc* d, int64_t ws_floats, int32_t prec);
 
 /* Plain multi-head scaled-dot-product attention, out[c, s] = sum_t softmax_t(<k[:, t], q[:, s]> / sqrt(ch)) v[c, t], on the streaming
  * any-T kernels above; q, k, v: (B, heads * ch, T) channel-major.  The nn.MultiheadAttention core of asteroid's DPTNet

@@ -135,6 +135,7 @@ SIGNATURES = {
     "rfx_gemm_fwd": [C.POINTER(GemmDesc), _P, _P, _P, _P, C.POINTER(Epilogue), _P, _P, _I32, _I32, _P, _I32, _P],
     "rfx_gemm_fwd_variant": [C.POINTER(GemmDesc), C.POINTER(Epilogue), _I32, _I32],
     "rfx_gemm_wgrad": [C.POINTER(GemmDesc), _P, _P, _P, _P, _I64, C.POINTER(C.c_int32), _I32, _P],
+    "rfx_gemm_wgrad_variant": [C.POINTER(GemmDesc), _I64, _I32],
     "rfx_fft_analysis": [C.POINTER(StftDesc), _P, _P, _P, _P, _P],
     "rfx_fft_synthesis_ws": [C.POINTER(StftDesc)],
     "rfx_fft_synthesis": [C.POINTER(StftDesc), _P, _P, _P, _P, _P, _P],

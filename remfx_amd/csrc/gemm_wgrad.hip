@@ -246,34 +246,37 @@ extern "C" int rfx_unpack_col(const float* dapack, int32_t M, int32_t Kpad, int3
 // R (channel tiles per wave) is a pure function of M so that host-side packing
 // and the kernel agree on Mpad = ceil(M / 32R) * 32R.
 
-extern "C" int rfx_gemm_wgrad(const rfx_gemm_desc* d, const rfx_ktab_entry* ktab, const float* in,
-                              const float* gout, float* dapack, int64_t ws_floats, int32_t* splits_out, int32_t prec, void* stream) {
-  if (!desc_ok(d) || !ktab || !in || !gout || !dapack || !splits_out) return -1;
-  *splits_out = 1;
-  if (d->K == 0) return 0;
+// What rfx_gemm_wgrad launches for (descriptor, workspace, arithmetic): the ONE place the selection lives -- the launcher and
+// rfx_gemm_wgrad_variant both call it, so what the latter reports is what the former runs.
+struct WgradPick {
+  int family;            // 0 gemm_thin_wgrad_kernel, 1 gemm_wgrad_kernel (exact fp32), 2 gemm_wgrad_bf_kernel, 3 gemm_wgrad_wide_kernel
+  int shape;             // thin: MM (1 / 2 / 4 / 8); exact: (TM - 1) * 2 + (TK - 1); bf / wide: the launchers' shape index (gemm_wgrad.h)
+  int splits, xcd_grouped;
+  int tiles_per_sample, total_tiles, tiles_per_block, kt, mt;
+  uint32_t in_bytes, g_bytes;
+  int64_t slice;
+};
+
+// 0, or -1 where rfx_gemm_wgrad refuses the plan.  d->K == 0 (nothing to launch) is the caller's case.
+static int wgrad_pick(const rfx_gemm_desc* d, int64_t ws_floats, int prec, WgradPick& k) {
+  k = WgradPick{};
+  k.splits = 1;
   const int64_t slice = (int64_t)d->M * d->Kpad;
+  k.slice = slice;
   const int max_splits = (int)(ws_floats / slice < 1 ? 0 : (ws_floats / slice > 4096 ? 4096 : ws_floats / slice));
   if (max_splits < 1) return -1;
   if (d->in_bf16) return -1;                          // bf16 storage is implemented for the gradient operand only (wide kernel)
   if (d->out_bf16 && (prec != 2 || d->M <= 8 || ((d->out_b0 | d->out_cs | d->out_as | d->out_ns) & 1))) return -1;
-  WgradArgs w;
-  w.d = *d; w.ktab = ktab; w.in = in; w.g = gout; w.dapack = dapack; w.split_stride = slice;
   const int P = d->OA * d->OB;
-  w.tiles_per_sample = (P + 31) / 32;
-  w.total_tiles = d->N * w.tiles_per_sample;
-  hipStream_t s = (hipStream_t)stream;
+  k.tiles_per_sample = (P + 31) / 32;
+  k.total_tiles = d->N * k.tiles_per_sample;
   if (d->M <= 8) {
     const int64_t total = (int64_t)d->N * P;
     int splits = (int)(total / 4096 < 1 ? 1 : (total / 4096 > 64 ? 64 : total / 4096));
-    splits = min(splits, max_splits);
-    *splits_out = splits;
-    dim3 grid((d->K + 3) / 4, splits);
-    w.tiles_per_block = 0;
-    if (d->M <= 1) hipLaunchKernelGGL(gemm_thin_wgrad_kernel<1>, grid, dim3(256), 0, s, w);
-    else if (d->M <= 2) hipLaunchKernelGGL(gemm_thin_wgrad_kernel<2>, grid, dim3(256), 0, s, w);
-    else if (d->M <= 4) hipLaunchKernelGGL(gemm_thin_wgrad_kernel<4>, grid, dim3(256), 0, s, w);
-    else hipLaunchKernelGGL(gemm_thin_wgrad_kernel<8>, grid, dim3(256), 0, s, w);
-    RFX_CHECK_LAUNCH();
+    k.splits = min(splits, max_splits);
+    k.family = 0;
+    k.shape = d->M <= 1 ? 1 : d->M <= 2 ? 2 : d->M <= 4 ? 4 : 8;
+    k.tiles_per_block = 0;
     return 0;
   }
   // wide-load kernel (gemm_wgrad.h): both operands contiguous and unit-stride along b, quads never straddle an output row
@@ -282,7 +285,7 @@ extern "C" int rfx_gemm_wgrad(const rfx_gemm_desc* d, const rfx_ktab_entry* ktab
   if (prec != 0 && d->SB == 1 && d->in_bs == 1 && d->out_bs == 1 && d->out_sb == 1 &&
       (d->OA == 1 || d->OB % 4 == 0) && d->in_extent > 0 && d->in_extent <= 0x7fffffffLL && g_span <= 0x7fffffffLL &&
       d->out_cs >= 0 && d->out_as >= 0) {
-    w.in_bytes = (uint32_t)d->in_extent; w.g_bytes = (uint32_t)g_span;
+    k.in_bytes = (uint32_t)d->in_extent; k.g_bytes = (uint32_t)g_span;
     const bool r96 = d->M > 64 && ((d->M + 95) / 96) * 96 < ((d->M + 127) / 128) * 128;
     // 96 x 256 tiles (bf16 mode: the hi + lo images of the split mode would need 101 KB of LDS) when K has >= 2 of them:
     // twice the MFMA work per staged element and half the re-reads of g
@@ -294,16 +297,15 @@ extern "C" int rfx_gemm_wgrad(const rfx_gemm_desc* d, const rfx_ktab_entry* ktab
     int splits = max(1, 2048 / (mt * kt));
     const int min_chunks = (int64_t)mt * kt * (chunks / 32) >= 512 ? 32 : 8;
     splits = min(min(splits, max_splits), max(1, chunks / min_chunks));
-    w.total_tiles = chunks;
-    w.tiles_per_block = (chunks + splits - 1) / splits;
-    splits = (chunks + w.tiles_per_block - 1) / w.tiles_per_block;
-    w.kt = kt; w.mt = mt; w.splits = splits;
-    *splits_out = splits;
+    k.total_tiles = chunks;
+    k.tiles_per_block = (chunks + splits - 1) / splits;
+    splits = (chunks + k.tiles_per_block - 1) / k.tiles_per_block;
+    k.kt = kt; k.mt = mt; k.splits = splits;
     // every (k, m) tile of a position split re-reads the same g rows / input rows: group them behind one L2
     // (measured on the Demucs B=64 step, bf16: 44.3 -> 40.2 ms of weight-gradient launches)
-    w.xcd_grouped = splits >= 8;
-    dim3 grid = w.xcd_grouped ? dim3(((splits + 7) / 8) * 8 * kt * mt, 1, 1) : dim3(kt, mt, splits);
-    return prec == 1 ? rfx_launch_wgrad_wide_bf3(w, shape, grid, s) : rfx_launch_wgrad_wide_bf16(w, shape, grid, s);
+    k.xcd_grouped = splits >= 8;
+    k.family = 3; k.shape = shape;
+    return 0;
   }
   // strided plans (the time branch's encoder convs): the 32-position kernel takes a bf16 gradient operand with two-byte loads.
   // num_records of its sample descriptors is 2^31 - 1 bytes: the operand's span past a sample base must stay below that
@@ -319,25 +321,78 @@ extern "C" int rfx_gemm_wgrad(const rfx_gemm_desc* d, const rfx_ktab_entry* ktab
   int splits = max(1, 2048 / (mt * kt));
   // >= 64 position tiles per workgroup when there is plenty of work; short sequences (LSTM / attention projections,
   // P ~ 8-38 k positions) would otherwise launch a few dozen workgroups on 256 CUs: go down to 16 tiles there
-  const int min_tiles = (int64_t)mt * kt * (w.total_tiles / 64) >= 512 ? 64 : 16;
-  splits = min(min(splits, max_splits), max(1, w.total_tiles / min_tiles));
-  w.tiles_per_block = (w.total_tiles + splits - 1) / splits;
-  splits = (w.total_tiles + w.tiles_per_block - 1) / w.tiles_per_block;
-  w.kt = kt; w.mt = mt; w.splits = splits;
-  *splits_out = splits;
-  dim3 grid(kt, mt, splits);
-  w.xcd_grouped = 0;
+  const int min_tiles = (int64_t)mt * kt * (k.total_tiles / 64) >= 512 ? 64 : 16;
+  splits = min(min(splits, max_splits), max(1, k.total_tiles / min_tiles));
+  k.tiles_per_block = (k.total_tiles + splits - 1) / splits;
+  splits = (k.total_tiles + k.tiles_per_block - 1) / k.tiles_per_block;
+  k.kt = kt; k.mt = mt; k.splits = splits;
+  k.xcd_grouped = 0;
   if (prec != 0) {
     // (XCD-grouped block order measured slower for this staging: Demucs B=64 408.0 ms off, 411.8 ms on -- not used here)
-    const int shape = rows96 ? 0 : (narrow && tk == 2) ? 1 : narrow ? 2 : (tm == 2 && tk == 2) ? 3 : tm == 2 ? 4 : tk == 2 ? 5 : 6;
-    return prec == 1 ? rfx_launch_wgrad_bf3(w, shape, grid, s) : rfx_launch_wgrad_bf16(w, shape, grid, s);
+    k.family = 2;
+    k.shape = rows96 ? 0 : (narrow && tk == 2) ? 1 : narrow ? 2 : (tm == 2 && tk == 2) ? 3 : tm == 2 ? 4 : tk == 2 ? 5 : 6;
+    return 0;
   }
-  if (tm == 2 && tk == 2) hipLaunchKernelGGL((gemm_wgrad_kernel<2, 2>), grid, dim3(256), 0, s, w);
-  else if (tm == 2) hipLaunchKernelGGL((gemm_wgrad_kernel<2, 1>), grid, dim3(256), 0, s, w);
-  else if (tk == 2) hipLaunchKernelGGL((gemm_wgrad_kernel<1, 2>), grid, dim3(256), 0, s, w);
+  k.family = 1;
+  k.shape = (tm - 1) * 2 + (tk - 1);
+  return 0;
+}
+
+extern "C" int rfx_gemm_wgrad(const rfx_gemm_desc* d, const rfx_ktab_entry* ktab, const float* in,
+                              const float* gout, float* dapack, int64_t ws_floats, int32_t* splits_out, int32_t prec, void* stream) {
+  if (!desc_ok(d) || !ktab || !in || !gout || !dapack || !splits_out) return -1;
+  *splits_out = 1;
+  if (d->K == 0) return 0;
+  WgradPick k;
+  if (wgrad_pick(d, ws_floats, prec, k) != 0) return -1;
+  WgradArgs w;
+  w.d = *d; w.ktab = ktab; w.in = in; w.g = gout; w.dapack = dapack; w.split_stride = k.slice;
+  w.tiles_per_sample = k.tiles_per_sample;
+  w.total_tiles = k.total_tiles;
+  w.tiles_per_block = k.tiles_per_block;
+  w.kt = k.kt; w.mt = k.mt; w.splits = k.splits;
+  w.xcd_grouped = k.xcd_grouped;
+  w.in_bytes = k.in_bytes; w.g_bytes = k.g_bytes;
+  *splits_out = k.splits;
+  hipStream_t s = (hipStream_t)stream;
+  if (k.family == 0) {
+    dim3 grid((d->K + 3) / 4, k.splits);
+    if (k.shape == 1) hipLaunchKernelGGL(gemm_thin_wgrad_kernel<1>, grid, dim3(256), 0, s, w);
+    else if (k.shape == 2) hipLaunchKernelGGL(gemm_thin_wgrad_kernel<2>, grid, dim3(256), 0, s, w);
+    else if (k.shape == 4) hipLaunchKernelGGL(gemm_thin_wgrad_kernel<4>, grid, dim3(256), 0, s, w);
+    else hipLaunchKernelGGL(gemm_thin_wgrad_kernel<8>, grid, dim3(256), 0, s, w);
+    RFX_CHECK_LAUNCH();
+    return 0;
+  }
+  if (k.family == 3) {
+    dim3 grid = k.xcd_grouped ? dim3(((k.splits + 7) / 8) * 8 * k.kt * k.mt, 1, 1) : dim3(k.kt, k.mt, k.splits);
+    return prec == 1 ? rfx_launch_wgrad_wide_bf3(w, k.shape, grid, s) : rfx_launch_wgrad_wide_bf16(w, k.shape, grid, s);
+  }
+  dim3 grid(k.kt, k.mt, k.splits);
+  if (k.family == 2) return prec == 1 ? rfx_launch_wgrad_bf3(w, k.shape, grid, s) : rfx_launch_wgrad_bf16(w, k.shape, grid, s);
+  if (k.shape == 3) hipLaunchKernelGGL((gemm_wgrad_kernel<2, 2>), grid, dim3(256), 0, s, w);
+  else if (k.shape == 2) hipLaunchKernelGGL((gemm_wgrad_kernel<2, 1>), grid, dim3(256), 0, s, w);
+  else if (k.shape == 1) hipLaunchKernelGGL((gemm_wgrad_kernel<1, 2>), grid, dim3(256), 0, s, w);
   else hipLaunchKernelGGL((gemm_wgrad_kernel<1, 1>), grid, dim3(256), 0, s, w);
   RFX_CHECK_LAUNCH();
   return 0;
 }
 
-
+// Which kernel instantiation rfx_gemm_wgrad launches for (desc, ws_floats, prec), and how it cuts the positions: tests assert it
+// before they judge a result.  splits | xcd_grouped << 13 | g16 << 14 | shape << 16 | family << 20, where
+//   family 0 gemm_thin_wgrad_kernel<shape>             (shape = 1 / 2 / 4 / 8)
+//          1 gemm_wgrad_kernel<TM, TK>                 (exact fp32; shape = (TM - 1) * 2 + (TK - 1))
+//          2 gemm_wgrad_bf_kernel<.., MODE = prec>     (shape 0 .. 6: the table above rfx_launch_wgrad_bf in gemm_wgrad.h)
+//          3 gemm_wgrad_wide_kernel<.., MODE = prec>   (shape 0 .. 5: the table above rfx_launch_wgrad_wide)
+//   g16: the gradient operand is read as stored bf16 (the G16 instantiations); xcd_grouped: the 1-D XCD-grouped block order;
+//   splits: position splits = partial matrices left in the workspace (1 .. 4096).
+// -1: rfx_gemm_wgrad refuses these arguments; 0: K == 0, nothing is launched.  Pure function of its arguments.
+extern "C" int rfx_gemm_wgrad_variant(const rfx_gemm_desc* d, int64_t ws_floats, int32_t prec) {
+  if (!desc_ok(d) || prec < 0 || prec > 2) return -1;
+  if (d->K == 0) return 0;
+  WgradPick k;
+  if (wgrad_pick(d, ws_floats, prec, k) != 0) return -1;
+  // the bf / wide launchers take a stored-bf16 gradient in the bf16 mode only (wgrad_pick has refused the rest)
+  const int g16 = d->out_bf16 ? 1 : 0;
+  return k.splits | (k.xcd_grouped << 13) | (g16 << 14) | (k.shape << 16) | (k.family << 20);
+}

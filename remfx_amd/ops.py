@@ -201,6 +201,7 @@ def enter_compute_stream(device):
 
 SINK = None                   # the armed GradSink (optim.FlatParams.zero_grad arms, .join disarms)
 TRACE_VARIANT = None          # bench.py sets this to a list: gemm_fwd appends rfx_gemm_fwd_variant() of every launch
+TRACE_WGRAD = None            # tests set this to a list: gemm_wgrad appends rfx_gemm_wgrad_variant() of every launch it made
 
 
 ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "tanh": 3, "prelu": 4, "leaky": 5, "sigmoid": 6}
@@ -478,12 +479,18 @@ def gemm_wgrad(dp, x, g):
         rc = _lib.lib().rfx_gemm_wgrad(C.byref(dp.desc_for(x, g)), _ptr(dp.ktab), _ptr(x), _ptr(g), _ptr(ws), cap, C.byref(ns),
                                        GEMM_PREC, _stream())
         if rc == 0:
+            if TRACE_WGRAD is not None:
+                TRACE_WGRAD.append(_lib.lib().rfx_gemm_wgrad_variant(C.byref(dp.desc_for(x, g)), cap, GEMM_PREC))
             return WgradOut(ws, ns.value)
         if rc != -1:                                         # -1 = "plan not supported by the 16-bit path"; anything else is a real failure
             check(rc, "rfx_gemm_wgrad")
+        if TRACE_WGRAD is not None:
+            TRACE_WGRAD.append(-1)                           # refused: the retry below is the launch
         g = g.float()                                        # a plan the wide-load kernel does not take: widen once
     check(_lib.lib().rfx_gemm_wgrad(C.byref(dp.desc), _ptr(dp.ktab), _ptr(x), _ptr(g), _ptr(ws), cap, C.byref(ns),
                                     GEMM_PREC, _stream()), "rfx_gemm_wgrad")
+    if TRACE_WGRAD is not None:
+        TRACE_WGRAD.append(_lib.lib().rfx_gemm_wgrad_variant(C.byref(dp.desc), cap, GEMM_PREC))
     return WgradOut(ws, ns.value)
 
 
@@ -756,11 +763,13 @@ def conv1d_fork(x, w, bias=None, stride=1, padding=0, dilation=1, stat_sums=None
 
 
 # ---- transposed convolution -----------------------------------------------------------
-def convT2d_forward(x, w, bias, stride, dilation, crop_lo, out_len, act=None):
+def convT2d_forward(x, w, bias, stride, dilation, crop_lo, out_len, act=None, out=None):
+    """out: optional (N, Cout, out_len) fp32 buffer of the caller's to write into."""
     _req(x, "x"); _req(w, "weight")
     N, Cin, IA, IB = x.shape
     _, Cout, KA, KB = w.shape
-    out = torch.empty((N, Cout, out_len[0], out_len[1]), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((N, Cout, out_len[0], out_len[1]), device=x.device, dtype=torch.float32)
     ax = _merge_axis(w.shape[2:], stride, (0, 0), dilation)
     if (ax is not None and act is None and Cout * stride[ax] >= 4 and crop_lo[1 - ax] == 0
             and out_len[1 - ax] == x.shape[3 - ax]):
