@@ -796,6 +796,11 @@ typedef struct rfx_cl_conv_desc {
   int32_t cm_fold;        /* 0: merged row phases (output row oa*G + psi + g_off); 1: folded positions (position b * (M / Co) + psi) */
 } rfx_cl_conv_desc;
 int rfx_cl_conv(const rfx_cl_conv_desc* d, void* stream);
+/* Which cl_conv_kernel<MODE, RW, NT, WM, NTC, KS, DA, DB, HALO> rfx_cl_conv would launch for d: the launcher's own validation and
+ * selection code, nothing launched, no device needed (pointers are only compared with NULL).  Returns
+ *   MODE | RW << 3 | NT << 5 | WM << 7 | NTC << 9 | KS << 11 | DB << 13 | HALO << 16        (DA is 2 in every instantiation)
+ * or a negative value where rfx_cl_conv refuses d -- a halo form (NTC > 1 or db0 != 0) with |db0 + t * db_step| > 8 included. */
+int rfx_cl_conv_variant(const rfx_cl_conv_desc* d);
 /* dst[i] = bf16(idx[i] < 0 ? 0 : src[idx[i]]): weights -> packed MFMA fragments (idx built once per layer by the host planner) */
 int rfx_cl_pack(const float* src, const int32_t* idx, int64_t n, void* dst, void* stream);
 /* channel-major fp32 / bf16 (N, C, A, B) [strides in elements, B contiguous] <-> channels-last bf16; B % 64 == 0, C % 8 == 0.
@@ -848,6 +853,10 @@ typedef struct rfx_cl_wgrad_desc {
 } rfx_cl_wgrad_desc;
 int64_t rfx_cl_wgrad_ws_floats(const rfx_cl_wgrad_desc* d);
 int rfx_cl_wgrad(const rfx_cl_wgrad_desc* d, void* stream);
+/* Which cl_wgrad_kernel<RW, WK, PW> rfx_cl_wgrad would launch for d (ws must be non-NULL, it is not read): the launcher's own
+ * validation and selection code, nothing launched, no device needed.  Returns RW | WK << 2 | PW << 5 | xcd_grouped << 13
+ * (xcd_grouped: S >= 8, the XCD-grouped block order) or a negative value where rfx_cl_wgrad refuses d. */
+int rfx_cl_wgrad_variant(const rfx_cl_wgrad_desc* d);
 int rfx_cl_wgrad_reduce(const float* ws, const int32_t* map, int64_t nmap, int32_t S, int32_t DT, int32_t RW, int32_t WK, float* dw,
                         int64_t wn, float* db, int32_t accumulate, void* stream);
 

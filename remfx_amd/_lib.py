@@ -252,9 +252,11 @@ SIGNATURES = {
     "rfx_channel_sum_ws": [_P, _I32, _I32, _I32, _I32, _I64, _I64, _I64, _I64],
     "rfx_channel_sum": [_P, _I32, _I32, _I32, _I32, _I64, _I64, _I64, _I64, _P, _P, _P],
     "rfx_cl_conv": [C.POINTER(ClConvDesc), _P],
+    "rfx_cl_conv_variant": [C.POINTER(ClConvDesc)],
     "rfx_cl_pack": [_P, _P, _I64, _P, _P],
     "rfx_cl_wgrad_ws_floats": [_P],
     "rfx_cl_wgrad": [_P, _P],
+    "rfx_cl_wgrad_variant": [_P],
     "rfx_cl_wgrad_reduce": [_P, _P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _I32, _P],
     "rfx_cl_from_cm": [_P, _I32, _I64, _I64, _I64, _I32, _I32, _I32, _I32, C.POINTER(ClTensor), C.POINTER(ClTensor), C.POINTER(ClTensor),
                        _I32, _P],

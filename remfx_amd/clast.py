@@ -15,6 +15,8 @@ import torch
 from . import _lib, ops
 from ._lib import ClConvDesc, ClTensor, ClWgradDesc, check
 
+TRACE = None                  # tests set this to a list: conv / wgrad append ("conv" | "wgrad", variant code) of every launch they make
+
 EPI = {"store": 0, "gelu": 1, "glu": 2, "dgelu": 3, "dglu": 4, "store_cm": 5}
 
 
@@ -188,6 +190,8 @@ def conv(form, apack, x, N, IA, IB, OA, mode, bias=None, out0=None, out1=None, a
         if cm_out.dtype != torch.float32 or cm_out.stride(3) != 1:
             raise ValueError("store_cm: fp32 (N, C, rows, positions) with contiguous positions")
         d.cm_out, d.cm_ns, d.cm_cs, d.cm_as, d.cm_fold = cm_out.data_ptr(), cm_out.stride(0), cm_out.stride(1), cm_out.stride(2), int(cm_fold)
+    if TRACE is not None:
+        TRACE.append(("conv", _lib.lib().rfx_cl_conv_variant(C.byref(d))))
     check(_lib.lib().rfx_cl_conv(C.byref(d), _stream()), "rfx_cl_conv")
 
 
@@ -486,6 +490,8 @@ def wgrad(form, p, q, N, OA, IA, B, dw, db=None, accumulate=False, p_c0=0, q_c0=
         raise RuntimeError("rfx_cl_wgrad: geometry rejected")
     ws = torch.empty(nws, device=p.device, dtype=torch.float32)
     d.ws = ws.data_ptr()
+    if TRACE is not None:
+        TRACE.append(("wgrad", L.rfx_cl_wgrad_variant(C.byref(d))))
     check(L.rfx_cl_wgrad(C.byref(d), _stream()), "rfx_cl_wgrad")
     mp = _dev_map(form, p.device)
     check(L.rfx_cl_wgrad_reduce(C.c_void_p(ws.data_ptr()), C.c_void_p(mp.data_ptr()), mp.numel(), d.S, form.DT, form.RW, form.WK,

@@ -445,9 +445,11 @@ __global__ __launch_bounds__(512, 4) void cl_conv_kernel(const ClConvK g) {
   }
 }
 
+// query: nothing is launched, the return value names the instantiation (rfx_cl_conv_variant, include/remfx_hip.h)
 template <int MODE, int RW, int NT, int WM, int NTC, int KS, int DA, int DB, bool HALO>
-static int cl_conv_launch(const ClConvK& k, dim3 grid, hipStream_t s) {
+static int cl_conv_launch(const ClConvK& k, dim3 grid, hipStream_t s, bool query) {
   using Cfg = ClConvCfg<RW, NT, WM, NTC, KS, DA, DB, HALO>;
+  if (query) return MODE | RW << 3 | NT << 5 | WM << 7 | NTC << 9 | KS << 11 | DB << 13 | (HALO ? 1 : 0) << 16;
   static bool attr_done = false;
   if (!attr_done) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&cl_conv_kernel<MODE, RW, NT, WM, NTC, KS, DA, DB, HALO>),
@@ -463,36 +465,36 @@ static int cl_conv_launch(const ClConvK& k, dim3 grid, hipStream_t s) {
 // tap geometry -> instantiation.  Ring depths fill the LDS the epilogue's transpose tiles need anyway (8 x 9.5 KiB for 96-row
 // waves): the B stream runs 2..5 units ahead, the A stream one.
 template <int MODE, int RW, int NT, int WM>
-static int cl_conv_pick(const ClConvK& k, dim3 grid, hipStream_t s) {
+static int cl_conv_pick(const ClConvK& k, dim3 grid, hipStream_t s, bool query) {
   const rfx_cl_conv_desc& d = k.d;
   const bool halo = d.NTC > 1 || d.db0 != 0;
   constexpr int MT = RW * WM;
-  if (d.NTC == 3 && d.KS == 1 && halo) return cl_conv_launch<MODE, RW, NT, WM, 3, 1, 2, (MT >= 6 ? 4 : 6), true>(k, grid, s);
-  if (d.NTC == 1 && d.KS == 2 && !halo) return cl_conv_launch<MODE, RW, NT, WM, 1, 2, 2, (MT >= 6 ? 3 : 4), false>(k, grid, s);
-  if (d.NTC == 1 && d.KS == 1 && !halo) return cl_conv_launch<MODE, RW, NT, WM, 1, 1, 2, 6, false>(k, grid, s);
+  if (d.NTC == 3 && d.KS == 1 && halo) return cl_conv_launch<MODE, RW, NT, WM, 3, 1, 2, (MT >= 6 ? 4 : 6), true>(k, grid, s, query);
+  if (d.NTC == 1 && d.KS == 2 && !halo) return cl_conv_launch<MODE, RW, NT, WM, 1, 2, 2, (MT >= 6 ? 3 : 4), false>(k, grid, s, query);
+  if (d.NTC == 1 && d.KS == 1 && !halo) return cl_conv_launch<MODE, RW, NT, WM, 1, 1, 2, 6, false>(k, grid, s, query);
   return -1;
 }
 
 // tile height -> instantiation (the channel-major store exists for 32-row tiles only)
 template <int MODE>
-static int cl_conv_dispatch(const ClConvK& k, dim3 grid, hipStream_t s) {
+static int cl_conv_dispatch(const ClConvK& k, dim3 grid, hipStream_t s, bool query) {
   if constexpr (MODE == RFX_CL_STORE_CM) {
-    return k.d.BM == 32 ? cl_conv_pick<MODE, 1, 1, 1>(k, grid, s) : -1;
+    return k.d.BM == 32 ? cl_conv_pick<MODE, 1, 1, 1>(k, grid, s, query) : -1;
   } else {
     switch (k.d.BM) {
-      case 192: return cl_conv_pick<MODE, 3, 2, 2>(k, grid, s);
-      case 96: return cl_conv_pick<MODE, 3, 1, 1>(k, grid, s);
-      case 64: return cl_conv_pick<MODE, 2, 1, 1>(k, grid, s);
-      case 32: return cl_conv_pick<MODE, 1, 1, 1>(k, grid, s);
+      case 192: return cl_conv_pick<MODE, 3, 2, 2>(k, grid, s, query);
+      case 96: return cl_conv_pick<MODE, 3, 1, 1>(k, grid, s, query);
+      case 64: return cl_conv_pick<MODE, 2, 1, 1>(k, grid, s, query);
+      case 32: return cl_conv_pick<MODE, 1, 1, 1>(k, grid, s, query);
     }
     return -1;
   }
 }
 
 // one per epilogue mode (csrc/cl_conv_m_*.hip)
-int cl_conv_mode_store(const ClConvK& k, dim3 grid, hipStream_t s);
-int cl_conv_mode_gelu(const ClConvK& k, dim3 grid, hipStream_t s);
-int cl_conv_mode_glu(const ClConvK& k, dim3 grid, hipStream_t s);
-int cl_conv_mode_dgelu(const ClConvK& k, dim3 grid, hipStream_t s);
-int cl_conv_mode_dglu(const ClConvK& k, dim3 grid, hipStream_t s);
-int cl_conv_mode_cm(const ClConvK& k, dim3 grid, hipStream_t s);
+int cl_conv_mode_store(const ClConvK& k, dim3 grid, hipStream_t s, bool query);
+int cl_conv_mode_gelu(const ClConvK& k, dim3 grid, hipStream_t s, bool query);
+int cl_conv_mode_glu(const ClConvK& k, dim3 grid, hipStream_t s, bool query);
+int cl_conv_mode_dgelu(const ClConvK& k, dim3 grid, hipStream_t s, bool query);
+int cl_conv_mode_dglu(const ClConvK& k, dim3 grid, hipStream_t s, bool query);
+int cl_conv_mode_cm(const ClConvK& k, dim3 grid, hipStream_t s, bool query);

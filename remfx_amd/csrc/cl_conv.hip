@@ -29,7 +29,8 @@ static bool cl_fits32(const rfx_cl_tensor& t, int rows, int IB) {
   return ((int64_t)rows * t.as + (int64_t)IB * t.bs) * 2 < 0x7fffffffLL && t.bs % 8 == 0 && t.c0 % 8 == 0;
 }
 
-extern "C" int rfx_cl_conv(const rfx_cl_conv_desc* dp, void* stream) {
+// validation + instantiation ladder of rfx_cl_conv and of rfx_cl_conv_variant (query: nothing is launched, no device is touched)
+static int cl_conv_run(const rfx_cl_conv_desc* dp, void* stream, bool query) {
   if (!dp || !dp->in.p || !dp->apack) return -1;
   const rfx_cl_conv_desc& d = *dp;
   if (d.N <= 0 || d.OA <= 0 || d.OB <= 0 || d.OB % 256 || d.OB != d.IB || d.M <= 0 || d.NTR <= 0 || d.NTR > 16 || d.NCH <= 0) return -1;
@@ -43,6 +44,13 @@ extern "C" int rfx_cl_conv(const rfx_cl_conv_desc* dp, void* stream) {
   if ((d.mode == RFX_CL_GELU || d.mode == RFX_CL_DGELU) && !d.out1.p) return -1;
   if ((d.mode == RFX_CL_DGELU || d.mode == RFX_CL_DGLU) && !d.aux0.p) return -1;
   if (d.M % 8 && !cm) return -1;
+  if (d.NTC > 1 || d.db0 != 0) {                            // halo forms: a column tap reaches at most the 8 halo slots of the slab
+    if (d.NTC > 16) return -1;
+    for (int t = 0; t < d.NTC; ++t) {
+      const int v = d.db0 + t * d.db_step;
+      if (v > 8 || v < -8) return -1;
+    }
+  }
   const int orows = d.G > 1 ? d.OAo : d.OA;
   if (!cl_fits32(d.out0, orows, d.IB) || !cl_fits32(d.out1, orows, d.IB) || !cl_fits32(d.aux0, orows, d.IB) || !cl_fits32(d.res, orows, d.IB))
     return -1;
@@ -59,15 +67,18 @@ extern "C" int rfx_cl_conv(const rfx_cl_conv_desc* dp, void* stream) {
   const dim3 grid((unsigned)(8 * k.chunk * k.MG));
   hipStream_t s = (hipStream_t)stream;
   switch (d.mode) {
-    case RFX_CL_STORE: return cl_conv_mode_store(k, grid, s);
-    case RFX_CL_GELU: return cl_conv_mode_gelu(k, grid, s);
-    case RFX_CL_GLU: return cl_conv_mode_glu(k, grid, s);
-    case RFX_CL_DGELU: return cl_conv_mode_dgelu(k, grid, s);
-    case RFX_CL_DGLU: return cl_conv_mode_dglu(k, grid, s);
-    case RFX_CL_STORE_CM: return cl_conv_mode_cm(k, grid, s);
+    case RFX_CL_STORE: return cl_conv_mode_store(k, grid, s, query);
+    case RFX_CL_GELU: return cl_conv_mode_gelu(k, grid, s, query);
+    case RFX_CL_GLU: return cl_conv_mode_glu(k, grid, s, query);
+    case RFX_CL_DGELU: return cl_conv_mode_dgelu(k, grid, s, query);
+    case RFX_CL_DGLU: return cl_conv_mode_dglu(k, grid, s, query);
+    case RFX_CL_STORE_CM: return cl_conv_mode_cm(k, grid, s, query);
   }
   return -1;
 }
+
+extern "C" int rfx_cl_conv(const rfx_cl_conv_desc* dp, void* stream) { return cl_conv_run(dp, stream, false); }
+extern "C" int rfx_cl_conv_variant(const rfx_cl_conv_desc* dp) { return cl_conv_run(dp, nullptr, true); }
 
 // ---- weight packing -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void cl_pack_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx, int64_t n,

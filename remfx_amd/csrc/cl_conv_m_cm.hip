@@ -1,4 +1,4 @@
 // rfx_cl_conv, epilogue mode RFX_CL_STORE_CM (kernel template: csrc/cl_conv.h)
 #include "cl_conv.h"
 
-int cl_conv_mode_cm(const ClConvK& k, dim3 grid, hipStream_t s) { return cl_conv_dispatch<RFX_CL_STORE_CM>(k, grid, s); }
+int cl_conv_mode_cm(const ClConvK& k, dim3 grid, hipStream_t s, bool query) { return cl_conv_dispatch<RFX_CL_STORE_CM>(k, grid, s, query); }

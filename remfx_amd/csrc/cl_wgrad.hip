@@ -321,8 +321,11 @@ static int clw_geometry(const rfx_cl_wgrad_desc& d, ClWgK& k) {
   return 0;
 }
 
+// query: nothing is launched, the return value names the instantiation (rfx_cl_wgrad_variant, include/remfx_hip.h)
 template <int RW, int WK, int PW>
-static int clw_launch1(const ClWgK& k, int lds, hipStream_t s) {
+static int clw_launch1(const ClWgK& k, int lds, hipStream_t s, bool query) {
+  const bool grouped = k.d.S >= 8;                             // the kernel's own test: XCD-grouped block order
+  if (query) return RW | WK << 2 | PW << 5 | (grouped ? 1 : 0) << 13;
   static int attr_lds = 0;
   if (lds > attr_lds) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&cl_wgrad_kernel<RW, WK, PW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
@@ -330,13 +333,13 @@ static int clw_launch1(const ClWgK& k, int lds, hipStream_t s) {
       return -3;
     attr_lds = lds;
   }
-  hipLaunchKernelGGL((cl_wgrad_kernel<RW, WK, PW>), dim3((unsigned)(k.d.S >= 8 ? 8 * k.spx * k.DT : k.d.S * k.DT)), dim3(512), lds, s, k);
+  hipLaunchKernelGGL((cl_wgrad_kernel<RW, WK, PW>), dim3((unsigned)(grouped ? 8 * k.spx * k.DT : k.d.S * k.DT)), dim3(512), lds, s, k);
   RFX_CHECK_LAUNCH();
   return 0;
 }
 template <int RW, int WK>
-static int clw_launch(const ClWgK& k, int lds, hipStream_t s) {
-  return k.d.PW == 128 ? clw_launch1<RW, WK, 128>(k, lds, s) : clw_launch1<RW, WK, 64>(k, lds, s);
+static int clw_launch(const ClWgK& k, int lds, hipStream_t s, bool query) {
+  return k.d.PW == 128 ? clw_launch1<RW, WK, 128>(k, lds, s, query) : clw_launch1<RW, WK, 64>(k, lds, s, query);
 }
 
 extern "C" int64_t rfx_cl_wgrad_ws_floats(const rfx_cl_wgrad_desc* dp) {
@@ -345,7 +348,8 @@ extern "C" int64_t rfx_cl_wgrad_ws_floats(const rfx_cl_wgrad_desc* dp) {
   return (int64_t)dp->S * k.DT * 8 * dp->RW * 2 * 1024;
 }
 
-extern "C" int rfx_cl_wgrad(const rfx_cl_wgrad_desc* dp, void* stream) {
+// validation + instantiation ladder of rfx_cl_wgrad and of rfx_cl_wgrad_variant (query: nothing is launched, no device is touched)
+static int clw_run(const rfx_cl_wgrad_desc* dp, void* stream, bool query) {
   if (!dp || !dp->p.p || !dp->q.p || !dp->ws) return -1;
   ClWgK k;
   if (clw_geometry(*dp, k)) return -1;
@@ -353,14 +357,16 @@ extern "C" int rfx_cl_wgrad(const rfx_cl_wgrad_desc* dp, void* stream) {
   if (lds > 160 * 1024) return -1;
   hipStream_t s = (hipStream_t)stream;
   if (dp->RW == 3) {
-    if (dp->WK == 1) return clw_launch<3, 1>(k, lds, s);
-    if (dp->WK == 2) return clw_launch<3, 2>(k, lds, s);
-    return clw_launch<3, 4>(k, lds, s);
+    if (dp->WK == 1) return clw_launch<3, 1>(k, lds, s, query);
+    if (dp->WK == 2) return clw_launch<3, 2>(k, lds, s, query);
+    return clw_launch<3, 4>(k, lds, s, query);
   }
-  if (dp->WK == 1) return clw_launch<2, 1>(k, lds, s);
-  if (dp->WK == 2) return clw_launch<2, 2>(k, lds, s);
-  return clw_launch<2, 4>(k, lds, s);
+  if (dp->WK == 1) return clw_launch<2, 1>(k, lds, s, query);
+  if (dp->WK == 2) return clw_launch<2, 2>(k, lds, s, query);
+  return clw_launch<2, 4>(k, lds, s, query);
 }
+extern "C" int rfx_cl_wgrad(const rfx_cl_wgrad_desc* dp, void* stream) { return clw_run(dp, stream, false); }
+extern "C" int rfx_cl_wgrad_variant(const rfx_cl_wgrad_desc* dp) { return clw_run(dp, nullptr, true); }
 
 // ---- fixed-order reduction + scatter ----------------------------------------------------------------------------------------------
 // map: one int32 per accumulator element of the kq == 0 waves of every D tile ([DT][WC][RW * 2 * 16][64]): flat index into the weight

@@ -1,0 +1,462 @@
+"""CPU: tests/clast_ref.py proven against float64 autograd, its floors asserted, the case tables walked through the launchers' own selection
+(rfx_cl_conv_variant / rfx_cl_wgrad_variant: no GPU), the halo-overflow refusal, the power of the bound and the planted faults
+(DESIGN.md 4.19)."""
+import ctypes as C
+import functools
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import clast_ref as R
+
+CONV = R.conv_cases()
+WGRAD = R.wgrad_cases()
+BY_ID = {c.id: c for c in CONV + WGRAD}
+
+
+@functools.lru_cache(maxsize=None)
+def _conv_eval(cid):
+    """restatement + judge at K = 1 of one case, computed once for the floors, the power and the fault tests"""
+    c = BY_ID[cid]
+    inp = R.conv_inputs(c)
+    form = R.build_form(c.kind, c.dims)
+    got = R.restate_conv(c, inp, form)
+    lin = R.conv_linear(c, inp)
+    return c, inp, form, got, lin
+
+
+def _wgeom(c):
+    from remfx_amd import clast
+    form = R.build_wform(c.kind, c.dims)
+    PW = form.PW if c.B % form.PW == 0 else 64
+    OA = R.wshapes(c.kind, c.dims, c.N, c.A, c.B)[3][0]
+    saved = clast.CLW_SPLITS
+    clast.CLW_SPLITS = c.splits
+    try:
+        S = form.splits(c.N * (c.B // PW) * OA)
+    finally:
+        clast.CLW_SPLITS = saved
+    return form, PW, S, c.N * (c.B // PW) * OA
+
+
+# ---- the reference against float64 autograd ------------------------------------------------------------------------------------------------
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+@pytest.mark.parametrize("fwd,bwd,dims,A", [("conv", "dgrad", (24, 16, 3, 3), 3), ("conv", "dgrad", (24, 16, 1, 3), 1), ("s4", "s4d", (24, 16), 2),
+                                            ("tr", "trd", (16, 24), 2), ("s4f", "s4fd", (24, 16), 1), ("trf", "trfd", (16, 24), 1)])
+def test_input_gradients_against_autograd(fwd, bwd, dims, A):
+    """the input-gradient kinds are the adjoint of their forward kind: <lin_bwd(g), x> == <g, lin_fwd(x)> element by element through autograd"""
+    xs, ys, ws, _ = R.shapes(fwd, dims, 2, A, 256)
+    x = torch.randn(xs, generator=_g(1), dtype=torch.float64, requires_grad=True)
+    w = torch.randn(ws, generator=_g(2), dtype=torch.float64)
+    y = R.lin(fwd, dims, x, w)
+    assert tuple(y.shape) == ys
+    g = torch.randn(ys, generator=_g(3), dtype=torch.float64)
+    y.backward(g)
+    bx, by, bw, _ = R.shapes(bwd, dims, 2, A, 256)
+    assert bx == ys and by == xs and bw == ws
+    assert float((R.lin(bwd, dims, g, w) - x.grad).abs().max()) < 1e-12
+
+
+def test_transposed_kinds_against_explicit_sums():
+    """tr / tail: out[4 q + psi - 2] = w[psi + 4] x[q - 1] + w[psi] x[q]; s4: out[oa] = sum_k w[k] x[4 oa + k - 2] -- written out as loops"""
+    x = torch.randn(1, 3, 2, 256, generator=_g(4), dtype=torch.float64)
+    w = torch.randn(3, 5, 8, 1, generator=_g(5), dtype=torch.float64)
+    y = R.lin("tr", (3, 5), x, w)
+    ref = torch.zeros(1, 5, 8, 256, dtype=torch.float64)
+    for q in range(2):
+        for k in range(8):
+            o = 4 * q + k - 2
+            if 0 <= o < 8:
+                ref[:, :, o] += torch.einsum("ncb,cd->ndb", x[:, :, q], w[:, :, k, 0])
+    assert float((y - ref).abs().max()) < 1e-12
+    x = torch.randn(1, 3, 8, 256, generator=_g(6), dtype=torch.float64)
+    w = torch.randn(5, 3, 8, 1, generator=_g(7), dtype=torch.float64)
+    y = R.lin("s4", (5, 3), x, w)
+    ref = torch.zeros(1, 5, 2, 256, dtype=torch.float64)
+    for oa in range(2):
+        for k in range(8):
+            i = 4 * oa + k - 2
+            if 0 <= i < 8:
+                ref[:, :, oa] += torch.einsum("ncb,dc->ndb", x[:, :, i], w[:, :, k, 0])
+    assert float((y - ref).abs().max()) < 1e-12
+
+
+def test_dx_kind_against_autograd():
+    Cc, H, dil = 16, 6, 2
+    x = torch.randn(2, Cc, 1, 256, generator=_g(8), dtype=torch.float64, requires_grad=True)
+    w1 = torch.randn(H, Cc, 1, 3, generator=_g(9), dtype=torch.float64)
+    h = F.conv2d(x, w1, padding=(0, dil), dilation=(1, dil))
+    dh = torch.randn(2, 16, 1, 256, generator=_g(10), dtype=torch.float64)
+    h.backward(dh[:, :H])
+    assert float((R.lin("dx", (Cc, H, dil), dh, w1) - x.grad).abs().max()) < 1e-12
+
+
+@pytest.mark.parametrize("kind,dims,A", [("w", (24, 16, 3, 3), 2), ("ws4", (24, 16), 2), ("wtr", (16, 24), 2), ("ws4f", (24, 16), 1), ("wtrf", (16, 24), 1),
+                                         ("wdc1", (8, 16, 2), 2)])
+def test_weight_gradient_against_conv2d_weight(kind, dims, A):
+    """wgrad_linear (autograd of the layer) against torch.nn.grad.conv2d_weight / the defining sum, and db = sum P"""
+    ps, qs, ws, _ = R.wshapes(kind, dims, 2, A, 256)
+    p = torch.randn(ps, generator=_g(11), dtype=torch.float64)
+    q = torch.randn(qs, generator=_g(12), dtype=torch.float64)
+    dw, db = R.wgrad_linear(kind, dims, p, q)
+    if kind == "w":
+        ref = torch.nn.grad.conv2d_weight(q, ws, p, padding=(1, 1))
+    elif kind == "wdc1":
+        ref = torch.nn.grad.conv2d_weight(q, ws, p, padding=(0, 2), dilation=(1, 2))
+    elif kind == "ws4":
+        ref = torch.nn.grad.conv2d_weight(q, ws, p, stride=(4, 1), padding=(2, 0))
+    elif kind == "wtr":                                             # the transposed layer is the adjoint of a convolution q -> p with the same weight
+        ref = torch.nn.grad.conv2d_weight(q, ws, p, stride=(4, 1), padding=(2, 0))
+    elif kind == "ws4f":
+        ref = torch.nn.grad.conv2d_weight(q, ws, p, stride=(1, 4), padding=(0, 2))
+    else:
+        ref = torch.nn.grad.conv2d_weight(q, ws, p, stride=(1, 4), padding=(0, 2))
+    assert float((dw - ref).abs().max()) < 1e-10
+    assert float((db - p.sum((0, 2, 3))).abs().max()) == 0.0
+
+
+def test_activation_formulas_against_autograd():
+    u = torch.randn(4096, generator=_g(13), dtype=torch.float64, requires_grad=True)
+    assert float((R.gelu(u) - F.gelu(u)).abs().max()) < 1e-14
+    F.gelu(u).sum().backward()
+    assert float((R.dgelu(u.detach()) - u.grad).abs().max()) < 1e-14
+    zab = torch.randn(2, 16, 1, 64, generator=_g(14), dtype=torch.float64, requires_grad=True)
+    g = torch.randn(2, 8, 1, 64, generator=_g(15), dtype=torch.float64)
+    F.glu(zab, dim=1).backward(g)
+    a, b = zab.detach()[:, :8], zab.detach()[:, 8:]
+    s = torch.sigmoid(b)
+    assert float((torch.cat([g * s, g * a * s * (1 - s)], 1) - zab.grad).abs().max()) < 1e-14
+
+
+def test_im2col_reference():
+    x = torch.randn(1, 2, 8, 64, generator=_g(16))
+    o = R.im2col_ref(x, 2, 64, False)
+    xb = R.bf(x)
+    for oa in range(2):
+        for k in range(8):
+            i = 4 * oa + k - 2
+            for c in range(2):
+                want = xb[0, c, i] if 0 <= i < 8 else torch.zeros(64, dtype=torch.float64)
+                assert torch.equal(o[0, oa, :, 2 * k + c], want)
+    x = torch.randn(1, 1, 1, 256, generator=_g(17))
+    o = R.im2col_ref(x, 1, 64, True)
+    for b in (0, 1, 63):
+        for k in range(8):
+            i = 4 * b + k - 2
+            want = R.bf(x)[0, 0, 0, i] if 0 <= i < 256 else 0.0
+            assert float(o[0, 0, b, k]) == float(want)
+    assert bool((o[..., 8:] == 0).all())
+
+
+# ---- the case tables through the launchers' own selection ------------------------------------------------------------------------------------
+# every instantiation rfx_cl_conv / rfx_cl_wgrad can select (cl_conv_dispatch x cl_conv_pick; the RW / WK / PW ladder of cl_wgrad.hip)
+_M = ("RFX_CL_STORE", "RFX_CL_GELU", "RFX_CL_GLU", "RFX_CL_DGELU", "RFX_CL_DGLU")
+_F32 = ("1, 1, 1, 3, 1, 2, 6, true", "1, 1, 1, 1, 2, 2, 4, false", "1, 1, 1, 1, 1, 2, 6, false")
+_F64 = ("2, 1, 1, 3, 1, 2, 6, true", "2, 1, 1, 1, 2, 2, 4, false", "2, 1, 1, 1, 1, 2, 6, false")
+_F96 = ("3, 1, 1, 3, 1, 2, 6, true", "3, 1, 1, 1, 2, 2, 4, false", "3, 1, 1, 1, 1, 2, 6, false")
+_F192 = ("3, 2, 2, 3, 1, 2, 4, true", "3, 2, 2, 1, 2, 2, 3, false", "3, 2, 2, 1, 1, 2, 6, false")
+CONV_FORMS = [f"cl_conv_kernel<{m}, {f}>" for m in _M for f in _F32 + _F64 + _F96 + _F192] + [f"cl_conv_kernel<RFX_CL_STORE_CM, {f}>" for f in _F32]
+WGRAD_FORMS = ["cl_wgrad_kernel<2, 1, 64>", "cl_wgrad_kernel<2, 1, 128>", "cl_wgrad_kernel<2, 2, 64>", "cl_wgrad_kernel<2, 2, 128>",
+               "cl_wgrad_kernel<2, 4, 64>", "cl_wgrad_kernel<2, 4, 128>", "cl_wgrad_kernel<3, 1, 64>", "cl_wgrad_kernel<3, 1, 128>",
+               "cl_wgrad_kernel<3, 2, 64>", "cl_wgrad_kernel<3, 2, 128>", "cl_wgrad_kernel<3, 4, 64>", "cl_wgrad_kernel<3, 4, 128>"]
+
+
+def test_form_lists():
+    assert len(CONV_FORMS) == 63 == len(set(CONV_FORMS)) and len(WGRAD_FORMS) == 12 == len(set(WGRAD_FORMS))
+
+
+@pytest.mark.parametrize("case", CONV, ids=[c.id for c in CONV])
+def test_conv_case_names_its_instantiation(case):
+    assert R.host_form(case) == case.form
+
+
+@pytest.mark.parametrize("case", WGRAD, ids=[c.id for c in WGRAD])
+def test_wgrad_case_names_its_instantiation(case):
+    assert R.host_form(case) == (case.form, case.order)
+    form, PW, S, steps = _wgeom(case)
+    assert S == case.S, (S, steps)
+    assert (case.order == "grouped") == (S >= 8)
+    if case.ahead:
+        assert form.ahead == case.ahead
+    pre = -(-(form.NTR - form.SA) // form.SA)
+    for e in case.edges:
+        if e.startswith("PRE"):
+            assert pre == int(e[3:]), (e, pre)
+    if "multi_step" in case.edges:
+        assert -(-steps // S) >= 2
+    if "last_split_short" in case.edges:
+        sps = -(-steps // S)
+        assert steps % sps != 0 and (S + 7) // 8 > 1
+    if "sample_boundary" in case.edges:                                # some split holds steps of two samples
+        sps = -(-steps // S)
+        per_n = steps // case.N
+        assert any((s * sps) // per_n != (min((s + 1) * sps, steps) - 1) // per_n for s in range(S))
+
+
+def test_case_tables_reach_every_form():
+    assert {c.form for c in CONV} == set(CONV_FORMS)
+    assert {c.form for c in WGRAD} == set(WGRAD_FORMS)
+
+
+def test_named_edges_are_present():
+    ce = {e for c in CONV for e in c.edges}
+    for e in ("M==BM", "ragged_rows", "row_groups", "M8", "glu_M16", "halo_interior", "dilation2", "dilation8", "ptiles1", "ptiles7", "ptiles8", "ptiles9",
+              "ptiles17", "3taps_IA1", "3taps_IA2", "s4_OA1", "merged_IA1", "bias_absent", "bias_merged", "rowadd_rows", "res_dglu", "res_dgelu",
+              "out1_dglu", "gelu_inference", "cm_fold0", "cm_fold1", "cm_Co1", "cm_Co2", "cm_view", "x_c0", "out_slice", "folded_in", "folded_out",
+              "net", "head", "tail", "time"):
+        assert e in ce, e
+    assert any(c.B == 512 for c in CONV) and any(c.B == 768 for c in CONV)
+    assert any(c.mode == "store" and c.res for c in CONV) and any(c.mode == "gelu" and c.aux for c in CONV)
+    assert any(c.mode == "gelu" and not c.aux and c.out0 for c in CONV) and any(c.mode == "glu" and not c.bias for c in CONV)
+    we = {e for c in WGRAD for e in c.edges}
+    for e in ("PW64", "S1", "S3", "S8", "S>8", "spx2", "last_split_short", "grouped", "multi_step", "sample_boundary", "column_boundary", "PRE1", "PRE2",
+              "ahead1", "ahead2", "ahead3", "ahead4", "ragged_M40", "ragged_M104", "ragged_Cq24", "ragged_Cq40", "no_bias_column", "dilation2", "dilation8",
+              "p_c0", "q_c0", "accumulate", "folded", "structural_zeros", "net"):
+        assert e in we, e
+    # the tile counts the XCD chunk mapping sees
+    for c in CONV:
+        for e in c.edges:
+            if e.startswith("ptiles"):
+                ys = R.shapes(c.kind, c.dims, c.N, c.A, c.B)
+                assert c.N * ys[3][1] * (c.B // 256) == int(e[6:]), c.id
+
+
+# ---- the refusal of a column offset outside the halo -------------------------------------------------------------------------------------------
+def _variant_of(db0, db_step, NTC=3):
+    import numpy as np
+    from remfx_amd import clast
+    f = clast.ConvForm(32, 16, 1, NTC, 0, 0, db0, db_step, 1, lambda m, r, t, ch: np.zeros(np.broadcast(m, r, t, ch).shape, dtype=np.int64), KS=1)
+    x = torch.zeros(1, 1, 256, 16, dtype=torch.bfloat16)
+    y = torch.zeros(1, 1, 256, 32, dtype=torch.bfloat16)
+    ap = torch.zeros(f.idx.size, dtype=torch.bfloat16)
+    with R.recorder(True) as tr:
+        clast.conv(f, ap, x, 1, 1, 256, 1, "store", out0=y)
+        return tr[0][1]
+
+
+def test_halo_overflow_is_refused():
+    """rfx_cl_conv_variant runs the launcher's own checks: |db0 + t db_step| <= 8 for every column tap of a halo form.  Never launched."""
+    assert _variant_of(-8, 8) > 0 and _variant_of(-1, 1) > 0 and _variant_of(-2, 2) > 0
+    assert _variant_of(-9, 9) < 0                                     # dilation 9: both outer taps outside the halo
+    assert _variant_of(-8, 9) < 0                                     # only the last tap (+10)
+    assert _variant_of(-10, 8) < 0                                    # only the first (-10)
+    assert _variant_of(0, 5) < 0                                      # taps 0, 5, 10
+    assert _variant_of(0, 4) > 0                                      # taps 0, 4, 8: the limit itself
+
+
+def test_wgrad_variant_refuses_what_the_launcher_refuses():
+    from remfx_amd import _lib
+    d = _lib.ClWgradDesc()
+    assert _lib.lib().rfx_cl_wgrad_variant(C.byref(d)) < 0
+
+
+# ---- floors ---------------------------------------------------------------------------------------------------------------------------------
+def _quarter(v):
+    return max(0.25, math.ceil(v * 4 - 1e-9) / 4)
+
+
+def test_floors():
+    """FLOORS against the measurement: per class the largest floor over the table, rounded up to the next quarter"""
+    fl = {}
+    for c in CONV:
+        c, inp, form, got, lin = _conv_eval(c.id)
+        res = R.conv_judge(c, inp, got, 1.0, lin)
+        kl = c.mode
+        fl[kl] = max([fl.get(kl, 0.0)] + [R.floor_of(v, got[k], k != "cm") for k, v in res.items()])
+    for c in WGRAD:
+        form, PW, S, _ = _wgeom(c)
+        inp = R.wgrad_inputs(c)
+        got = R.restate_wgrad(c, inp, form, S, PW)
+        res = R.wgrad_judge(c, inp, got, {"dw": 1.0, "db": 1.0})
+        for k, v in res.items():
+            fl[k] = max(fl.get(k, 0.0), R.floor_of(v, got[k], False))
+    # rowsum
+    x = R.bf16_rne(torch.randn(37, 1, 192, 40, generator=_g(20)))
+    for A, G in ((1, 16), (1, 37)):
+        s = R.restate_rowsum(x, A, G, 0.5)
+        val, mag = 0.5 * x.double().sum((0, 2)), 0.5 * x.double().abs().sum((0, 2))
+        fl["rowsum"] = max(fl.get("rowsum", 0.0), float(((s.double() - val).abs() / (R.EPS32 * mag)).max()))
+    # the fused cl_elem modes in fp32
+    xx = R.bf16_rne(torch.randn(1, 16, 2, 64, generator=_g(21)))
+    rr = R.bf16_rne(torch.randn(1, 16, 2, 64, generator=_g(22)))
+    zz = R.bf16_rne(torch.randn(1, 32, 2, 64, generator=_g(23)))
+    v32 = R.bf16_rne(xx + rr)
+    e = []
+    for mode, o32, aux in (("gelu", F.gelu(v32), None), ("dgelu", v32 * R.dgelu(zz[:, :16].double()).float(), zz[:, :16]),
+                           ("dglu", torch.cat([v32 * torch.sigmoid(zz[:, 16:]), v32 * zz[:, :16] * torch.sigmoid(zz[:, 16:]) * (1 - torch.sigmoid(zz[:, 16:]))], 1), zz)):
+        lo, hi = 0.0, 64.0
+        got = R.bf16_rne(o32)
+        for _ in range(12):                                           # the smallest K (in eighths) the fp32 evaluation passes at
+            mid = 0.5 * (lo + hi)
+            lo, hi = (lo, mid) if R.from_cm_judge(mode, xx, rr, aux, got, mid)[0] <= 1.0 else (mid, hi)
+        e.append(hi)
+    fl["elem"] = max(e)
+    print({k: round(v, 3) for k, v in fl.items()})
+    for k, v in fl.items():
+        assert v <= R.FLOORS[k], (k, v)
+        assert R.FLOORS[k] == _quarter(v), (k, v, R.FLOORS[k])
+
+
+# ---- power -----------------------------------------------------------------------------------------------------------------------------------
+FOLD = 400.0
+# share (%) of the elements of an output whose fp32 slack reaches half their own bf16 ulp: the largest over the case table measured on the
+# reference alone (a property of the inputs and of K, not of a kernel), rounded up to the next quarter.  Measured: store 0.63; gelu 1.75 (z)
+# / 1.49; glu 1.04 (z) / 1.04; dgelu 1.53 (the gradient) / 0.01; dglu 0.21 / 0.00.  The pre-activations of the 192- and 384-channel layers
+# cancel most (1700 - 3500 products per element, K = 16 with the GELU floor); the staged outputs hardly at all: their inputs are exact.
+SHARE = {"store": {"out0": 0.75}, "gelu": {"out0": 2.0, "out1": 1.75}, "glu": {"out0": 1.25, "out1": 1.25}, "dgelu": {"out0": 1.75, "out1": 0.25},
+         "dglu": {"out1": 0.25, "out0": 0.25}}
+
+
+# Outputs computed from a rounded value that is NOT stored (store + res, gelu / dgelu without out0, dglu without out1): share (%) of the
+# elements cancelling less than FOLD-fold whose whole bound reaches one bf16 ulp of the element.  Measured on the reference over the table:
+# store 57.2; gelu out1 63.8; dgelu out0 58.2 / out1 95.6; dglu out1 61.2 / out0 89.6, rounded up.  These are large and cannot be made
+# small: bf16(bf16(v) + res) is off by up to half an ulp of v AND half an ulp of the sum, and the element is smaller than v about half of
+# the time; a product with gelu' or sigmoid is smaller than its factor nearly always.  The second rounding is the kernel's arithmetic (the
+# finding of 4.16), not slack of the test: the bound is still half an ulp of each value the kernel rounds, the tightest a reference that
+# cannot see the inner value can be.  Every case also runs in its staged form (out0 / out1 stored) somewhere in the table, where this term
+# is absent, and the non-storing variant must equal the storing one bit for bit on the GPU.
+INNER_SHARE = {("store", "out0"): 60.0, ("gelu", "out1"): 65.0, ("dgelu", "out0"): 60.0, ("dgelu", "out1"): 96.0, ("dglu", "out1"): 62.5,
+               ("dglu", "out0"): 90.0}
+
+
+@pytest.mark.parametrize("case", CONV, ids=[c.id for c in CONV])
+def test_every_conv_case_has_power(case):
+    c, inp, form, got, lin = _conv_eval(case.id)
+    K = R.K_conv(c)
+    assert K < 2.0 ** 14 / FOLD
+    res = R.conv_judge(c, inp, got, K, lin)
+    for k, v in res.items():
+        ref = v["val"]
+        rms = float(ref.pow(2).mean().sqrt())
+        assert float(v["tol32"].max()) <= 1e-3 * rms, (case.id, k, float(v["tol32"].max()) / rms)
+        if k == "cm":
+            continue
+        ulp = R._ulp16(ref)
+        miss = v["tol32"] >= 0.5 * ulp
+        mag = v["tol32"] / (K * R.EPS32)
+        below = mag < FOLD * ref.abs()
+        share = 100.0 * float(miss.double().mean())
+        print(f"{case.id} {k}: K {K:.0f}; fp32 slack / RMS {float(v['tol32'].max()) / rms:.2e}; slack above half the element's ulp in {share:.2f} %")
+        assert not bool((miss & below).any()), (case.id, k)
+        assert share <= SHARE[c.mode][k], (case.id, k, share)
+        # the WHOLE tolerance ahead of the final half ulp: with an unstaged inner rounding (store + res, gelu / dgelu without out0, dglu
+        # without out1) it carries half a bf16 ulp of the inner value times the derivative of what follows, which no reference can remove.
+        # It stays under half the element's ulp -- the whole bound under one ulp -- except where the element is smaller than the inner value
+        # (a residual of opposite sign, gelu at z < 0, a small gelu' or gate): that share has its own ceiling.
+        if float((v["pre"] - v["tol32"]).abs().max()) > 0:
+            miss2 = (v["pre"] >= 0.5 * ulp) & below
+            share2 = 100.0 * float(miss2.double().mean())
+            print(f"{case.id} {k}: unstaged inner rounding: whole bound of an ulp or more in {share2:.2f} % of the elements that cancel < {FOLD:.0f}-fold")
+            assert share2 <= INNER_SHARE[(c.mode, k)], (case.id, k, share2)
+
+
+@pytest.mark.parametrize("case", WGRAD, ids=[c.id for c in WGRAD])
+def test_every_wgrad_case_has_power(case):
+    inp = R.wgrad_inputs(case)
+    got = {"dw": torch.zeros(R.wshapes(case.kind, case.dims, case.N, case.A, case.B)[2]), "db": torch.zeros(R.wshapes(case.kind, case.dims, case.N, case.A, case.B)[0][1])}
+    res = R.wgrad_judge(case, inp, got, R.K_wgrad())
+    for k, v in res.items():
+        rms = float(v["val"].pow(2).mean().sqrt())
+        assert float(v["tol"].max()) <= 1e-3 * rms, (case.id, k, float(v["tol"].max()) / rms)
+
+
+# ---- planted faults ----------------------------------------------------------------------------------------------------------------------------
+CONV_FAULTS = [("halo_zero_interior", "tiles-b512-3x3"), ("halo_zero_interior", "tiles-b512-dil2"), ("halo_nonzero_row_end", "tiles-b768-dil8"),
+               ("halo_nonzero_row_end", "net48-dec-rewrite"), ("row_tap_dropped_first", "taps-3rows-ia2"), ("row_tap_dropped_last", "net48-enc-conv"),
+               ("merged_phase_off_by_one", "taps-tr-ia3"), ("bias_by_gemm_row", "epi-merged-bias"), ("bias_by_gemm_row", "tiles-b512-3x3"),
+               ("rowadd_wrong_row", "epi-rowadd"), ("ragged_rows_from_neighbour", "rows-groups-96"), ("last_ptile_skipped", "tiles-count9"),
+               ("res_twice_one_row", "tiles-b768-3x3"), ("truncation", "view-xslice"), ("one_ulp", "net48-dec-rewrite")]
+WGRAD_FAULTS = [("step_dropped", "wg-s3"), ("sample_boundary_stale", "wg-s1"), ("ring_row_early", "wg-s1"), ("source_missing", "wg-s11-short"),
+                ("bias_from_q_column", "wg-s3"), ("col_tap_off_by_one", "wg-dil2"), ("ragged_cq_from_neighbour", "wg-214-128")]
+
+
+def test_every_mutation_is_planted():
+    assert {m for m, _ in CONV_FAULTS} | {"row_past_oao"} == set(R.CONV_MUTATIONS)
+    assert {m for m, _ in WGRAD_FAULTS} | {"rowsum_last_sample"} == set(R.WGRAD_MUTATIONS)
+
+
+@pytest.mark.parametrize("mut,cid", CONV_FAULTS, ids=[f"{m}@{c}" for m, c in CONV_FAULTS])
+def test_conv_fault_is_rejected(mut, cid):
+    """the fault planted into the restatement, judged by the GPU test's own tolerance at the case that names the edge; what the old
+    assertions (test_gpu_clast._close at 3 ulps) say about the same tensors is recorded"""
+    c, inp, form, clean, lin = _conv_eval(cid)
+    K = R.K_conv(c)
+    assert all(v["q"] <= 1.0 for v in R.conv_judge(c, inp, clean, K, lin).values())
+    bad = R.restate_conv(c, inp, form, mutate=mut)
+    res = R.conv_judge(c, inp, bad, K, lin)
+    worst = max(v["q"] for v in res.values())
+    k = max(res, key=lambda n: res[n]["q"])
+    nbad = int(((bad[k].double() - res[k]["val"]).abs() > res[k]["tol"]).sum())
+    old = all(R.old_close(bad[n], res[n]["val"], 3.0, mag=res[n]["tol32"] / (K * R.EPS32) if c.res else None) for n in res if n != "cm")
+    print(f"FAULT {mut} @ {cid}: error / tolerance {worst:.1f} at {k}, {nbad} of {bad[k].numel()} elements outside; old _close "
+          f"{'accepts' if old else 'rejects'}; rel rms {R.rel_rms(bad[k], res[k]['val']):.2e} (clean {R.rel_rms(clean[k], res[k]['val']):.2e})")
+    assert worst > 1.0
+
+
+@pytest.mark.parametrize("mut,cid", WGRAD_FAULTS, ids=[f"{m}@{c}" for m, c in WGRAD_FAULTS])
+def test_wgrad_fault_is_rejected(mut, cid):
+    c = BY_ID[cid]
+    form, PW, S, _ = _wgeom(c)
+    inp = R.wgrad_inputs(c)
+    K = R.K_wgrad()
+    clean = R.restate_wgrad(c, inp, form, S, PW)
+    assert all(v["q"] <= 1.0 for v in R.wgrad_judge(c, inp, clean, K).values())
+    bad = R.restate_wgrad(c, inp, form, S, PW, mutate=mut)
+    res = R.wgrad_judge(c, inp, bad, K)
+    worst = max(v["q"] for v in res.values())
+    k = max(res, key=lambda n: res[n]["q"])
+    old = all(R.old_wclose(bad[n], res[n]["val"]) for n in res)
+    print(f"FAULT {mut} @ {cid}: error / tolerance {worst:.1f} at {k}; old _wclose {'accepts' if old else 'rejects'}; rel rms "
+          f"{R.rel_rms(bad[k], res[k]['val']):.2e} (clean {R.rel_rms(clean[k], res[k]['val']):.2e})")
+    assert worst > 1.0
+
+
+def test_elem_faults_are_rejected():
+    """from_cm's GLU backward with the stored halves swapped; rowsum without its last sample"""
+    K = R.k_of(R.FLOORS["elem"])
+    x = R.bf16_rne(torch.randn(1, 16, 2, 64, generator=_g(30)))
+    zab = R.bf16_rne(torch.randn(1, 32, 2, 64, generator=_g(31)))
+    s = torch.sigmoid(zab[:, 16:])
+    good = R.bf16_rne(torch.cat([x * s, x * zab[:, :16] * s * (1 - s)], 1))
+    assert R.from_cm_judge("dglu", x, None, zab, good, K)[0] <= 1.0
+    sw = torch.cat([zab[:, 16:], zab[:, :16]], 1)
+    s2 = torch.sigmoid(sw[:, 16:])
+    bad = R.bf16_rne(torch.cat([x * s2, x * sw[:, :16] * s2 * (1 - s2)], 1))
+    assert R.from_cm_judge("dglu", x, None, zab, bad, K)[0] > 1.0
+    xs = R.bf16_rne(torch.randn(9, 1, 64, 16, generator=_g(32)))
+    val, mag = xs.double().sum((0, 2)), xs.double().abs().sum((0, 2))
+    tol = R.k_of(R.FLOORS["rowsum"]) * R.EPS32 * mag
+    assert R.worst(R.restate_rowsum(xs, 1, 4, 1.0), val, tol)[0] <= 1.0
+    q = R.worst(R.restate_rowsum(xs, 1, 4, 1.0, mutate="rowsum_last_sample"), val, tol)[0]
+    print(f"FAULT rowsum_last_sample: error / tolerance {q:.1f}")
+    assert q > 1.0
+
+
+@pytest.mark.parametrize("cid,N", [("view-oslice-merged", 1), ("taps-tr-ia3", 2)])
+@pytest.mark.parametrize("stray_wins", [False, True])
+def test_row_stored_past_oao_is_rejected(cid, N, stray_wins):
+    """A merged form that stores output row OAo as well.  In the dense buffers of the GPU test that row lands on row 0 of the next sample,
+    where it races with the row's own store, and from the last sample on the guard behind the buffer: the restatement's result goes
+    through the GPU test's own Arena and checks.  The guard catches it whatever N and whoever wins the race; where the stray store wins,
+    the judge rejects row 0 of the second sample too."""
+    c, inp, form, clean, lin = _conv_eval(cid)
+    assert c.N == N and c.kind in R.MERGED and c.mode == "store"
+    OAo = 4 * c.A
+    K = R.K_conv(c)
+    arena = R.Arena("cpu")
+    got = {"out0": R.store_guarded(clean["out0"], OAo, arena, stray_wins)}
+    assert arena.intact() and all(v["q"] <= 1.0 for v in R.conv_judge(c, inp, got, K, lin).values())
+    bad = R.restate_conv(c, inp, form, mutate="row_past_oao")
+    assert bad["out0"].shape[2] == OAo + 1
+    arena = R.Arena("cpu")
+    got = {"out0": R.store_guarded(bad["out0"], OAo, arena, stray_wins)}
+    q = max(v["q"] for v in R.conv_judge(c, inp, got, K, lin).values())
+    print(f"FAULT row_past_oao @ {cid} (N = {N}, stray store {'last' if stray_wins else 'first'}): guard {'intact' if arena.intact() else 'overwritten'}; "
+          f"error / tolerance {q:.1f}")
+    assert not arena.intact()
+    assert (q > 1.0) == (stray_wins and N > 1)
