@@ -20,8 +20,10 @@ S * audio_channels rows of a clip with the clip's one (std, mean) pair while cha
 inverse STFT reads (rfx_fm_cm_affine_g), and adds the time branch in one pass (rfx_row_affine_add).  forward returns
 (B, S, audio_channels, T); HDemucs.separate runs files of any length through overlapping clips (segment.py).
 """
+import contextlib
 import math
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -51,27 +53,6 @@ def _data_parallel():
     return torch.is_grad_enabled() and ops.SINK is None
 
 
-def _dev_env(name, default):
-    """Hazard-hunt / measurement switches (they serialise streams, skip whole DConv branches or re-enable a known-bad statistics
-    path): honoured only under RFX_DEV=1, and then announced -- a leaked variable must not silently change results."""
-    v = os.environ.get(name)
-    if v is None or v == default:
-        return default
-    if os.environ.get("RFX_DEV") != "1":
-        import warnings
-        warnings.warn(f"{name}={v} ignored: development switch, set RFX_DEV=1 to honour it")
-        return default
-    import warnings
-    warnings.warn(f"RFX_DEV=1: development switch {name}={v} is ACTIVE and changes what the network computes or how it is ordered")
-    return v
-
-
-_XSUB = int(_dev_env("RFX_XSYNC_SUB", "0"))
-_CUR = [None, None]
-_XIDX = int(_dev_env("RFX_XSYNC_IDX", "-1"))
-_XSYNC = int(_dev_env("RFX_XSYNC", "0"))      # dev: serialisation points of the two-stream hazard hunt (DESIGN.md 4.10)
-
-
 def _time_stream(device):
     idx = device.index if device.index is not None else torch.cuda.current_device()
     st = _TIME_STREAMS.get(idx)
@@ -81,8 +62,8 @@ def _time_stream(device):
     return st
 
 
-CL_DCONV = os.environ.get("RFX_CL_DCONV", "1") != "0"
-CL_TIME_DCONV = os.environ.get("RFX_CL_TIME_DCONV", "1") != "0"    # ... the time branch's too (whole-clip GroupNorm: the kernels run in passes)       # ... and their DConv branches on the fused channels-last kernels (cldconv.py)
+CL_DCONV = os.environ.get("RFX_CL_DCONV", "1") != "0"              # ... and their DConv branches on the fused channels-last kernels (cldconv.py)
+CL_TIME_DCONV = os.environ.get("RFX_CL_TIME_DCONV", "1") != "0"    # ... the time branch's too (whole-clip GroupNorm: the kernels run in passes)
 
 
 class _ScaledEmbedding(nn.Module):
@@ -99,10 +80,6 @@ class _ScaledEmbedding(nn.Module):
     def table(self):
         """(num_embeddings, dim) scaled table == forward(arange(n))."""
         return self.embedding.weight * self.scale
-
-
-# partial-sum slots per sample for the GEMM-epilogue GroupNorm statistics (spreads same-address fp64 atomics)
-_STAT_SLOTS = 16
 
 
 class _LayerScale(nn.Module):
@@ -154,26 +131,6 @@ class _LocalState(nn.Module):
         return nnops.add(x, ops.conv1d(res, self.proj.weight, self.proj.bias))
 
 
-# The C >= 192 DConv branches took their GroupNorm statistics from the producing GEMM's epilogue (fp64 atomics into a zero-filled slot
-# buffer): those lose contributions while a second stream keeps the machine busy.  Default now: the GroupNorm kernel
-# computes them from the stored 16-bit tensor with per-chunk stores (what autocast's GroupNorm sees); 1 = the epilogue form (A/B).
-DCONV_EPI_STATS = _dev_env("RFX_DCONV_EPI_STATS", "0") != "0"
-_ST_MODE = int(_dev_env("RFX_ST_MODE", "0"))     # dev: how the statistics buffer of the channel-major DConv is zeroed (hazard hunt)
-
-
-def _stat_buf(x):
-    if _ST_MODE == 1:
-        return torch.zeros((x.shape[0], _STAT_SLOTS, 2), device=x.device, dtype=torch.float64)
-    st = ops.zeros((x.shape[0], _STAT_SLOTS, 2), x.device, torch.float64)
-    if _ST_MODE == 2:                                   # a second fill: does a late write-back of the first one matter?
-        ops._lib.check(ops._lib.lib().rfx_zero(ops._ptr(st), st.numel() * 8, ops._stream()), "rfx_zero")
-    return st
-
-
-_DCONV_DBG = None       # dev (scripts/probes/dconv_steps.py): a list collects per-sample checksums after every step of the channel-major path
-_DBG_SKIP = {int(v) for v in _dev_env('RFX_DBG_SKIP_DCONV_C', '').split(',') if v}   # measurement only
-
-
 class _DConv(nn.Module):
     def __init__(self, channels, compress=4, depth=2, init=1e-4, norm_type="group_norm", attn=False,
                  heads=4, ndecay=4, lstm=False, kernel_size=3):
@@ -212,8 +169,6 @@ class _DConv(nn.Module):
         return x
 
     def forward(self, x):
-        if _DBG_SKIP and self.layers[0][0].in_channels in _DBG_SKIP:
-            return x
         for seq, (dil, pad, lstm, attn) in zip(self.layers, self.spec):
             mods = list(seq)
             if (not lstm and not attn and mods[1].eps == mods[4].eps and mods[1].num_groups == 1 and
@@ -222,28 +177,21 @@ class _DConv(nn.Module):
                 # frequency-branch samples of (C, 256): the whole depth-layer in one launch per direction (csrc/dconv.hip)
                 x = nnops.dconv_layer(x, mods[0], mods[1], mods[3], mods[4], mods[6].scale, dil)
                 continue
-            st = _stat_buf(x) if DCONV_EPI_STATS else None   # GN(1, C) statistics out of the GEMM epilogue (A/B), else from the stored tensor
-            y, x = ops.conv1d_fork(x, mods[0].weight, mods[0].bias, 1, pad, dil, stat_sums=st, out_bf16=True)   # statistics come out of the GEMM epilogue
-            if _DCONV_DBG is not None:
-                _DCONV_DBG.append(("conv1", y.float().abs().sum(dim=(1, 2)), st.sum(dim=1).clone() if st is not None else None))
-            y = nnops.group_norm(y, 1, mods[1].weight, mods[1].bias, mods[1].eps, mode="gelu", sums=st)
-            if _DCONV_DBG is not None:
-                _DCONV_DBG.append(("gn1", y.float().abs().sum(dim=(1, 2)), None))
+            # Both GroupNorm kernels compute their GN(1, C) statistics from the stored 16-bit tensor with per-chunk stores (what autocast's
+            # GroupNorm sees).  Taking them from the producing GEMM's epilogue (fp64 atomics into a zero-filled slot buffer) loses
+            # contributions while a second stream keeps the machine busy.
+            y, x = ops.conv1d_fork(x, mods[0].weight, mods[0].bias, 1, pad, dil, out_bf16=True)
+            y = nnops.group_norm(y, 1, mods[1].weight, mods[1].bias, mods[1].eps, mode="gelu")
             i = 3
             if lstm:
                 y = mods[i](y); i += 1
             if attn:
                 y = mods[i](y); i += 1
-            st = _stat_buf(x) if DCONV_EPI_STATS else None
             # the 2C-channel tensor is read only by the GroupNorm + GLU kernel (and, in backward, its gradient only by GEMMs):
             # 16-bit storage in the bf16 mode
-            y = ops.conv1d(y, mods[i].weight, mods[i].bias, stat_sums=st, out_bf16=True)
-            if _DCONV_DBG is not None:
-                _DCONV_DBG.append(("conv2", y.float().abs().sum(dim=(1, 2)), st.sum(dim=1).clone() if st is not None else None))
+            y = ops.conv1d(y, mods[i].weight, mods[i].bias, out_bf16=True)
             x = nnops.group_norm(y, 1, mods[i + 1].weight, mods[i + 1].bias, mods[i + 1].eps,
-                                 mode="glu_scale_res", res=x, scale=mods[i + 3].scale, sums=st)
-            if _DCONV_DBG is not None:
-                _DCONV_DBG.append(("gn2", x.float().abs().sum(dim=(1, 2)), None))
+                                 mode="glu_scale_res", res=x, scale=mods[i + 3].scale)
         return x
 
 
@@ -317,10 +265,10 @@ class _HEncLayer(nn.Module):
         out = self._rest(y, inject)
         return (out, alias) if want_pair else out
 
-    def head(self, x, cl=False, ends=True):
+    def head(self, x, cl=False, im2col=False):
         """conv + GELU of a norm-free frequency layer as (B * Fr, C, T) samples, the DConv branch's input (channels-last trunk);
-        cl: as (B, Fr, T, C) channels-last bf16 samples (the fused channels-last DConv kernels)."""
-        if cl and ends and x.shape[1] <= 2 and x.shape[2] % 4 == 0 and not x.requires_grad:
+        cl: as (B, Fr, T, C) channels-last bf16 samples (the fused channels-last DConv kernels), im2col: those from one GEMM."""
+        if im2col:
             return clchain.head_conv(x, self.conv)          # 16-channel GEMM over the im2col of the 2-channel spectrogram
         y = ops.conv2d(x, self.conv.weight, self.conv.bias, (self.stride, 1), (self.pad, 0), out_bf16=ENC_Z16 or cl)
         if cl:
@@ -432,6 +380,53 @@ class _HDecLayer(nn.Module):
         return z, y
 
 
+class _Route(NamedTuple):
+    """Which kernels one forward takes (HDemucs._route): decided once per call, read everywhere else."""
+    Lc: int            # leading frequency layers on the channels-last bf16 trunk (0: none)
+    Lt: int            # ... and time layers (0 or Lc)
+    dcl: tuple         # dcl[i], i < Lc: the DConv branch of frequency layer i runs on the fused channels-last kernels (cldconv.py)
+    tdcl: tuple        # tdcl[i], i < Lt: ... of time layer i
+    im2col: bool       # frequency layer 0's convolution + GELU as one GEMM over the im2col of the 2-channel spectrum
+    fm: bool           # ... built straight from a frame-major spectrum, which the synthesis side takes too
+    two: bool          # the time branch on its own stream
+    cl_tail: bool      # the frequency decoder's last transposed convolution runs inside the channels-last decoder node
+    cl_tail_t: bool    # ... the time decoder's
+
+
+def _cl_geometry(enc, dec, freq):
+    """An encoder layer and its decoder layer are norm-free layers of the standard geometry the channels-last trunk is written for:
+    conv 8 / 4 pad 2 ((8, 1) along Fr when freq), 1x1 encoder rewrite, 3x3 decoder rewrite, channel counts in whole 16-channel K steps."""
+    return (enc.freq == freq and not enc.empty and enc.context == 0 and enc.kernel_size == 8 and enc.stride == 4 and enc.pad == 2
+            and not isinstance(enc.norm1, nn.GroupNorm) and not isinstance(enc.norm2, nn.GroupNorm)
+            and enc.conv.out_channels % 16 == 0
+            and dec.freq == freq and not dec.empty and dec.context == 1 and dec.kernel_size == 8 and dec.stride == 4 and dec.pad == 2
+            and not isinstance(dec.norm1, nn.GroupNorm) and not isinstance(dec.norm2, nn.GroupNorm))
+
+
+class _Streams:
+    """The main stream and, when `two`, the time branch's own; with `two` false every method is a no-op on the current stream."""
+
+    def __init__(self, two, device):
+        self.main = torch.cuda.current_stream() if two else None
+        self.time = _time_stream(device) if two else None
+
+    def on_time(self):
+        """Context: what is enqueued inside goes to the time stream."""
+        return torch.cuda.stream(self.time) if self.time is not None else contextlib.nullcontext()
+
+    def time_takes(self, t):
+        """The time stream waits for what main has enqueued and reads t from then on."""
+        if self.time is not None:
+            self.time.wait_stream(self.main)
+            t.record_stream(self.time)
+
+    def main_takes(self, t):
+        """The reverse: main waits for the time stream and reads t."""
+        if self.time is not None:
+            self.main.wait_stream(self.time)
+            t.record_stream(self.main)
+
+
 class HDemucs(nn.Module):
     def __init__(self, sources, audio_channels=2, channels=48, growth=2, nfft=4096, depth=6, freq_emb=0.2,
                  emb_scale=10, emb_smooth=True, kernel_size=8, time_stride=2, stride=4, context=1,
@@ -533,19 +528,12 @@ class HDemucs(nn.Module):
 
     def _cl_layers(self, le, device):
         """How many leading frequency layers take the channels-last bf16 trunk (0: none).  Conditions: bf16 arithmetic mode, whole
-        256-frame tiles, norm-free layers of the standard geometry (conv (8, 1) / 4 pad 2, 1x1 encoder rewrite, 3x3 decoder rewrite),
-        channel counts in whole 16-channel K steps."""
+        256-frame tiles, norm-free layers of the standard geometry (_cl_geometry), row counts divisible by the stride."""
         if not CL_TRUNK or ops.GEMM_PREC != 2 or device.type != "cuda" or le % 256 or le <= 0:
             return 0
         n, rows = 0, self.nfft // 2
         for i, enc in enumerate(self.freq_encoder):
-            dec = self.freq_decoder[self.depth - 1 - i]
-            ok = (enc.freq and not enc.empty and enc.context == 0 and enc.kernel_size == 8 and enc.stride == 4 and enc.pad == 2
-                  and not isinstance(enc.norm1, nn.GroupNorm) and not isinstance(enc.norm2, nn.GroupNorm)
-                  and enc.conv.out_channels % 16 == 0 and rows % 4 == 0
-                  and dec.freq and not dec.empty and dec.context == 1 and dec.kernel_size == 8 and dec.stride == 4 and dec.pad == 2
-                  and not isinstance(dec.norm1, nn.GroupNorm) and not isinstance(dec.norm2, nn.GroupNorm))
-            if not ok:
+            if not (_cl_geometry(enc, self.freq_decoder[self.depth - 1 - i], True) and rows % 4 == 0):
                 break
             n, rows = n + 1, rows // 4
         return n if 2 <= n < self.depth else 0
@@ -555,41 +543,74 @@ class HDemucs(nn.Module):
         norm-free geometry and every level is whole 256-position tiles."""
         if not CL_TIME or Lc == 0 or len(self.time_encoder) <= Lc or length % (4 ** Lc * 256):
             return 0
-        for i in range(Lc):
-            enc, dec = self.time_encoder[i], self.time_decoder[len(self.time_decoder) - 1 - i]
-            ok = (not enc.freq and not enc.empty and enc.context == 0 and enc.kernel_size == 8 and enc.stride == 4 and enc.pad == 2
-                  and not isinstance(enc.norm1, nn.GroupNorm) and not isinstance(enc.norm2, nn.GroupNorm)
-                  and enc.conv.out_channels % 16 == 0
-                  and not dec.freq and not dec.empty and dec.context == 1 and dec.kernel_size == 8 and dec.stride == 4 and dec.pad == 2
-                  and not isinstance(dec.norm1, nn.GroupNorm) and not isinstance(dec.norm2, nn.GroupNorm))
-            if not ok:
-                return 0
-        return Lc
+        nt = len(self.time_decoder)
+        return Lc if all(_cl_geometry(self.time_encoder[i], self.time_decoder[nt - 1 - i], False) for i in range(Lc)) else 0
 
-    def _time_encoder_step(self, idx, Lt, B, saved_t, lengths_t, xt, samp_t, len_t):
-        """Layer idx of the time encoder (on whatever stream is current).  Returns (xt, samp_t, len_t, inject): inject = the tensor the
+    def _route(self, Cin, length, device):
+        """The path a clip of (Cin, length) takes under the present flags and arithmetic mode: every routing clause of forward lives here
+        (or in _cl_layers / _cl_layers_time / _data_parallel, which only this calls).  Not cached: tests and bench.py flip the flags and
+        the mode on a live model."""
+        Lc = self._cl_layers(math.ceil(length / self.hop_length), device)
+        Lt = self._cl_layers_time(length, device, Lc)
+        dcl = tuple(CL_DCONV and self.freq_encoder[i].dconv.cl_ok() for i in range(Lc))
+        # time layer i sees the clip after its own convolution: length / 4 ** (i + 1) positions
+        tdcl = [CL_DCONV and CL_TIME_DCONV and self.time_encoder[i].dconv.cl_ok(length // 4 ** (i + 1)) for i in range(Lt)]
+        if Lt:
+            # layer 0 has channels-last samples only from the im2col head (one audio channel; forward refuses an input that requires a
+            # gradient, the head's other condition); else head_t runs and the layer stays channel-major
+            tdcl[0] = tdcl[0] and CL_ENDS and Cin == 1
+        # Frame-major ends (round 6): on the channels-last trunk the spectrum never takes torch.stft's [bin][frame] layout, which costs
+        # the FFT kernels 8-byte pieces of 128-byte lines on both sides of the U-Net.  _spec stores frame-major (full lines); the first
+        # convolution's im2col operand is built straight from it with the standardisation folded in (no separate affine pass); the
+        # de-standardisation behind the last transposed convolution is fused with the layout change to frame-major, which _ispec reads.
+        im2col = Lc > 0 and dcl[0] and CL_ENDS and Cin == 1 and (self.nfft // 2) % 4 == 0      # (the spectrum carries no gradient)
+        fm = FM_ENDS and im2col and len(self.sources) == 1
+        # ON again since the GroupNorm statistics are stored per chunk (DESIGN.md 4.10: with epilogue statistics -- a zero fill followed by
+        # fp64 atomics -- one clip of a batch came out 1e-3 wrong in ~3 % of forward passes whenever this stream ran beside the main one;
+        # scripts/probes/batch_invariance_loop.py is the acceptance test: 0 of 200).
+        two = TWO_STREAMS and device.type == "cuda" and Lt > 0 and not _data_parallel()
+
+        def cl_tail(last):         # the (C -> 1 - 2 audio channel) last transposed convolution as an im2col GEMM inside the node
+            return CL_ENDS and last.last and last.conv_tr.out_channels <= 2
+        return _Route(Lc, Lt, dcl, tuple(tdcl), bool(im2col), bool(fm), bool(two), bool(Lc and cl_tail(self.freq_decoder[-1])),
+                      bool(Lt and cl_tail(self.time_decoder[-1])))
+
+    def _analysis(self, input, fm, st):
+        """Standardise the waveform (the time branch's input, handed to its stream) and take the STFT.  Returns xt, the spectrum as
+        (x, None) complex-as-channels or (None, (spec_fm, coef_a, coef_b)) frame-major, and the statistics (mean, std, meant, stdt)."""
+        B, Cin, length = input.shape
+        hl, Fq = self.hop_length, self.nfft // 2
+        le, pad = math.ceil(length / hl), hl // 2 * 3
+        xt, meant, stdt = nnops.row_standardize(input, 1e-5)        # over (C, T) per clip
+        st.time_takes(xt)
+        if fm:
+            spec_fm = stft.stft(input.reshape(B * Cin, length), self.nfft, hl, mode="complex_fm", normalized=True,
+                                bins=Fq, frame0=2, frames_out=le, extra_pad=(pad, pad + le * hl - length)).detach()    # (B, le, Fq, 2)
+            mean, std, coef_a, coef_b = nnops.row_moments(spec_fm, 1e-5)                                             # over (C, Fr, T) per clip
+            return xt, None, (spec_fm, coef_a, coef_b), (mean, std, meant, stdt)
+        # _spec + _magnitude: STFT straight into complex-as-channels (B, 2*Cin, nfft/2, le)
+        cac = stft.stft(input.reshape(B * Cin, length), self.nfft, hl, mode="cac", normalized=True,
+                        bins=Fq, frame0=2, frames_out=le, extra_pad=(pad, pad + le * hl - length))
+        x = cac.view(B, Cin, 2, Fq, le).reshape(B, Cin * 2, Fq, le)
+        x, mean, std = nnops.row_standardize(x.detach(), 1e-5)      # over (C, Fr, T) per clip, unbiased std
+        return xt, x, None, (mean, std, meant, stdt)
+
+    def _encode_time(self, idx, r, B, length, saved_t, lengths_t, xt, samp_t):
+        """Layer idx of the time encoder (on whatever stream is current).  Returns (xt, samp_t, inject): inject = the tensor the
         frequency branch's layer reads (the empty time layer's output), else None."""
         inject = None
         tenc = self.time_encoder[idx]
-        if idx < Lt:
+        if idx < r.Lt:
             # time branch on the channels-last trunk: as the frequency layers, with A = 1 and the stride along positions
-            lengths_t.append(len_t)
-            len_t = len_t // 4
-            tdcl = CL_DCONV and CL_TIME_DCONV and tenc.dconv.cl_ok(len_t)      # len_t: this layer's clip length after its convolution
+            lengths_t.append(length // 4 ** idx)
             if idx == 0:
-                if tdcl and CL_ENDS and xt.shape[1] == 1 and not xt.requires_grad:
+                if r.tdcl[0]:
                     samp_t = clchain.head_conv(xt.unsqueeze(2), tenc.conv, along_b=True)     # (B, 1, L / 4, C) channels-last
                 else:
-                    samp_t, tdcl = tenc.head_t(xt), False
-            dt_ = tenc.dconv.forward_cl(samp_t) if tdcl else tenc.dconv(samp_t)
-            if _XSUB and _CUR[0] is not None and _XIDX in (-1, idx):          # dev: the hazard hunt's sub-layer serialisation points
-                if _XSUB & 1:
-                    _CUR[0].wait_stream(_CUR[1])          # main waits for the time stream's DConv
-                if _XSUB & 2:
-                    _CUR[1].wait_stream(_CUR[0])          # the time stream's stride-4 node waits for what main has enqueued
-            if idx < Lt - 1:
-                nxt_t = CL_DCONV and CL_TIME_DCONV and self.time_encoder[idx + 1].dconv.cl_ok(len_t // 4)
-                et, samp_t = clchain.enc_mid(dt_, tenc.rewrite, self.time_encoder[idx + 1].conv, None, B, y_cl=nxt_t, fold=True)
+                    samp_t = tenc.head_t(xt)
+            dt_ = tenc.dconv.forward_cl(samp_t) if r.tdcl[idx] else tenc.dconv(samp_t)
+            if idx < r.Lt - 1:
+                et, samp_t = clchain.enc_mid(dt_, tenc.rewrite, self.time_encoder[idx + 1].conv, None, B, y_cl=r.tdcl[idx + 1], fold=True)
             else:
                 et, xt = clchain.enc_tail(dt_, tenc.rewrite, B)
                 xt = xt.squeeze(2)
@@ -606,80 +627,29 @@ class HDemucs(nn.Module):
                 saved_t.append(xt)
             else:
                 inject = xt
-        return xt, samp_t, len_t, inject
+        return xt, samp_t, inject
 
-    def forward(self, input):
-        if input.ndim != 3 or input.shape[1] != self.audio_channels:
-            raise ValueError(f"expected (batch, {self.audio_channels}, frames), got {tuple(input.shape)}")
-        ops._req(input, "input")
-        B, Cin, length = input.shape
-        hl = self.hop_length
-        le = math.ceil(length / hl)
-        pad = hl // 2 * 3
-        if input.requires_grad:
-            raise NotImplementedError("HDemucs: gradient w.r.t. the input waveform is not on the reference's path")
+    def _encode(self, r, st, x, head, xt, B, length, le):
+        """Both encoders, layer by layer with the time layer first.  Returns the innermost frequency layer's output and the skips and
+        lengths of both branches."""
         saved, saved_t, lengths, lengths_t = [], [], [], []
-        Lc = self._cl_layers(le, input.device)
-        Lt = self._cl_layers_time(length, input.device, Lc)
         samp = samp_t = None
-        len_t = length
-        import contextlib
-        # ON again since the GroupNorm statistics are stored per chunk (with epilogue statistics -- a zero fill followed by
-        # fp64 atomics -- one clip of a batch came out 1e-3 wrong in ~3 % of forward passes whenever this stream ran beside the main one;
-        # scripts/probes/batch_invariance_loop.py is the acceptance test: 0 of 200).
-        two = TWO_STREAMS and input.is_cuda and Lt > 0 and not _data_parallel()
-        xt, meant, stdt = nnops.row_standardize(input, 1e-5)        # over (C, T) per clip
-        if two:
-            main_s, time_s = torch.cuda.current_stream(), _time_stream(input.device)
-            time_s.wait_stream(main_s)
-            xt.record_stream(time_s)
-        tctx = (lambda: torch.cuda.stream(time_s)) if two else contextlib.nullcontext
-        _CUR[0], _CUR[1] = (main_s, time_s) if two else (None, None)
-        Fq = self.nfft // 2
-        # Frame-major ends (round 6): on the channels-last trunk the spectrum never takes torch.stft's [bin][frame] layout, which costs
-        # the FFT kernels 8-byte pieces of 128-byte lines on both sides of the U-Net.  _spec stores frame-major (full lines); the first
-        # convolution's im2col operand is built straight from it with the standardisation folded in (no separate affine pass); the
-        # de-standardisation behind the last transposed convolution is fused with the layout change to frame-major, which _ispec reads.
-        fm = (FM_ENDS and Lc > 0 and CL_ENDS and CL_DCONV and Cin == 1 and Fq % 4 == 0 and len(self.sources) == 1
-              and self.freq_encoder[0].dconv.cl_ok())
-        if fm:
-            spec_fm = stft.stft(input.reshape(B * Cin, length), self.nfft, hl, mode="complex_fm", normalized=True,
-                                bins=Fq, frame0=2, frames_out=le, extra_pad=(pad, pad + le * hl - length)).detach()    # (B, le, Fq, 2)
-            mean, std, coef_a, coef_b = nnops.row_moments(spec_fm, 1e-5)                                             # over (C, Fr, T) per clip
-            x = None
-        else:
-            # _spec + _magnitude: STFT straight into complex-as-channels (B, 2*Cin, nfft/2, le)
-            cac = stft.stft(input.reshape(B * Cin, length), self.nfft, hl, mode="cac", normalized=True,
-                            bins=self.nfft // 2, frame0=2, frames_out=le, extra_pad=(pad, pad + le * hl - length))
-            x = cac.view(B, Cin, 2, Fq, le).reshape(B, Cin * 2, Fq, le)
-            x, mean, std = nnops.row_standardize(x.detach(), 1e-5)      # over (C, Fr, T) per clip, unbiased std
         for idx, encode in enumerate(self.freq_encoder):
             lengths.append(le if x is None else x.shape[-1])
             inject = None
             if idx < len(self.time_encoder):
-                if two and (_XSYNC & 2) and _XIDX in (-1, idx):
-                    time_s.wait_stream(main_s)
-                with tctx():
-                    xt, samp_t, len_t, inject = self._time_encoder_step(idx, Lt, B, saved_t, lengths_t, xt, samp_t, len_t)
-                if two and (_XSYNC & 1) and _XIDX in (-1, idx):
-                    main_s.wait_stream(time_s)
-                if two and inject is not None:                 # the merge: layer 4 of the frequency branch reads the time branch
-                    main_s.wait_stream(time_s)
-                    inject.record_stream(main_s)
-            if idx < Lc:
+                with st.on_time():
+                    xt, samp_t, inject = self._encode_time(idx, r, B, length, saved_t, lengths_t, xt, samp_t)
+                if inject is not None:                 # the merge: layer 4 of the frequency branch reads the time branch
+                    st.main_takes(inject)
+            if idx < r.Lc:
                 # channels-last trunk: the DConv branch on (B * Fr, C, T) samples, everything between two branches in one node
-                dcl = CL_DCONV and encode.dconv.cl_ok()      # this layer's DConv branch runs on channels-last samples
                 if idx == 0:
-                    samp = clchain.head_conv_fm(spec_fm, coef_a, coef_b, encode.conv) if fm else encode.head(x, cl=dcl, ends=CL_ENDS)
-                d = encode.dconv.forward_cl(samp) if dcl else encode.dconv(samp)
-                if getattr(self, "_dbg", None) is not None and not dcl:        # dev: per-clip checksums around the channel-major DConv branches
-                    csn = lambda t: t.float().abs().reshape(B, -1).sum(1) if t.is_contiguous() else t.float().abs().contiguous().reshape(B, -1).sum(1)
-                    self._dbg.setdefault("samp", {})[idx] = csn(samp)
-                    self._dbg.setdefault("d", {})[idx] = csn(d)
-                if idx < Lc - 1:
+                    samp = clchain.head_conv_fm(*head, encode.conv) if r.fm else encode.head(x, cl=r.dcl[0], im2col=r.im2col)
+                d = encode.dconv.forward_cl(samp) if r.dcl[idx] else encode.dconv(samp)
+                if idx < r.Lc - 1:
                     emb_rows = self.freq_emb.table() * self.freq_emb_scale if (idx == 0 and self.freq_emb is not None) else None
-                    nxt = CL_DCONV and self.freq_encoder[idx + 1].dconv.cl_ok()
-                    e, samp = clchain.enc_mid(d, encode.rewrite, self.freq_encoder[idx + 1].conv, emb_rows, B, y_cl=nxt)
+                    e, samp = clchain.enc_mid(d, encode.rewrite, self.freq_encoder[idx + 1].conv, emb_rows, B, y_cl=r.dcl[idx + 1])
                 else:
                     e, x = clchain.enc_tail(d, encode.rewrite, B)
                 saved.append(e)
@@ -694,58 +664,53 @@ class HDemucs(nn.Module):
                 emb = self.freq_emb.table().t()[None, :, :, None]
                 x = nnops.add(x, emb, self.freq_emb_scale)
             saved.append(x)
-        x = ops.zeros(x.shape, x.device)
-        xt = ops.zeros(x.shape, x.device)
-        if getattr(self, "_dbg", None) is not None:        # dev (scripts/probes/first_wrong_tensor.py): per-clip checksums of the skips
-            cs = lambda t: t.float().abs().sum(dim=tuple(range(1, t.dim()))) if t.shape[0] == B else t.float().abs().view(B, -1).sum(1)
-            self._dbg["saved"] = [cs(t) for t in saved]
-            self._dbg["x"] = cs(x)
-            with tctx():
-                self._dbg["saved_t"] = [cs(t) for t in saved_t]
+        return x, saved, saved_t, lengths, lengths_t
+
+    def _decoder_node(self, x, saved, layers, tail, fold=False, length=None):
+        """The trunk layers of a decoder (`layers`, down to layer 0) in one channels-last node on their skips, popped from `saved`; fold:
+        the time decoder, x (B, C, L), cropped to `length`.  tail: the last transposed convolution runs inside the node; else the node
+        returns that layer's input and the generic channel-major kernels follow."""
+        skips = [saved.pop(-1) for _ in layers]
+        if fold:
+            x = x.unsqueeze(2)
+        if tail:
+            x = clchain.freq_decoder(x, skips, layers, fold=fold, tail=True)
+            return x.squeeze(2) if fold else x
+        last = layers[-1]
+        y = clchain.freq_decoder(x, skips, layers, fold=fold)
+        if fold:
+            x = ops.conv_transpose1d(y.squeeze(2), last.conv_tr.weight, last.conv_tr.bias, last.stride, 1, last.pad, length)
+        else:
+            full = (y.shape[2] - 1) * last.stride + last.kernel_size
+            x = ops.conv_transpose2d(y, last.conv_tr.weight, last.conv_tr.bias, (last.stride, 1), (1, 1), (last.pad, 0),
+                                     (full - 2 * last.pad, y.shape[3]))
+        return x if last.last else nnops.gelu(x)
+
+    def _decode(self, r, st, shape, device, saved, saved_t, lengths, lengths_t, length):
+        """Both decoders from zero tensors of the innermost `shape`, layer by layer with the frequency layer first; the layers below
+        r.Lc / r.Lt run as one node each (_decoder_node) when the loop reaches the first of them."""
+        x = ops.zeros(shape, device)
+        xt = ops.zeros(shape, device)
         offset = self.depth - len(self.time_decoder)
         fadd = tadd = False                      # the previous layer already added this layer's skip (activation_add)
         for idx, decode in enumerate(self.freq_decoder):
             j = self.depth - 1 - idx
-            if j < Lc:
-                pre = None
-                lengths.pop(-1)
-                if j == Lc - 1:                   # layers Lc - 1 .. 0 in one node; the last transposed convolution (C -> 2 audio) stays channel-major
-                    skips = [saved.pop(-1) for _ in range(Lc)]
-                    last = self.freq_decoder[-1]
-                    if CL_ENDS and last.last and last.conv_tr.out_channels <= 2:
-                        x = clchain.freq_decoder(x, skips, list(self.freq_decoder[idx:]), tail=True)
-                    else:
-                        y0 = clchain.freq_decoder(x, skips, list(self.freq_decoder[idx:]))
-                        full = (y0.shape[2] - 1) * last.stride + last.kernel_size
-                        x = ops.conv_transpose2d(y0, last.conv_tr.weight, last.conv_tr.bias, (last.stride, 1), (1, 1), (last.pad, 0),
-                                                 (full - 2 * last.pad, y0.shape[3]))
-                        if not last.last:
-                            x = nnops.gelu(x)
-            else:
+            pre = None
+            if j >= r.Lc:
                 skip = saved.pop(-1)
-                x, pre = decode(x, skip, lengths.pop(-1), next_skip=saved[-1] if (saved and j != Lc) else None, skip_added=fadd)
+                x, pre = decode(x, skip, lengths.pop(-1), next_skip=saved[-1] if (saved and j != r.Lc) else None, skip_added=fadd)
                 fadd = decode.fused_next_add
-            if idx >= offset and two and (self.time_decoder[idx - offset].empty):
-                time_s.wait_stream(main_s)                     # the empty time layer reads the frequency branch's layer-4 tensor
-                pre.record_stream(time_s)
-            if two and (_XSYNC & 8):
-                time_s.wait_stream(main_s)
-            with tctx():
-                if idx >= offset and j < Lt:
-                    length_t = lengths_t.pop(-1)
-                    if j == Lt - 1:
-                        skips_t = [saved_t.pop(-1) for _ in range(Lt)]
-                        lastt = self.time_decoder[-1]
-                        if CL_ENDS and lastt.last and lastt.conv_tr.out_channels <= 2:
-                            xt = clchain.freq_decoder(xt.unsqueeze(2), skips_t, list(self.time_decoder[idx - offset:]), fold=True, tail=True).squeeze(2)
-                        else:
-                            yt0 = clchain.freq_decoder(xt.unsqueeze(2), skips_t, list(self.time_decoder[idx - offset:]), fold=True)
-                            xt = ops.conv_transpose1d(yt0.squeeze(2), lastt.conv_tr.weight, lastt.conv_tr.bias, lastt.stride, 1, lastt.pad,
-                                                      lengths_t[0] if lengths_t else length_t)
-                            if not lastt.last:
-                                xt = nnops.gelu(xt)
-                elif idx >= offset:
-                    tdec = self.time_decoder[idx - offset]
+            elif j == r.Lc - 1:
+                x = self._decoder_node(x, saved, list(self.freq_decoder[idx:]), r.cl_tail)
+            if idx < offset:
+                continue
+            tdec = self.time_decoder[idx - offset]
+            if tdec.empty:
+                st.time_takes(pre)                     # the empty time layer reads the frequency branch's layer-4 tensor
+            with st.on_time():
+                if j == r.Lt - 1:
+                    xt = self._decoder_node(xt, saved_t, list(self.time_decoder[idx - offset:]), r.cl_tail_t, fold=True, length=length)
+                elif j >= r.Lt:
                     length_t = lengths_t.pop(-1)
                     if tdec.empty:
                         xt, _ = tdec(pre[:, :, 0], None, length_t)
@@ -754,14 +719,14 @@ class HDemucs(nn.Module):
                         skip_t = saved_t.pop(-1)
                         xt, _ = tdec(xt, skip_t, length_t, next_skip=saved_t[-1] if saved_t else None, skip_added=tadd)
                         tadd = tdec.fused_next_add
-            if two and (_XSYNC & 4):
-                main_s.wait_stream(time_s)
-        if two:
-            main_s.wait_stream(time_s)
-            xt.record_stream(main_s)
-            if _XSYNC & 16:
-                torch.cuda.synchronize()
-        S = len(self.sources)
+        st.main_takes(xt)
+        return x, xt
+
+    def _synthesis(self, x, xt, stats, fm, B, Cin, length):
+        """De-standardise both branches, inverse STFT, add: -> (B, S, Cin, length)."""
+        mean, std, meant, stdt = stats
+        hl, Fq, S = self.hop_length, self.nfft // 2, len(self.sources)
+        le, pad = math.ceil(length / hl), hl // 2 * 3
         if S != 1:
             # Several sources: the last transposed convolutions are the generic ones (out_channels > 2) and leave x as
             # (B, S * Cin * 2, Fq, le) in (source, channel, re / im) order, xt as (B, S * Cin, length).  The G = S * Cin rows of a clip
@@ -784,3 +749,17 @@ class HDemucs(nn.Module):
                             length=length).view(B, S, Cin, length)
         xt = nnops.row_affine(xt.reshape(B, -1), stdt, meant).view(B, S, -1, length)
         return nnops.add(xt.reshape(B, S * Cin, 1, length), xo.reshape(B, S * Cin, 1, length)).view(B, S, Cin, length)
+
+    def forward(self, input):
+        if input.ndim != 3 or input.shape[1] != self.audio_channels:
+            raise ValueError(f"expected (batch, {self.audio_channels}, frames), got {tuple(input.shape)}")
+        ops._req(input, "input")
+        if input.requires_grad:
+            raise NotImplementedError("HDemucs: gradient w.r.t. the input waveform is not on the reference's path")
+        B, Cin, length = input.shape
+        r = self._route(Cin, length, input.device)
+        st = _Streams(r.two, input.device)
+        xt, x, head, stats = self._analysis(input, r.fm, st)
+        x, saved, saved_t, lengths, lengths_t = self._encode(r, st, x, head, xt, B, length, math.ceil(length / self.hop_length))
+        x, xt = self._decode(r, st, x.shape, x.device, saved, saved_t, lengths, lengths_t, length)
+        return self._synthesis(x, xt, stats, r.fm, B, Cin, length)

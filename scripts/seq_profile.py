@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from remfx_amd import _lib, ops
 import bench
+from launch_trace import wrap_library
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 dev = torch.device("cuda:0")
@@ -27,9 +28,7 @@ def site():
     return ">".join(out[-5:])
 
 
-def wrap(name):
-    fn = getattr(L, name)
-
+def wrap(name, fn):
     def timed(*args):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         rc = fn(*args)
@@ -67,9 +66,7 @@ opt = model.configure_optimizers()["optimizer"]
 data = bench.synthetic_batch(B, 0, dev)
 for it in range(3):
     if it == 2:
-        for name in _lib.SIGNATURES:
-            if name not in ("rfx_abi_version", "rfx_gemm_pick_r", "rfx_gemm_fwd_variant", "rfx_dconv_layer_ok"):
-                setattr(L, name, wrap(name))
+        wrap_library(wrap, queries=False)
         torch.cuda.synchronize(); T0 = time.perf_counter()
     opt.zero_grad()
     loss = model.training_step(data, 0)
