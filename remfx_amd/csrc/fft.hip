@@ -33,8 +33,8 @@
 #include <stdlib.h>
 #ifndef RFX_FFT_PAIR_OCC
 // waves per SIMD the pair-loss kernel is compiled for where three workgroups fit a CU's LDS (n_fft 2048 / 4096; n_fft 1024 needs
-// 53 KB): 3 = 168 registers + 44 spilled instead of 220, MRSTFT forward + backward at 64 clips 7.80 -> 7.23 ms (A/B:
-// scripts/build_abl.py fft RFX_FFT_PAIR_OCC 2, scripts/perf_loss.py)
+// 53 KB): 3 = 168 registers instead of 220, MRSTFT forward + backward at 64 clips 7.80 -> 7.23 ms (A/B: scripts/build_abl.py fft
+// RFX_FFT_PAIR_OCC 2, scripts/perf_loss.py) when 44 registers still spilled; nothing spills since the window moved to LDS
 #define RFX_FFT_PAIR_OCC 3
 #endif
 #include <mutex>
@@ -172,19 +172,20 @@ template <int LOGN>
 struct FftState {
   const v2f* twB;                                        // LDS, + (u & 15)
   const v2f* twAs;                                       // LDS, + u (RA >= 4)
+  const v2f *twB0, *twAs0;                               // the same tables without the thread's offset (fft_core<LOGN, true> adds it per call)
   v2f twA0;                                              // RA = 2: W_512^u; butterfly h uses W_512^(u + 32 h) = twA0 W_16^h
 };
-template <int LOGN>
+template <int LOGN, bool HALF = true>                      // HALF: the split / merge table e^{-i pi k / NC} (the pair-loss kernel has no such step)
 struct FftTables {
-  v2f twH[FftCfg<LOGN>::NH];
+  v2f twH[HALF ? FftCfg<LOGN>::NH : 1];
   v2f tw256t[256];
   v2f twAs[FftCfg<LOGN>::RA >= 4 ? 256 : 1];
 };
-template <int LOGN>
-__device__ __forceinline__ void fft_setup(const FftArgs& a, FftTables<LOGN>& tb, FftState<LOGN>& st) {
+template <int LOGN, bool HALF>
+__device__ __forceinline__ void fft_setup(const FftArgs& a, FftTables<LOGN, HALF>& tb, FftState<LOGN>& st) {
   typedef FftCfg<LOGN> K;
   const int tid = threadIdx.x, u = tid & (K::T - 1);
-  {                                                        // all loads first: a load -> wait -> LDS write loop costs a round trip each
+  if (HALF) {                                                      // all loads first: a load -> wait -> LDS write loop costs a round trip each
     constexpr int NI = (K::NH + 255) / 256;
     v2f tmp[NI];
 #pragma unroll
@@ -196,16 +197,24 @@ __device__ __forceinline__ void fft_setup(const FftArgs& a, FftTables<LOGN>& tb,
   if (K::RA >= 4) tb.twAs[tid] = a.tables[256 + tid];
   st.twB = tb.tw256t + (u & 15);
   st.twAs = tb.twAs + u;
+  st.twB0 = tb.tw256t;
+  st.twAs0 = tb.twAs;
   st.twA0 = a.tables[256 + (K::RA == 2 ? u : 0)];
 }
 
 // The three passes on one batch: z = the thread's 16 points i = u + T n (n = 0..15) of frame fl.  Result: Z[k] in layout E3.
 // Callers put a barrier before the first LDS read of the NEXT use of `data`.
-template <int LOGN>
+// RC: the passes' LDS addresses are recomputed at each call (a few VALU) instead of being carried in a register each across the caller's
+// batch loop -- for the callers that are register-bound at three waves per SIMD (pair loss, fused-gradient synthesis)
+template <int LOGN, bool RC = false>
 __device__ __forceinline__ void fft_core(v2f (&z)[16], v2f* data, const FftState<LOGN>& st, const v2f* wout = nullptr) {
   typedef FftCfg<LOGN> K;
-  const int tid = threadIdx.x, u = tid & (K::T - 1), fl = tid / K::T;
+  int tid = threadIdx.x;
+  if (RC) asm volatile("" : "+v"(tid));
+  const int u = tid & (K::T - 1), fl = tid / K::T;
   v2f* fr = data + fl * K::FS;
+  const v2f* twB = RC ? st.twB0 + (u & 15) : st.twB;
+  const v2f* twAs = RC ? st.twAs0 + u : st.twAs;
   if (K::RA > 1) {
     // pass A: butterfly h works on z[h + NB q], j1 = u + h T;  E1: element (b1 = m, j1) at (j1 / 16) RS1 + 16 m + j1 % 16
     v2f* wA = fr + (u >> 4) * K::RS1 + (u & 15);
@@ -221,7 +230,7 @@ __device__ __forceinline__ void fft_core(v2f (&z)[16], v2f* data, const FftState
         v2f b = st.twA0;
         asm volatile("" : "+v"(b));                      // keeps the eight products out of loop-invariant registers
         w[1] = cmul(b, v2f{CS[h & 7][0], CS[h & 7][1]});
-      } else w[1] = st.twAs[h * K::T];
+      } else w[1] = twAs[h * K::T];
 #pragma unroll
       for (int m = 2; m < K::RA; ++m) w[m] = (m & 1) ? cmul(w[m - 1], w[1]) : cmul(w[m / 2], w[m / 2]);
       wA[h * (K::T / 16) * K::RS1] = z[h + K::NB * fft_slot<K::RA>(0)];
@@ -240,7 +249,7 @@ __device__ __forceinline__ void fft_core(v2f (&z)[16], v2f* data, const FftState
     v2f* wB = fr + (u & 15) * K::RS2 + (u >> 4) * 16;
     wB[0] = z[fft_slot<16>(0)];
 #pragma unroll
-    for (int m = 1; m < 16; ++m) wB[m] = cmul(z[fft_slot<16>(m)], st.twB[16 * m]);
+    for (int m = 1; m < 16; ++m) wB[m] = cmul(z[fft_slot<16>(m)], twB[16 * m]);
   }
   lds_barrier();
 #pragma unroll
@@ -271,7 +280,7 @@ __global__ __launch_bounds__(256, 3) void fft_analysis_kernel(const FftArgs a) {
   if (row >= d.R) return;
   const int tid = threadIdx.x, u = tid & (T - 1), fl = tid / T;
   FftState<LOGN> st;
-  fft_setup<LOGN>(a, tb, st);
+  fft_setup(a, tb, st);
   lds_barrier();                       // the passes read the tables other threads loaded
   const int f_end = d.frame0 + d.frames_out;
   const float* xr = a.x + (int64_t)row * d.T;
@@ -442,7 +451,7 @@ __global__ __launch_bounds__(256, 3) void fft_synthesis_kernel(const FftArgs a) 
   if (row >= d.R) return;
   const int tid = threadIdx.x, u = tid & (T - 1), fl = tid / T;
   FftState<LOGN> st;
-  fft_setup<LOGN>(a, tb, st);
+  fft_setup(a, tb, st);
   lds_barrier();                       // the merge step below reads the table other threads loaded
   // The synthesis window is applied where the inverse transform leaves the registers (pass C): output m of a thread is time index
   // i = mA + RA (mB + 16 m) = samples (2 i, 2 i + 1); its 16 window pairs are frame-independent.  The overlap-add then only sums LDS
@@ -495,14 +504,18 @@ __global__ __launch_bounds__(256, 3) void fft_synthesis_kernel(const FftArgs a) 
     if (!last_walk) own_hi = (int64_t)F1 * d.hop + woff;
   }
   const int f_stop = OWN ? F1 : f_end;                      // frames at and beyond f_stop are not this workgroup's
-  const bool fm = d.mode == RFX_STFT_COMPLEX_FM;           // frame-major spectrum: lanes along bins
+  const bool fm = LG || d.mode == RFX_STFT_COMPLEX_FM;     // frame-major spectrum: lanes along bins (the only layout of the LG source)
   // all loads of the thread's NIT items first (clamped indices, validity applied to the values): a load -> use loop costs one
   // memory round trip per item and batch
   constexpr int NIT = (K::NH * FB + 255) / 256;
   v2f xkv[NIT], xmv[NIT];
   float ykv[NIT], ymv[NIT];                                // loss-gradient source: the target magnitudes of the same cells
   auto item = [&](int it, int& fl2, int& k) -> bool {
-    const int idx = tid + 256 * it;
+    // LG: recomputed at each use -- carried across the frame loop, the items' indices, LDS addresses and 64-bit cell addresses were
+    // spilled and reloaded in every batch (12 - 13 private-memory loads).  The plain synthesis has the registers to carry them, and
+    // recomputing them there cost time (_ispec at n_fft 4096: 328 -> 401 us)
+    int idx = tid + 256 * it;
+    if (LG) asm volatile("" : "+v"(idx));
     const bool act = idx < K::NH * FB;
     const int ii = act ? idx : 0;
     fl2 = fm ? ii / K::NH : ii & (FB - 1);
@@ -533,13 +546,21 @@ __global__ __launch_bounds__(256, 3) void fft_synthesis_kernel(const FftArgs a) 
       int fl2, k;
       item(it, fl2, k);
       const int f2 = fb + fl2;
-      const int fo = f2 < f_stop ? f2 - d.frame0 : 0;
-      xkv[it] = fetch(k, fo);
-      xmv[it] = fetch(NC - k, fo);
-      if (lg) {
-        const int64_t cell0 = ((int64_t)row * FO + fo) * d.bins;
-        ykv[it] = a.lg_ymag[cell0 + (k < d.bins ? k : 0)];
-        ymv[it] = a.lg_ymag[cell0 + (NC - k < d.bins ? NC - k : 0)];
+      if (LG) {
+        // uniform 64-bit base of the batch + a 32-bit lane offset (no lane address is carried from batch to batch); a frame beyond
+        // f_stop reads the batch's first frame instead (any valid cell: its value is dropped by the merge step)
+        const int64_t cb = ((int64_t)row * FO + (fb - d.frame0)) * d.bins;
+        const v2f* xb = reinterpret_cast<const v2f*>(a.x) + cb;
+        const int o = ((f2 < f_stop ? fl2 : 0) * d.bins) & 0x7fffffff;
+        const int k1 = k < d.bins ? k : 0, k2 = NC - k < d.bins ? NC - k : 0;
+        xkv[it] = xb[o + k1];
+        xmv[it] = xb[o + k2];
+        ykv[it] = (a.lg_ymag + cb)[o + k1];
+        ymv[it] = (a.lg_ymag + cb)[o + k2];
+      } else {
+        const int fo = f2 < f_stop ? f2 - d.frame0 : 0;
+        xkv[it] = fetch(k, fo);
+        xmv[it] = fetch(NC - k, fo);
       }
     }
   };
@@ -576,7 +597,7 @@ __global__ __launch_bounds__(256, 3) void fft_synthesis_kernel(const FftArgs a) 
 #pragma unroll
     for (int n = 0; n < 16; ++n) z[n] = data[fl * K::FS + u + T * n];
     lds_barrier();
-    fft_core<LOGN>(z, data, st, wout);
+    fft_core<LOGN, LG>(z, data, st, wout);
     lds_barrier();
     const int nf = min(FB, f_stop - fb0);
     const int span = (nf - 1) * d.hop + N;
@@ -898,7 +919,8 @@ __global__ __launch_bounds__(256, (LOGN == 9 ? 2 : RFX_FFT_PAIR_OCC)) void fft_p
   constexpr int NC = K::NC, T = K::T, FB = K::FB, N = NC;
   constexpr int NIT = (K::NH * FB + 255) / 256;                 // epilogue items per thread
   __shared__ v2f data[FB * K::FS];
-  __shared__ FftTables<LOGN> tb;
+  __shared__ FftTables<LOGN, false> tb;                         // no split table: its room is the window's
+  __shared__ float wtab[N];                                     // the window centred in n_fft, 0 outside it
   __shared__ double part[3][4];
   const rfx_stft_desc& d = a.d;
   const int b = blockIdx.x, xcd = b & 7, qb = b >> 3;
@@ -910,23 +932,27 @@ __global__ __launch_bounds__(256, (LOGN == 9 ? 2 : RFX_FFT_PAIR_OCC)) void fft_p
   FftState<LOGN> st;
   FftArgs fa;
   fa.tables = a.tables;
-  fft_setup<LOGN>(fa, tb, st);
-  lds_barrier();
+  fft_setup(fa, tb, st);
   const int f_end = d.frames_out;
   const float* xr = a.x + (int64_t)row * d.T;
   const float* yr = a.y + (int64_t)row * d.T;
   const int woff = (N - d.win) / 2;
-  float wv[16];
+  // A thread's 16 window values are frame-independent, but held in registers across the batch loop they were spilled and reloaded
+  // from private memory in every transform (at three waves per SIMD the loop has no 16 registers to spare): they are read from an
+  // LDS table at each use instead, base + immediate offset, lanes contiguous.
   {
-    float wl[16];
+    constexpr int NW = N / 256;
+    float wl[NW];
 #pragma unroll
-    for (int n = 0; n < 16; ++n) wl[n] = a.window[min(max(u + T * n - woff, 0), d.win - 1)];
+    for (int j = 0; j < NW; ++j) wl[j] = a.window[min(max(tid + 256 * j - woff, 0), d.win - 1)];
 #pragma unroll
-    for (int n = 0; n < 16; ++n) {
-      const int w0 = u + T * n - woff;
-      wv[n] = ((w0 >= 0) & (w0 < d.win)) ? wl[n] : 0.f;
+    for (int j = 0; j < NW; ++j) {
+      const int w0 = tid + 256 * j - woff;
+      wtab[tid + 256 * j] = ((w0 >= 0) & (w0 < d.win)) ? wl[j] : 0.f;
     }
   }
+  lds_barrier();
+  const float* wv = wtab + u;                                   // wv[T * n]: the window at point u + T n
   const int shift = d.n_fft / 2;
   // workgroup-uniform: all 2 FB frames of the batch inside the signal -> plain loads, issued before the preceding epilogue
   auto batch_fast = [&](int fb0) -> bool {
@@ -934,17 +960,21 @@ __global__ __launch_bounds__(256, (LOGN == 9 ? 2 : RFX_FFT_PAIR_OCC)) void fft_p
     return (fb0 + 2 * FB <= f_end) & (pb0 - shift >= 0) & (pb0 + (int64_t)(2 * FB - 1) * d.hop + N - 1 - shift < (int64_t)d.T);
   };
   v2f z[16];
-  auto load_fast = [&](const float* sr, int fb0) {
-    const int64_t o = (int64_t)(fb0 + fl) * d.hop - shift + u;
-    const int64_t ob = o + (int64_t)FB * d.hop;
+  auto load_fast = [&](const float* sr, int fb0, bool ok) {
+    // uniform 64-bit bases + one non-negative 32-bit lane offset: no 64-bit lane address is carried from batch to batch
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));                                // recomputed from the thread index at each use
+    const int vo = ok ? ((t / T) * d.hop + (t & (T - 1))) & 0x7fffffff : 0;
+    const float* pa = ok ? sr + ((int64_t)fb0 * d.hop - shift) : reinterpret_cast<const float*>(a.tables);
+    const float* pb = ok ? pa + (int64_t)FB * d.hop : pa;
 #pragma unroll
-    for (int n = 0; n < 16; ++n) z[n] = v2f{sr[o + T * n], sr[ob + T * n]};
+    for (int n = 0; n < 16; ++n) z[n] = v2f{pa[vo + T * n], pb[vo + T * n]};
   };
   // one signal's 2 FB frames: window (fast) or map + stage (edges), three passes -> Z in layout E3
   auto transform = [&](const float* sr, int fb0, bool fast) {
     if (fast) {
 #pragma unroll
-      for (int n = 0; n < 16; ++n) z[n] = z[n] * wv[n];
+      for (int n = 0; n < 16; ++n) z[n] = z[n] * wv[T * n];
     } else {
 #pragma unroll 1
       for (int n = 0; n < 16; ++n) {
@@ -967,17 +997,17 @@ __global__ __launch_bounds__(256, (LOGN == 9 ? 2 : RFX_FFT_PAIR_OCC)) void fft_p
       for (int n = 0; n < 16; ++n) z[n] = data[fl * K::FS + u + T * n];
       lds_barrier();
     }
-    fft_core<LOGN>(z, data, st);
+    fft_core<LOGN, true>(z, data, st);
     lds_barrier();
   };
   bool fast = f_first < f_end && batch_fast(f_first);
-  if (fast) load_fast(xr, f_first);
+  load_fast(xr, f_first, fast);
   double accA = 0.0, accB = 0.0, accC = 0.0;
   for (int g = 0; g < a.nbatch; ++g) {
     const int fb0 = f_first + g * 2 * FB;
     if (fb0 >= f_end) break;                                   // workgroup-uniform
     transform(xr, fb0, fast);
-    if (fast) load_fast(yr, fb0);                              // the target's loads fly over the prediction's epilogue
+    load_fast(yr, fb0, fast);                              // the target's loads fly over the prediction's epilogue
     float px[NIT][2];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -992,17 +1022,19 @@ __global__ __launch_bounds__(256, (LOGN == 9 ? 2 : RFX_FFT_PAIR_OCC)) void fft_p
       const v2f Sb = v2f{Dm.y, -Dm.x};                            // S_b = -i Dm
       px[it][0] = fmaxf(rfx_pow2(Sa.x, Sa.y), a.eps);
       px[it][1] = fmaxf(rfx_pow2(Sb.x, Sb.y), a.eps);
-      if (a.xspec && act) {
+      if (a.xspec && act) {                                    // uniform 64-bit base + 32-bit lane offset (no lane address is carried)
         const int f2 = fb0 + fl2;
-        if (f2 < f_end) a.xspec[((int64_t)row * d.frames_out + f2) * d.bins + k] = Sa;
-        if (f2 + FB < f_end) a.xspec[((int64_t)row * d.frames_out + f2 + FB) * d.bins + k] = Sb;
+        v2f* xs = a.xspec + ((int64_t)row * d.frames_out + fb0) * d.bins;
+        const int off = (fl2 * d.bins + k) & 0x7fffffff;
+        if (f2 < f_end) xs[off] = Sa;
+        if (f2 + FB < f_end) (xs + (int64_t)FB * d.bins)[off] = Sb;
       }
       __builtin_amdgcn_sched_barrier(0);                       // one item at a time: interleaving all NIT costs ~120 spilled VGPRs
     }
     lds_barrier();
     transform(yr, fb0, fast);
     fast = (g + 1 < a.nbatch) && (fb0 + 2 * FB < f_end) && batch_fast(fb0 + 2 * FB);
-    if (fast) load_fast(xr, fb0 + 2 * FB);
+    load_fast(xr, fb0 + 2 * FB, fast);
     float fa0 = 0.f, fb1 = 0.f, fc2 = 0.f;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -1024,7 +1056,7 @@ __global__ __launch_bounds__(256, (LOGN == 9 ? 2 : RFX_FFT_PAIR_OCC)) void fft_p
         fa0 += ok ? dd * dd : 0.f;
         fb1 += ok ? py[c] : 0.f;
         fc2 += ok ? fabsf(__builtin_amdgcn_logf(px[it][c]) - __builtin_amdgcn_logf(py[c])) : 0.f;
-        if (a.ymag && ok) a.ymag[((int64_t)row * d.frames_out + f2) * d.bins + k] = ym;
+        if (a.ymag && ok) (a.ymag + ((int64_t)row * d.frames_out + fb0 + c * FB) * d.bins)[(fl2 * d.bins + k) & 0x7fffffff] = ym;
       }
       __builtin_amdgcn_sched_barrier(0);
     }
