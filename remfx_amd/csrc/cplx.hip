@@ -116,7 +116,29 @@ __global__ __launch_bounds__(256) void cplx_affine_act_bwd_kernel(const float* _
   }
 }
 
+// Unit vector and magnitude of a complex number without leaving fp32's range: both parts are scaled by the power of two that brings the
+// larger one into [0.5, 1) (exact), so the squares neither underflow nor overflow and every nonzero finite value keeps its own phase.
+// (In sqrtf(re^2 + im^2) the squares are subnormal below |z| ~ 1e-19 and 0 below 1e-23: tanh(0) / 0 = NaN in the bounded mask, phase
+// 0 in the phase mask -- DESIGN.md 4.20.)  z = 0: n = (0, 0), mag = 0, e = 0.  One division.
+struct CxPolar { float nr, ni, mag, h; int e; };
+__device__ __forceinline__ CxPolar cx_polar(float re, float im) {
+  CxPolar p;
+  (void)frexpf(fmaxf(fabsf(re), fabsf(im)), &p.e);
+  const float ur = ldexpf(re, -p.e), ui = ldexpf(im, -p.e);
+  p.h = sqrtf(ur * ur + ui * ui);                       // in [0.5, 1.42) unless z = 0
+  const float rh = p.h > 0.f ? 1.f / p.h : 0.f;
+  p.nr = ur * rh; p.ni = ui * rh;
+  p.mag = ldexpf(p.h, p.e);
+  return p;
+}
+// below CX_SMALL the quotients tanh(a) / a and sech^2(a) - tanh(a) / a come from their series (the next terms are below 2e-8 relative)
+constexpr float CX_SMALL = 0.0625f;
+__device__ __forceinline__ float cx_tanhc_series(float a2) {       // tanh(a) / a = 1 - a^2/3 + 2 a^4/15 - 17 a^6/315
+  return 1.f + a2 * (-1.f / 3.f + a2 * (2.f / 15.f + a2 * (-17.f / 315.f)));
+}
+
 // m, tf, out: (N, 2, P) planes (sample stride given).  out = tanh(|m|)/|m| * m (*) tf   (complex product)
+// m = 0 (where the reference is 0 / 0): out = 0 and, backward, gm = gout (*) conj(tf), the limits.
 __global__ void bound_mask_kernel(const float* __restrict__ m, const float* __restrict__ tf, float* __restrict__ out,
                                   int N, int64_t P, int64_t m_ns, int64_t tf_ns, int64_t out_ns) {
   const int64_t total = (int64_t)N * P;
@@ -124,13 +146,14 @@ __global__ void bound_mask_kernel(const float* __restrict__ m, const float* __re
     const int64_t p = i % P, n = i / P;
     const float mr = m[n * m_ns + p], mi = m[n * m_ns + P + p];
     const float tr = tf[n * tf_ns + p], ti = tf[n * tf_ns + P + p];
-    const float mag = sqrtf(mr * mr + mi * mi);
-    const float k = tanhf(mag) / mag;
-    const float ar = k * mr, ai = k * mi;
+    const CxPolar z = cx_polar(mr, mi);
+    const float th = z.mag < CX_SMALL ? z.mag * cx_tanhc_series(z.mag * z.mag) : tanhf(z.mag);
+    const float ar = th * z.nr, ai = th * z.ni;
     out[n * out_ns + p] = ar * tr - ai * ti;
     out[n * out_ns + P + p] = ar * ti + ai * tr;
   }
 }
+// with n = m / |m|, a = |m|:  gm = k ga + (sech^2 a - k) (ga . n) n,  k = tanh(a) / a
 __global__ void bound_mask_bwd_kernel(const float* __restrict__ m, const float* __restrict__ tf,
                                       const float* __restrict__ gout, float* __restrict__ gm, int N, int64_t P,
                                       int64_t m_ns, int64_t tf_ns, int64_t g_ns, int64_t gm_ns) {
@@ -141,24 +164,29 @@ __global__ void bound_mask_bwd_kernel(const float* __restrict__ m, const float* 
     const float tr = tf[n * tf_ns + p], ti = tf[n * tf_ns + P + p];
     const float gr = gout[n * g_ns + p], gi = gout[n * g_ns + P + p];
     const float gar = gr * tr + gi * ti, gai = -gr * ti + gi * tr;   // gout (*) conj(tf)
-    const float mag = sqrtf(mr * mr + mi * mi);
-    const float th = tanhf(mag);
-    const float k = th / mag;
-    const float kp = ((1.f - th * th) * mag - th) / (mag * mag);      // dk/dmag
-    const float dot = (gar * mr + gai * mi) * kp / mag;
-    gm[n * gm_ns + p] = gar * k + dot * mr;
-    gm[n * gm_ns + P + p] = gai * k + dot * mi;
+    const CxPolar z = cx_polar(mr, mi);
+    const float a2 = z.mag * z.mag;
+    const float th = tanhf(z.mag);
+    const float rmag = ldexpf(z.h > 0.f ? 1.f / z.h : 0.f, -z.e);
+    const bool small = z.mag < CX_SMALL;
+    const float k = small ? cx_tanhc_series(a2) : th * rmag;
+    // sech^2 a - k = -2 a^2/3 + 8 a^4/15 - 34 a^6/105 + ...
+    const float q = small ? a2 * (-2.f / 3.f + a2 * (8.f / 15.f + a2 * (-34.f / 105.f))) : (1.f - th * th) - k;
+    const float dot = (gar * z.nr + gai * z.ni) * q;
+    gm[n * gm_ns + p] = gar * k + dot * z.nr;
+    gm[n * gm_ns + P + p] = gai * k + dot * z.ni;
   }
 }
 
 // Open-Unmix Separator, niter = 0 "wiener": estimate = magnitude x phase of the mixture STFT
 // (models.py:298 via umx Separator).  xc, out: complex [n] (view_as_real layout); mag: [n].
+// The phase is atan2(im, re) of every nonzero bin however small; only x = 0 takes (1, 0).
 __global__ void phase_mask_kernel(const float* __restrict__ mag, const float2* __restrict__ xc,
                                   float2* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float2 x = xc[i];
-    const float a = sqrtf(x.x * x.x + x.y * x.y);
-    const float c = a > 0.f ? x.x / a : 1.f, s = a > 0.f ? x.y / a : 0.f;   // cos / sin of atan2(im, re)
+    const CxPolar z = cx_polar(x.x, x.y);
+    const float c = z.h > 0.f ? z.nr : 1.f, s = z.ni;               // cos / sin of atan2(im, re)
     const float m = mag[i];
     out[i] = make_float2(m * c, m * s);
   }
@@ -167,8 +195,8 @@ __global__ void phase_mask_bwd_kernel(const float2* __restrict__ xc, const float
                                       float* __restrict__ gmag, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float2 x = xc[i], g = gout[i];
-    const float a = sqrtf(x.x * x.x + x.y * x.y);
-    const float c = a > 0.f ? x.x / a : 1.f, s = a > 0.f ? x.y / a : 0.f;
+    const CxPolar z = cx_polar(x.x, x.y);
+    const float c = z.h > 0.f ? z.nr : 1.f, s = z.ni;
     gmag[i] = g.x * c + g.y * s;
   }
 }
