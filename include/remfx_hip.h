@@ -30,9 +30,11 @@ extern "C" {
 enum rfx_act {
   RFX_ACT_NONE = 0,
   RFX_ACT_RELU = 1,   /* classifier.py:271-272 */
-  RFX_ACT_GELU = 2,   /* exact erf GELU: HDemucs enc/dec, DConv */
+  RFX_ACT_GELU = 2,   /* erf-form GELU (not the tanh approximation) from a 5-term fp32 erf: cdf within 3e-7 absolute, GELU within
+                         5e-7 at |x| ~ 3, GELU' within 3e-7: HDemucs enc/dec, DConv */
   RFX_ACT_TANH = 3,   /* tcn.py:129 */
-  RFX_ACT_PRELU = 4,  /* per-output-channel slope: tcn.py:47,51 */
+  RFX_ACT_PRELU = 4,  /* per-output-channel slope: tcn.py:47,51.  GEMM epilogues and rfx_prelu_fwd / _bwd only: the entry points
+                         without a slope argument (rfx_act_fwd / _bwd / _add_fwd / rfx_act_rows / _rows16) refuse it with -1 */
   RFX_ACT_LEAKY = 5,  /* slope 0.01: DCUNet */
   RFX_ACT_SIGMOID = 6 /* classifier.py:231 */
 };
@@ -285,7 +287,8 @@ int rfx_lstm_bwd(const float* gout, const void* pack, const float* gates, const 
 int rfx_lstm_set_local(int32_t fwd_max_sequences, int32_t bwd_max_sequences);
 
 /* ---- elementwise / reductions ------------------------------------------------ */
-/* y = act(x) elementwise over n contiguous floats; PReLU/bias not supported here. */
+/* y = act(x) elementwise over n contiguous floats (any 4-byte alignment); no bias, and act == RFX_ACT_PRELU is refused (-1) by this
+ * and the next four entry points: they carry no slope. */
 int rfx_act_fwd(const float* x, float* y, int64_t n, int32_t act, void* stream);
 /* gx = gy * act'(x) */
 int rfx_act_bwd(const float* x, const float* gy, float* gx, int64_t n, int32_t act, void* stream);
@@ -359,12 +362,14 @@ int rfx_span_mask(float* x, int32_t R, int32_t F, int32_t T, const int32_t* f0, 
  * frames of `width` 200 at `stride` 100, the central parts are stitched back; reached from models.py:319).
  * x: (B, C, T) contiguous; h: (C, width * Bn) with Bn = B * nfr, position t * Bn + b * nfr + k = step t of frame k of row b
  * (the channel-major layout of rfx_lstm_fwd).  mode 0: h = frames of x (zero beyond T);  1: x = adjoint of mode 0 applied to h;
- * 2: x = stitched central parts of h (+ skip[b][c][tau] when skip != NULL);  3: h = adjoint of mode 2 applied to x. */
+ * 2: x = stitched central parts of h (+ skip[b][c][tau] when skip != NULL);  3: h = adjoint of mode 2 applied to x.
+ * The frames have to cover the row: T > (nfr - 1) * stride + width is refused (-1, nothing written).  Fewer samples than frames
+ * (zero padding, whole frames of it included) are fine. */
 int rfx_blstm_frames(const float* src, const float* skip, float* dst, int32_t B, int32_t C, int32_t T, int32_t nfr,
                      int32_t width, int32_t stride, int32_t mode, void* stream);
 
 /* out[0] = scale * sum |a-b| over n elements (nn.L1Loss, models.py:320: scale = 1 / n).  ws: RFX_L1_SLOTS doubles of per-workgroup
- * partials (no initialisation needed), added in slot order. */
+ * partials (no initialisation needed), added in slot order.  n == 0: out[0] = 0 is written (whatever the scale), no slot is. */
 #define RFX_L1_SLOTS 512
 int rfx_l1_sum(const float* a, const float* b, int64_t n, double* ws, float scale, float* out, void* stream);
 

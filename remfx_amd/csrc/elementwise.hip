@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64) void l1_finish_kernel(const double* __restrict_
   double acc = 0.0;                     // one wave: lane l adds slots l, l + 64, ... in order, then the fixed butterfly
   for (int k = threadIdx.x; k < nslots; k += 64) acc += slots[k];
   acc = rfx_wave_sum_d(acc);
-  if (threadIdx.x == 0) out[0] = (float)acc * scale;          // torch: (fp32 sum) / numel
+  if (threadIdx.x == 0) out[0] = nslots ? (float)acc * scale : 0.f;          // torch: (fp32 sum) / numel; n == 0: 0 whatever the scale
 }
 
 // slots[c][chunk] = partial sum_{n,a,b} x[...] of the chunk; grid = (C, chunks); added in chunk order by rfx_slot_sum_kernel
@@ -178,7 +178,7 @@ static int grid_for(int64_t n) {
 }
 
 extern "C" int rfx_act_fwd(const float* x, float* y, int64_t n, int32_t act, void* stream) {
-  if (!x || !y || n < 0) return -1;
+  if (!x || !y || n < 0 || act == RFX_ACT_PRELU) return -1;     // no slope argument here: rfx_prelu_fwd / _bwd
   if (n == 0) return 0;
   hipLaunchKernelGGL(act_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, y, n, act);
   RFX_CHECK_LAUNCH();
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void act_rows_kernel(const ActRowsArgs a) {
 static int act_rows_launch(bool x16, const void* x, int64_t xs0, int64_t xs1, int64_t xs2, const float* gy, int64_t gs0,
                            int64_t gs1, int64_t gs2, void* out, int64_t os0, int64_t os1, int64_t os2, int32_t D0,
                            int32_t D1, int32_t D2, int32_t T, int32_t act, void* stream) {
-  if (!x || !out || D0 <= 0 || D1 <= 0 || D2 <= 0 || T <= 0) return -1;
+  if (!x || !out || D0 <= 0 || D1 <= 0 || D2 <= 0 || T <= 0 || act == RFX_ACT_PRELU) return -1;
   const int64_t rows = (int64_t)D0 * D1 * D2, per = ((int64_t)T + 255) / 256;
   if (rows * per > 0x7fffffffLL) return -1;
   ActRowsArgs a;
@@ -274,14 +274,14 @@ extern "C" int rfx_act_rows16(const void* x, int64_t xs0, int64_t xs1, int64_t x
   return act_rows_launch(true, x, xs0, xs1, xs2, gy, gs0, gs1, gs2, out, os0, os1, os2, D0, D1, D2, T, act, stream);
 }
 extern "C" int rfx_act_bwd(const float* x, const float* gy, float* gx, int64_t n, int32_t act, void* stream) {
-  if (!x || !gy || !gx || n < 0) return -1;
+  if (!x || !gy || !gx || n < 0 || act == RFX_ACT_PRELU) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, gy, gx, n, act);
   RFX_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int rfx_act_add_fwd(const float* x, const float* res, float* y, int64_t n, int32_t act, void* stream) {
-  if (!x || !res || !y || n < 0) return -1;
+  if (!x || !res || !y || n < 0 || act == RFX_ACT_PRELU) return -1;
   if (n == 0) return 0;
   hipLaunchKernelGGL(act_add_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, res, y, n, act);
   RFX_CHECK_LAUNCH();
@@ -334,11 +334,12 @@ extern "C" int rfx_prelu_bwd(const float* x, const float* gy, const float* slope
 // out[0] = scale * sum |a - b|; ws: RFX_L1_SLOTS doubles (per-workgroup partials, no initialisation needed)
 extern "C" int rfx_l1_sum(const float* a, const float* b, int64_t n, double* ws, float scale, float* out, void* stream) {
   if (!a || !b || !out || !ws || n < 0) return -1;
-  if (n == 0) return 0;
-  int g = grid_for(n);
+  int g = n > 0 ? grid_for(n) : 0;                                      // n == 0: out[0] = 0 and no slot, as rfx_sumsq
   g = g > RFX_L1_SLOTS ? RFX_L1_SLOTS : g;
-  hipLaunchKernelGGL(l1_sum_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, a, b, n, ws);
-  RFX_CHECK_LAUNCH();
+  if (g) {
+    hipLaunchKernelGGL(l1_sum_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, a, b, n, ws);
+    RFX_CHECK_LAUNCH();
+  }
   hipLaunchKernelGGL(l1_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ws, g, scale, out);
   RFX_CHECK_LAUNCH();
   return 0;
@@ -520,6 +521,7 @@ __global__ void blstm_frames_kernel(const float* __restrict__ src, const float* 
 extern "C" int rfx_blstm_frames(const float* src, const float* skip, float* dst, int32_t B, int32_t Cn, int32_t T, int32_t nfr,
                                 int32_t width, int32_t stride, int32_t mode, void* stream) {
   if (!src || !dst || B <= 0 || Cn <= 0 || T <= 0 || nfr <= 0 || width <= 0 || stride <= 0 || mode < 0 || mode > 3) return -1;
+  if ((int64_t)T > ((int64_t)nfr - 1) * stride + width) return -1;      // the frames must cover T: mode 2 would read past frame nfr - 1
   const int64_t total = (mode == 0 || mode == 3) ? (int64_t)Cn * width * B * nfr : (int64_t)B * Cn * T;
   hipLaunchKernelGGL(blstm_frames_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, skip, dst, B, Cn, T,
                      nfr, width, stride, mode);
