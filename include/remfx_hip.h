@@ -633,7 +633,10 @@ int rfx_stft_loss_grad(const float* xc, const float* yc, int32_t R, int64_t n, f
  * models.py:320): two frames of a signal come out of one complex FFT (w s_a + i w s_b), the prediction's clamped powers wait in
  * registers for the target's and the three row sums are written to sums [R][3] (every workgroup stores its partial into its own slot of
  * ws -- rfx_stft_pair_loss_ws(d) doubles, no initialisation needed -- and the slots are added in order: bit-reproducible).  d: R, T, n_fft (512 / 1024 / 2048), hop, win, frames_out = 1 + T / hop,
- * bins = n_fft / 2 + 1, frame0 = 0, in_mode 0.  xspec / ymag (both or neither): the prediction's spectrum, frame-major complex
+ * bins = n_fft / 2 + 1, frame0 = 0, in_mode 0, no extra pads, scale = 1 (the kernel applies no scale).  Refused with -1, nothing
+ * written: n_fft above 2048, in_mode != 0, an extra pad, frame0 != 0, bins != n_fft / 2 + 1, scale != 1, xspec without ymag or ymag
+ * without xspec.  NOT checked: frames_out against 1 + T / hop (the caller's), and herm, mode, eps, alpha, accum, in_offset, which the
+ * kernel does not read.  xspec / ymag (both or neither): the prediction's spectrum, frame-major complex
  * [R][frames][bins][2], and the clamped target magnitudes [R][frames][bins], for rfx_stft_loss_grad_m + rfx_fft_synthesis
  * (RFX_STFT_COMPLEX_FM) in the backward. */
 int64_t rfx_stft_pair_loss_ws(const rfx_stft_desc* d);

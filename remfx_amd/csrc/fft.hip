@@ -1090,6 +1090,7 @@ extern "C" int rfx_stft_pair_loss(const rfx_stft_desc* d, const float* x, const 
                                   double* ws, float* sums, float* xspec, float* ymag, void* stream) {
   if (!stft_desc_ok(d) || !x || !y || !window || !sums || !ws || (xspec == nullptr) != (ymag == nullptr)) return -1;
   if (d->n_fft > 2048 || d->in_mode != 0 || d->extra_pad_l || d->extra_pad_r || d->frame0 != 0 || d->bins != d->n_fft / 2 + 1) return -1;
+  if (d->scale != 1.f) return -1;                              // the kernel never reads d->scale (no caller sets it): refused, not ignored
   PairArgs a;
   a.d = *d; a.x = x; a.y = y; a.window = window; a.slots = ws; a.eps = eps;
   a.xspec = reinterpret_cast<v2f*>(xspec); a.ymag = ymag;

@@ -185,8 +185,10 @@ def test_pair_loss_kernel(geom):
 @pytest.mark.parametrize("case", [(1024, 120, 600, 5, 30011), (2048, 240, 1200, 3, 20000), (512, 50, 240, 9, 7001)])
 def test_loss_gradient_inside_synthesis(case, monkeypatch):
     """rfx_fft_synthesis_lossgrad (gradient spectrum formed in the inverse transform's merge step, never written) against
-    rfx_stft_loss_grad_m + rfx_fft_synthesis: the same per-cell arithmetic, so the two differ only by the order of the overlap-add
-    atomics; identical signals still get an exactly zero gradient."""
+    rfx_stft_loss_grad_m + rfx_fft_synthesis.  Both overlap-add by ownership at these shapes (no atomics: each is bit-reproducible on its
+    own); they differ in the cell arithmetic's rounding -- the fused form takes one reciprocal of |X| where the cell kernel divides three
+    times -- and in nothing else; identical signals still get an exactly zero gradient.  The device against itself: the per-element
+    check against fp64 is tests/test_gpu_fft_kernel.py."""
     from remfx_amd import losses
     n_fft, hop, win, R, L = case
     g = torch.Generator().manual_seed(n_fft + R)
