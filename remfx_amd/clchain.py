@@ -95,17 +95,13 @@ def _wgrad(f, p, q, N, OA, IA, B, w, b, bias_src=None):
     """Weight (and bias) gradient of one layer: into the armed GradSink's slices on its side stream (returns None, None), else fresh
     tensors for autograd.  bias_src: the channels-last tensor whose position sum is the bias gradient when the GEMM form does not
     carry it (transposed convolutions: the bias gradient sums Q, not P)."""
-    sink = ops.SINK
-    tw = sink.lookup(w) if sink is not None else None
-    tb = sink.lookup(b) if (tw is not None and b is not None) else None
-    if tw is not None and (b is None or tb is not None):
-        with torch.cuda.stream(sink.stream_for_wgrad(p, q)):
-            clast.wgrad(f, p, q, N, OA, IA, B, tw[1], tb[1] if (f.bias and b is not None) else _scratch_bias(f, p), accumulate=True)
+    sw = ops.sink_write(w, b, operands=(p, q))
+    if sw is not None:
+        with sw:
+            dw, db = sw.grads
+            clast.wgrad(f, p, q, N, OA, IA, B, dw, db if (f.bias and b is not None) else _scratch_bias(f, p), accumulate=True)
             if b is not None and not f.bias:
-                rowsum(bias_src, 1, b.numel(), tb[1], accumulate=True)
-        sink.wrote(tw[0])
-        if b is not None:
-            sink.wrote(tb[0])
+                rowsum(bias_src, 1, b.numel(), db, accumulate=True)
         return None, None
     dw = torch.empty(w.shape, device=w.device, dtype=torch.float32)
     db = torch.empty(b.shape, device=w.device, dtype=torch.float32) if b is not None else None
@@ -350,12 +346,11 @@ class FreqDecoderFn(torch.autograd.Function):
             Cs = tw.shape[1]
             g16 = clast.im2col_s4(g, A, T, fold)
             grads_p[4 * J + 2], _ = _wgrad(form("wtail", Cc, Cs), y0, g16, Bn, A, A, T, tw, None)
-            sink = ops.SINK
-            tbs = sink.lookup(tb) if sink is not None else None
             dtb = ops.channel_sum(g)
-            if tbs is not None:
-                tbs[1].add_(dtb)
-                sink.wrote(tbs[0])
+            sw = ops.sink_write(tb)
+            if sw is not None:
+                with sw:
+                    sw.grads[0].add_(dtb)
             else:
                 grads_p[4 * J + 3] = dtb
             ftd = form("taild", Cc, Cs)

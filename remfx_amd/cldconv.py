@@ -168,10 +168,8 @@ def layer_backward(gy, x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, sc
     partial = alloc("partial", (min(GRID, S), npg), torch.float32, dev)
     # the five small gradients go straight into the parameters' slices of the flat gradient buffer when a GradSink is armed
     # (autograd would add each returned tensor into .grad with a launch of its own)
-    sink = ops.SINK
-    tgt = [sink.lookup(p) for p in (scale, g2w, g2b, g1w, g1b)] if sink is not None else [None]
-    direct = all(t is not None for t in tgt)
-    pg = None if direct else alloc("pg", (npg,), torch.float32, dev)
+    sw = ops.sink_write(scale, g2w, g2b, g1w, g1b)
+    pg = None if sw is not None else alloc("pg", (npg,), torch.float32, dev)
     d = _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale)
     d.TPS = TPS
     d.gy, d.y, d.a, d.hpre, d.stats = gy.data_ptr(), dx.data_ptr(), a.data_ptr(), hpre.data_ptr(), stats.data_ptr()
@@ -184,14 +182,12 @@ def layer_backward(gy, x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, sc
         d.tsum, d.sums = tsum.data_ptr(), sums.data_ptr()
     else:
         d.w1dp = clchain.packed(tb["w1dp"], w1).data_ptr()
-    if direct:
-        for q, t in enumerate(tgt):
-            d.pg_dst[q] = t[1].data_ptr()
-    check(_lib.lib().rfx_cl_dconv_bwd(C.byref(d), C.c_void_p(pg.data_ptr() if pg is not None else None), C.c_void_p(ops.raw_stream())),
-          "rfx_cl_dconv_bwd")
-    if direct:
-        for t in tgt:
-            sink.wrote(t[0])
+    if sw is not None:
+        for q, t in enumerate(sw.grads):
+            d.pg_dst[q] = t.data_ptr()
+    with sw or ops.NO_SINK:
+        check(_lib.lib().rfx_cl_dconv_bwd(C.byref(d), C.c_void_p(pg.data_ptr() if pg is not None else None),
+                                          C.c_void_p(ops.raw_stream())), "rfx_cl_dconv_bwd")
     if passes:                                      # dx = gy + the transposed 3-tap convolution of dh (taps cross tile edges)
         fx = _dx_form(Cc, H, dil)
         clast.conv(fx, clchain.packed(fx, w1), dh, Bn, A, Tt, A, "store", out0=dx, res=gy)

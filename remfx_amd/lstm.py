@@ -126,11 +126,10 @@ class _LSTMLayerFn(torch.autograd.Function):
             dx = ops.conv2d_dgrad(dG, wcat, tuple(x4.shape), x4.stride(), (1, 1), (0, 0), (1, 1)).squeeze(2)
         # the eight parameter gradients: with a GradSink armed (all eight recognised) they are computed on its side stream and
         # accumulated in place; nothing downstream in the backward chain needs them
-        sink = ops.SINK
-        tg = [sink.lookup(p) for p in ctx.params] if sink is not None else [None]
-        sunk = all(t is not None for t in tg)
-        stream = sink.stream_for_wgrad(x, dG, out) if sunk else torch.cuda.current_stream()
-        with torch.cuda.stream(stream):
+        sw = ops.sink_write(*ctx.params, operands=(x, dG, out))
+        sunk = sw is not None
+        with sw or ops.NO_SINK:
+            # no w given: the inner call claims nothing and returns the two concatenated gradients
             dwcat, dbcat = ops.conv2d_wgrad(x4, dG, tuple(wcat.shape), (1, 1), (0, 0), (1, 1), True)
             dwcat = dwcat.view(8 * H, Cin)
             out4 = out.unsqueeze(2)
@@ -139,7 +138,7 @@ class _LSTMLayerFn(torch.autograd.Function):
                 dp, xs, gs = _whh_plan(out4, dG, H, d, Bn)
                 dap = ops.gemm_wgrad(dp, xs, gs)
                 if sunk:                     # straight into the parameter's slice of the flat gradient buffer (no temporary, no add)
-                    ops.unpack_add(dp, dap, tg[1 + 4 * d][1])
+                    ops.unpack_add(dp, dap, sw.grads[1 + 4 * d])
                     dwhh.append(None)
                     continue
                 dw = ops.zeros((4 * H, H), g.device)
@@ -148,12 +147,10 @@ class _LSTMLayerFn(torch.autograd.Function):
             db0, db1 = dbcat[:4 * H], dbcat[4 * H:]
             grads = (dwcat[:4 * H], dwhh[0], db0, db0, dwcat[4 * H:], dwhh[1], db1, db1)
             if sunk:                         # one launch instead of six add_ into the flat gradient buffer's views
-                v = [t[1] for t in tg]
+                v = sw.grads
                 check(_lib.lib().rfx_lstm_grad_scatter(_ptr(dwcat), _ptr(dbcat), H, Cin, _ptr(v[0]), _ptr(v[4]), _ptr(v[2]), _ptr(v[3]),
                                                        _ptr(v[6]), _ptr(v[7]), _stream()), "rfx_lstm_grad_scatter")
         if sunk:
-            for i, _ in tg:
-                sink.wrote(i)
             return (dx,) + (None,) * 10
         return (dx,) + grads + (None, None)
 

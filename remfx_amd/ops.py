@@ -4,6 +4,7 @@ PyTorch is used here only for device memory, streams and the autograd tape; ever
 op below launches hand-written HIP kernels from libremfx_hip.so.  There is no CPU
 or ATen fallback: tensors must be fp32 CUDA(HIP) tensors and the library must load.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -64,16 +65,25 @@ class GradSink:
     (FlatAdamW.step) and the gradient exchange (ddp.GradSync) join the side stream before they read the buffer.
 
     Armed by FlatParams.zero_grad(), joined / disarmed by FlatParams.join().  A weight is recognised by its storage address:
-    the tensor a backward node saved must start where a parameter's view of the flat buffer starts, be contiguous and have the
-    parameter's size (`w.unsqueeze(2)` of a Conv1d weight qualifies, a transposed or concatenated weight does not and takes the
-    ordinary autograd route)."""
+    the tensor a backward node saved must start where a parameter's view of the flat buffer starts, be contiguous fp32 on the GPU
+    and have the parameter's size (`w.unsqueeze(2)` of a Conv1d weight qualifies, a transposed or concatenated weight does not
+    and takes the ordinary autograd route).
+
+    All a backward node does to write parameter gradients is `sw = ops.sink_write(w, b, operands=(x, g))`.  None back (no sink
+    armed, or a parameter not recognised: the claim is all-or-nothing; a None parameter such as an absent bias is skipped and has a
+    None view) means fresh tensors for autograd, and nothing was counted, called or done to a stream.  Otherwise its kernels
+    ACCUMULATE into `sw.grads[k]` inside `with sw:` and it returns None for those gradients.  `operands`, the tensors the kernels
+    read, send the body to the side stream (ordered after the current one, the allocator told that the side stream uses them);
+    without them, or with `side is None`, it runs where the caller is.  Leaving the scope counts one write per claimed parameter,
+    in argument order, with the CALLER's stream current: `note_stream()` and ddp.GradSync's `on_write`, which may launch a bucket's
+    all-reduce from there, rely on that.  A kernel that SETS its outputs claims with `first_write=True`: refused once one of the
+    parameters has a gradient in this step, so an earlier use's is never overwritten."""
 
     MODE = "side"      # "side": weight gradients on a side stream; "main": in place on the compute stream; "off": autograd accumulation
 
     def __init__(self, flat, side_stream=True):
         self.flat = flat
-        self.base = flat.data.data_ptr()
-        self.index = {self.base + 4 * o: i for i, o in enumerate(flat.offsets)}
+        self.index = {flat.data.data_ptr() + 4 * o: i for i, o in enumerate(flat.offsets)}
         dev = flat.data.device
         self.side = torch.cuda.Stream(device=dev) if (side_stream and dev.type == "cuda") else None
         self.used_side = False
@@ -84,18 +94,24 @@ class GradSink:
         # writes for the engine.  join() and ddp.GradSync order the optimiser step / a bucket's all-reduce behind all of them.
         self.write_streams = {}
 
-    def lookup(self, w):
-        """(index, 1-D gradient view) of the parameter `w` is, or None."""
-        if w is None or not w.is_cuda:
-            return None
-        i = self.index.get(w.data_ptr())
-        if i is None:
-            return None
-        p = self.flat.params[i]
-        if w.numel() != p.numel() or not w.is_contiguous() or w.dtype != torch.float32:
-            return None
-        o = self.flat.offsets[i]
-        return i, self.flat.grad[o:o + p.numel()]
+    def claim(self, params, operands=None, first_write=False):
+        """The scope (SinkWrite) in which the caller's kernels write the gradients of `params`, or None -- see the class text."""
+        flat = self.flat
+        idx, grads = [], []
+        for w in params:
+            if w is None:
+                grads.append(None)
+                continue
+            i = self.index.get(w.data_ptr()) if w.is_cuda else None
+            if i is None:
+                return None
+            n = flat.params[i].numel()
+            if w.numel() != n or not w.is_contiguous() or w.dtype != torch.float32 or (first_write and self.writes[i]):
+                return None
+            o = flat.offsets[i]
+            idx.append(i)
+            grads.append(flat.grad[o:o + n])
+        return SinkWrite(self, idx, grads, operands) if idx else None
 
     def note_stream(self):
         """Remember the current stream as one that carries gradient writes of this step."""
@@ -109,26 +125,12 @@ class GradSink:
             if st != stream:
                 stream.wait_stream(st)
 
-    def wrote(self, i):
-        self.writes[i] += 1
-        if self.flat.grad.is_cuda:
+    def _wrote(self, idx):
+        for i in idx:
+            self.writes[i] += 1
             self.note_stream()
-        if self.on_write is not None:
-            self.on_write(i)
-
-    def stream_for_wgrad(self, *operands):
-        """The stream weight-gradient work goes to (ordered after everything already on the current stream).  The operands were
-        allocated on the current stream: tell the caching allocator the side stream uses them too."""
-        main = torch.cuda.current_stream()
-        self.note_stream()
-        if self.side is None:
-            return main
-        self.side.wait_stream(main)
-        for t in operands:
-            if t is not None:
-                t.record_stream(self.side)
-        self.used_side = True
-        return self.side
+            if self.on_write is not None:
+                self.on_write(i)
 
     def join(self):
         """Current stream waits for every queued weight gradient: the side stream's, and whatever other streams (the time branch's)
@@ -140,6 +142,47 @@ class GradSink:
         if cur is not None and self.write_streams:
             self.order_after_writes(cur)
             self.write_streams = {}
+
+
+class SinkWrite:
+    """The scope of one granted GradSink claim (GradSink.claim).  grads: one 1-D view of the flat gradient buffer per parameter
+    given, None for a None parameter.  A plain object, no generator: ~330 of these per Demucs step on a host-bound path."""
+    __slots__ = ("sink", "idx", "grads", "operands", "outer")
+
+    def __init__(self, sink, idx, grads, operands):
+        self.sink, self.idx, self.grads, self.operands, self.outer = sink, idx, grads, operands, None
+
+    def __enter__(self):
+        sink = self.sink
+        if self.operands is not None:
+            sink.note_stream()                         # the caller's stream: the operands' producers, and the writes counted at exit
+            side = sink.side
+            if side is not None:
+                self.outer = torch.cuda.current_stream()
+                side.wait_stream(self.outer)           # ordered after everything already on the current stream
+                for t in self.operands:                # allocated on the current stream: the caching allocator must know the
+                    if t is not None:                  # side stream uses them too
+                        t.record_stream(side)
+                sink.used_side = True
+                torch.cuda.set_stream(side)
+        return self
+
+    def __exit__(self, etype, exc, tb):
+        if self.outer is not None:
+            torch.cuda.set_stream(self.outer)
+        if etype is None:                             # on the caller's stream again: GradSync may launch an all-reduce from on_write
+            self.sink._wrote(self.idx)
+        return False
+
+
+NO_SINK = contextlib.nullcontext()     # the scope of a refused claim where one launch serves both routes: `with sw or ops.NO_SINK:`
+
+
+def sink_write(*params, operands=None, first_write=False):
+    """The one way a backward node writes parameter gradients through the armed GradSink (see its text): a SinkWrite scope, or
+    None when no sink is armed or the claim is refused (then the node returns fresh tensors to autograd)."""
+    sink = SINK
+    return sink.claim(params, operands, first_write) if sink is not None else None
 
 
 class StepGC:
@@ -288,10 +331,6 @@ class DevPlan:
             self._desc16[key] = v
         return v
 
-    def set_io(self, x=None, out=None):
-        """Refresh strides for a new tensor with the same geometry key (cheap)."""
-        return self
-
 
 _PLANS = {}
 
@@ -435,16 +474,15 @@ def gemm_fwd(dp, apack, x, out, bias=None, act=None, act_param=None, res=None, a
     tab = dp.tap_tab if prec else dp.ktab
     if dp2 is not None and prec:
         a2, k2, K2, Kpad2 = _ptr(apack2), _ptr(dp2.tap_tab), dp2.p.ntaps, dp2.p.Kpad_t
-        dp.desc.gpt2 = int(dp2.p.gpt)                      # the second table's own channel blocking
     elif dp2 is not None:
         a2, k2, K2, Kpad2 = _ptr(apack2), _ptr(dp2.ktab), dp2.p.K, dp2.p.Kpad
     else:
         a2, k2, K2, Kpad2 = None, None, 0, 0
     if x.dtype == torch.bfloat16 and not (prec == 2 and dp.p.R > 0):
         x = x.float()                # thin / channel-major plans (fewer than 8 input channels, M <= 8) read fp32: widen once
-    desc = dp.desc_for(x, out)
+    desc = dp.desc_for(x, out)                  # fp32 in, fp32 out: dp.desc itself
     if dp2 is not None and prec:
-        desc.gpt2 = int(dp2.p.gpt)
+        desc.gpt2 = int(dp2.p.gpt)              # the second table's own channel blocking
     if TRACE_VARIANT is not None:               # measurement hook (bench.py): which kernel instantiation this launch is
         TRACE_VARIANT.append(_lib.lib().rfx_gemm_fwd_variant(C.byref(desc), C.byref(e), int(dp2 is not None), prec))
     check(_lib.lib().rfx_gemm_fwd(C.byref(desc), _ptr(apack), _ptr(tab), _ptr(x), _ptr(out),
@@ -604,20 +642,16 @@ def conv2d_wgrad(x, g, wshape, stride, padding, dilation, need_bias, w=None, b=N
     dp = _plans(key, x.device, lambda: convplan.conv_fwd_plan(
         tuple(x.shape), x.stride(), tuple(wshape), stride, padding, dilation, g.stride(), bias_row=need_bias))
     p = dp.p
-    sink = SINK
-    tw = sink.lookup(w) if (sink is not None and w is not None) else None
-    tb = sink.lookup(b) if (tw is not None and need_bias) else None
-    if tw is not None and (tb is not None or not need_bias):
-        with torch.cuda.stream(sink.stream_for_wgrad(x, g)):
+    sw = sink_write(w, b, operands=(x, g)) if (w is not None and (b is not None) == bool(need_bias)) else None
+    if sw is not None:
+        with sw:
+            dw, db = sw.grads
             wg = gemm_wgrad(dp, x, g)
             if need_bias:       # weight + bias gradient out of the same matrices in one launch
                 check(_lib.lib().rfx_unpack_add_bias(_ptr(wg.ws), _ptr(dp.woff), p.w_ms, p.M, p.extra["n_weight_rows"], p.Kpad,
-                                                     _ptr(tw[1]), p.K - 1, _ptr(tb[1]), wg.splits, _stream()), "rfx_unpack_add_bias")
+                                                     _ptr(dw), p.K - 1, _ptr(db), wg.splits, _stream()), "rfx_unpack_add_bias")
             else:
-                unpack_add(dp, wg, tw[1])                  # conv_fwd_plan rows = every live (ci, ka, kb) of every output channel, once
-        sink.wrote(tw[0])
-        if need_bias:
-            sink.wrote(tb[0])
+                unpack_add(dp, wg, dw)                     # conv_fwd_plan rows = every live (ci, ka, kb) of every output channel, once
         return None, None
     wg = gemm_wgrad(dp, x, g)
     if p.extra.get("dense", True):
@@ -627,6 +661,18 @@ def conv2d_wgrad(x, g, wshape, stride, padding, dilation, need_bias, w=None, b=N
     unpack_set(dp, wg, dw)                                 # conv_fwd_plan rows = every live (ci, ka, kb) of every output channel, once
     db = unpack_col(dp, wg, p.K - 1) if need_bias else None
     return dw, db
+
+
+def _conv2d_backward(ctx, g, res=None):
+    """(dx, dw, db) of a node that saved (x, w, ...) and set ctx.bias / ctx.cfg as Conv2dFn.forward does; res: see conv2d_dgrad."""
+    x, w = ctx.saved_tensors[:2]
+    stride, padding, dilation, has_bias = ctx.cfg
+    dx = dw = db = None
+    if ctx.needs_input_grad[0]:
+        dx = conv2d_dgrad(g, w, tuple(x.shape), tuple(x.stride()), stride, padding, dilation, res=res)
+    if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+        dw, db = conv2d_wgrad(x, g, tuple(w.shape), stride, padding, dilation, has_bias, w, ctx.bias)
+    return dx, dw, db
 
 
 class Conv2dFn(torch.autograd.Function):
@@ -641,15 +687,7 @@ class Conv2dFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        stride, padding, dilation, has_bias = ctx.cfg
-        g = g if g.is_contiguous() else g.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = conv2d_dgrad(g, w, tuple(x.shape), tuple(x.stride()), stride, padding, dilation)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            dw, db = conv2d_wgrad(x, g, tuple(w.shape), stride, padding, dilation, has_bias, w, ctx.bias)
-        return dx, dw, db, None, None, None, None, None
+        return _conv2d_backward(ctx, g if g.is_contiguous() else g.contiguous()) + (None,) * 5
 
 
 class ConvFork2dFn(torch.autograd.Function):
@@ -667,15 +705,7 @@ class ConvFork2dFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, gres):
-        x, w = ctx.saved_tensors
-        stride, padding, dilation, has_bias = ctx.cfg
-        g = g if g.is_contiguous() else g.contiguous()
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = conv2d_dgrad(g, w, tuple(x.shape), tuple(x.stride()), stride, padding, dilation, res=gres)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            dw, db = conv2d_wgrad(x, g, tuple(w.shape), stride, padding, dilation, has_bias, w, ctx.bias)
-        return dx, dw, db, None, None, None, None, None
+        return _conv2d_backward(ctx, g if g.is_contiguous() else g.contiguous(), gres) + (None,) * 5
 
 
 class ConvGlu2dFn(torch.autograd.Function):
@@ -710,8 +740,7 @@ class ConvGlu2dFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        x, w, y2 = ctx.saved_tensors
-        stride, padding, dilation, has_bias = ctx.cfg
+        y2 = ctx.saved_tensors[2]
         N, C2 = y2.shape[0], y2.shape[1]
         S = y2.numel() // (N * C2)
         g2 = torch.empty_like(y2)
@@ -719,12 +748,7 @@ class ConvGlu2dFn(torch.autograd.Function):
             check(_lib.lib().rfx_glu_bwd_bf16(_ptr(y2), _ptr(g.contiguous()), _ptr(g2), N, C2, S, _stream()), "rfx_glu_bwd_bf16")
         else:
             check(_lib.lib().rfx_glu_bwd(_ptr(y2), _ptr(g.contiguous()), _ptr(g2), N, C2, S, _stream()), "rfx_glu_bwd")
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = conv2d_dgrad(g2, w, tuple(x.shape), tuple(x.stride()), stride, padding, dilation)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            dw, db = conv2d_wgrad(x, g2, tuple(w.shape), stride, padding, dilation, has_bias, w, ctx.bias)
-        return dx, dw, db, None, None, None
+        return _conv2d_backward(ctx, g2) + (None,) * 3
 
 
 def conv2d_glu(x, w, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1)):
@@ -808,18 +832,13 @@ class ConvT2dFn(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_strided(tuple(x.shape), xs, device=x.device, dtype=torch.float32)
                 gemm_fwd(dp, pack_cached(dp, w), g, dx)
-            sink = SINK
-            tw = sink.lookup(w) if (sink is not None and need_w) else None
-            tb = sink.lookup(ctx.bias) if (tw is not None and has_bias) else None
-            if tw is not None and (tb is not None or not has_bias):
+            sw = sink_write(w, ctx.bias, operands=(x, g)) if need_w else None
+            if sw is not None:
                 # in place on the sink's side stream (see conv2d_wgrad)
-                with torch.cuda.stream(sink.stream_for_wgrad(x, g)):
-                    unpack_add(dp, gemm_wgrad(dp, g, x), tw[1])
+                with sw:
+                    unpack_add(dp, gemm_wgrad(dp, g, x), sw.grads[0])
                     if has_bias:
-                        tb[1].add_(channel_sum(g))
-                sink.wrote(tw[0])
-                if has_bias:
-                    sink.wrote(tb[0])
+                        sw.grads[1].add_(channel_sum(g))
                 return dx, None, None, None, None, None, None
             if need_w:
                 dw = zeros(tuple(w.shape), w.device)
