@@ -409,7 +409,14 @@ int rfx_localstate_gen_bwd(const float* q, const float* k, const float* cont, co
  * after every effect: remfx/effects.py:297-616 (RandomPedalboard{Distortion, Delay, Chorus, Compressor, Reverb}.forward),
  * :619-629 (LoudnessNormalize), called from remfx/datasets.py:109-202 (parallel_process_effects) and :205-330
  * (DynamicEffectDataset.process_effects).  x, y: (B, T) fp32 contiguous mono clips; every parameter is a B-vector on the device
- * (each clip draws its own).  y may alias x except for rfx_fx_delay.  Algorithms: csrc/fx.hip; oracle/ref_effects.py. */
+ * (each clip draws its own).  y may alias x (the same pointer: in place) for distortion, chorus, compressor, reverb, scale, limiter, eq,
+ * widener and phaser, with the same bits as out of place; rfx_fx_delay and rfx_fx_sox_reverb refuse x == y, rfx_fx_normalize_rows
+ * refuses it with a row table.  Every entry point returns -1, with nothing launched or written, for a null pointer, B outside
+ * 1 ... 65535, T < 1 or a parameter outside what its comment states.  rfx_fx_compressor: env_ws is B * T floats and holds the
+ * envelope afterwards.  rfx_fx_chorus: sample_rate from 4000 to 80600 Hz (a 50 ms delay and a block fit the 4096-sample ring).
+ * rfx_fx_reverb: 12544 <= sample_rate <= 143526 (every ring at least one 64-sample block long, the twelve rings within 160 KB of
+ * LDS); -1 outside.  Algorithms: csrc/fx.hip; oracle/ref_effects.py.  Every form of every kernel is pinned per element to the fp64
+ * statements of tests/fx_ref.py. */
 int rfx_fx_distortion(const float* x, float* y, int32_t B, int64_t T, const float* gain /* 10^(drive_db / 20) */, void* stream);
 int rfx_fx_delay(const float* x, float* y, int32_t B, int64_t T, const int32_t* delay_samples, const float* feedback,
                  const float* mix, void* stream);
@@ -443,7 +450,7 @@ int rfx_fx_normalize_rows(const float* x, float* y, const int32_t* rows, int32_t
                           int32_t nhop, int32_t nblk, double inv_block, const double* coef, float target_lufs, void* ws, void* stream);
 /* The rest of remfx/effects.py: RandomPedalboardLimiter (:468-494), RandomParametricEQ (:37-214), RandomStereoWidener (:217-252),
  * RandomVolumeAutomation (:255-294), RandomPedalboardPhaser (:418-465).  Parameters per row unless stated.
- * limiter: ws = 2 * B * T floats; params = 9 x B floats on the device, rows thr1 ratio1 c_attack1 c_release1 (stage 1),
+ * limiter: ws = 2 * B * T floats (afterwards: stage 2's envelope, then stage 1's output); params = 9 x B floats on the device, rows thr1 ratio1 c_attack1 c_release1 (stage 1),
  *          thr2 ratio2 c_attack2 c_release2 (stage 2, linear thresholds and ballistics coefficients as for rfx_fx_compressor), make-up.
  * eq: nsec = 2..8 biquads; coef on the device, per row nsec x {b0 b1 b2 a1 a2} (a0 = 1) then the (2 nsec)^2 zero-input state
  *     transition of `chunk` samples, row-major; chunk * 64 >= T.

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void fx_limit_out_kernel(const float* __restri
 //   in = 0.015 x;  out = sum_j comb_j(in);  out = allpass_3(allpass_2(allpass_1(allpass_0(out))));  y = wet1 * out + dry * x
 //   comb:    o = buf[i]; last = o (1 - damp) + last damp; buf[i] = in + last * feedback; return o          (lag = comb length)
 //   allpass: o = buf[i]; buf[i] = in + 0.5 o; return o - in                                                (lag = length)
-// Every filter's lag (>= 225 * sr / 44100 samples) exceeds a 64-sample block, so one wave per clip renders 64 samples per
+// Every filter's lag (>= 225 * sr / 44100 samples, at least 64 from 12544 Hz: lower rates are refused) covers a 64-sample block, so one wave per clip renders 64 samples per
 // iteration; the one-pole damping filter inside a comb is a one-sample linear recurrence = a 6-step wave scan.
 // All 12 delay buffers of a clip live in LDS.
 #define FX_RV_NC 8
@@ -742,7 +742,9 @@ extern "C" int rfx_fx_compressor(const float* x, float* y, float* env_ws, int32_
 }
 extern "C" int rfx_fx_reverb(const float* x, float* y, int32_t B, int64_t T, int32_t sample_rate, const float* damp,
                              const float* feedback, const float* wet1, const float* dry, void* stream) {
-  if (!fx_ok(x, y, B, T) || !damp || !feedback || !wet1 || !dry || sample_rate < 8000 || sample_rate > 192000) return -1;
+  // 12544 ... 143526 Hz: below, the shortest ring (225 * sr / 44100) is under one 64-sample block; above, the twelve rings
+  // (12587 * sr / 44100 floats) exceed 160 KB of LDS.  The per-ring and arena checks below are what decides.
+  if (!fx_ok(x, y, B, T) || !damp || !feedback || !wet1 || !dry || sample_rate < 12544 || sample_rate > 143526) return -1;
   static const int comb_t[FX_RV_NC] = {1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617};
   static const int ap_t[FX_RV_NA] = {556, 441, 341, 225};
   FxReverbArgs a{};
