@@ -660,8 +660,14 @@ int rfx_fft_synthesis_lossgrad(const rfx_stft_desc* d, const float* xspec, const
                                float w_lm, float eps, const float* gup, const float* window, float* ws, float* out, void* stream);
 /* g[i] = w * gup[0] * sign(a[i] - b[i])   (nn.L1Loss backward; gup as above, NULL = 1) */
 int rfx_l1_grad(const float* a, const float* b, int64_t n, float w, const float* gup, float* g, void* stream);
-/* per row: sums[r] = { sum x, sum t, sum x t, sum x^2, sum t^2 } in fp64 (auraloss SISDRLoss).  ws: 5 * R * RFX_SISDR_SLOTS doubles of
- * per-workgroup partials (no initialisation needed), added in slot order. */
+/* Every loss entry point that takes R rows of samples or spectra launches one grid row per signal row: R > RFX_LOSS_MAX_ROWS is
+ * refused with -1 and nothing launched (rfx_stft_loss_reduce / _grad / _grad_m, rfx_sisdr_sums, rfx_time_sums, rfx_time_loss_grad,
+ * rfx_logcosh_rows / _grad, rfx_stft_scaled_loss / _grad).  The one-wave tails (rfx_sisdr_finish, rfx_time_loss_rows, both combines)
+ * take any R. */
+#define RFX_LOSS_MAX_ROWS 65535
+/* per row: sums[r] = { sum x, sum t, sum x t, sum x^2, sum t^2 } in fp64 (auraloss SISDRLoss).  ws: per-workgroup partials (no
+ * initialisation needed), added in slot order.  The call writes 5 * R * g doubles of it, g = min(max(ceil(L / 2048), 1),
+ * RFX_SISDR_SLOTS) workgroups per row = rfx_time_sums_ws(R, L); 5 * R * RFX_SISDR_SLOTS doubles are enough for every L. */
 #define RFX_SISDR_SLOTS 128
 int rfx_sisdr_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs,
                    double* ws, double* sums, void* stream);
@@ -694,17 +700,21 @@ int rfx_time_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t 
                   double h_cur, double h_next, double* ws, double* sums, void* stream);
 /* From the row sums (kind LOGCOSH: sums [R][1] of rfx_logcosh_rows), in fp64: rows [R] fp32 = the per-row losses; coef [R][3] fp64
  * (may be NULL) = (a, b, c) with d loss_r / d x~[n] = a x~[n] + b t~[n] + c (zeros for LOGCOSH); out[0] = their mean / sum
- * (RFX_REDUCE_NONE: out untouched, may be NULL).  kind SISDR with RFX_REDUCE_MEAN returns the bits of rfx_sisdr_finish. */
+ * (RFX_REDUCE_NONE: out untouched, may be NULL; otherwise out == NULL is refused).  kind SISDR with RFX_REDUCE_MEAN returns the bits
+ * of rfx_sisdr_finish.  The residual energies Sxx' - 2 al Sxt' + al^2 Stt' and Sxx' - 2 Sxt' + Stt' are differences of fp64 sums: their
+ * rounding error is bounded by 6.2e-16 (Sxx + Stt), so res + eps stays positive while Sxx + Stt is below 1.6e7 at eps = 1e-8 (DESIGN.md
+ * 4.24; full scale at 262144 samples is 5.2e5). */
 int rfx_time_loss_rows(const double* sums, int32_t R, int64_t L, int32_t kind, int32_t zero_mean, double eps, int32_t reduction,
                        float* rows, double* coef, float* out, void* stream);
 /* gx [R][L] contiguous = g_r (h_prev u[n+1] + h_cur u[n] + h_next u[n-1]), u[m] = a_r x~[m] + b_r t~[m] + c_r inside the row, 0 outside
  * (without taps: g_r u[n]); every element formed in fp64 and rounded once.  g_r from gup on the device: gup[0] / R (MEAN), gup[0] (SUM),
- * gup[r] (NONE). */
+ * gup[r] (NONE).  gup is required; x, t and gx must be aligned to 4 bytes (-1 otherwise), any 16-byte phase is taken. */
 int rfx_time_loss_grad(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, const double* coef,
                        int32_t has_taps, double h_prev, double h_cur, double h_next, const float* gup, int32_t reduction, float* gx,
                        void* stream);
 /* sums [R] fp64 = sum_n log(cosh(a (x - t)) + eps) / a per row (ws: rfx_logcosh_ws(R, L) doubles, slots as above), then
- * rfx_time_loss_rows(kind LOGCOSH);  gx [R][L] = g_r sinh(a z) / (cosh(a z) + eps) / L with g_r as for rfx_time_loss_grad. */
+ * rfx_time_loss_rows(kind LOGCOSH);  gx [R][L] = g_r sinh(a z) / (cosh(a z) + eps) / L with g_r as for rfx_time_loss_grad.
+ * a > 0 is required (a <= 0 and NaN: -1); no |a z| overflows. */
 int64_t rfx_logcosh_ws(int32_t R, int64_t L);
 int rfx_logcosh_rows(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, double a, double eps, double* ws,
                      double* sums, void* stream);
@@ -735,7 +745,10 @@ int rfx_stft_scaled_loss(const float* xc, const float* yc, int32_t R, int32_t fr
  * dM = w_sc (Mx - My) / (sqrt(A) sqrt(B)) + (w_lm / Mx + w_lin) sign(Mx - My) with A, B of the row (per_example_sc) or of the batch.
  * fbt_idx [bins][3] / fbt_w: the band of the TRANSPOSED bank, { first filter, count, offset } per bin -- every bin gathers from its
  * (at most two, for a triangular bank) filters: no scatter, no atomics.  NULL: identity.  w_sc, w_lm, w_lin carry the 1 / nres,
- * 1 / R and 1 / (R n) factors; gup (may be NULL) as for rfx_stft_loss_grad.  gxc then goes through rfx_fft_synthesis. */
+ * 1 / R and 1 / (R n) factors; gup (may be NULL) as for rfx_stft_loss_grad.  gxc then goes through rfx_fft_synthesis.
+ * A frame's n_out dM values sit in LDS: n_out * 4 bytes must fit 160 KiB (-1 otherwise; -3 if the runtime refuses the raised limit
+ * above 64 KiB).  A filter with an empty band has Mx = My = 0 and a non-finite dM: the bins whose transposed band lists it get a
+ * non-finite gradient, all others are unaffected (the shipped mel banks have no empty row). */
 int rfx_stft_scaled_loss_grad(const float* xc, const float* mx, const float* my, int32_t R, int32_t frames, int32_t bins,
                               const int32_t* fbt_idx, const float* fbt_w, int32_t n_out, float eps, const double* sums,
                               int32_t per_example_sc, float w_sc, float w_lm, float w_lin, const float* gup, float* gxc, void* stream);

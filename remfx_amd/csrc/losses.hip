@@ -331,7 +331,7 @@ static int grid_red(int64_t n) {
 
 extern "C" int rfx_stft_loss_reduce(const float* xc, const float* yc, int32_t R, int64_t n, float eps, double* ws,
                                     float* sums, void* stream) {
-  if (!xc || !yc || !sums || !ws || R <= 0 || n <= 0) return -1;
+  if (!xc || !yc || !sums || !ws || R <= 0 || R > RFX_LOSS_MAX_ROWS || n <= 0) return -1;
   const int g = grid_red(n);                                                 // <= RFX_STFT_REDUCE_SLOTS
   hipLaunchKernelGGL(stft_loss_reduce_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)xc, (const float2*)yc, n, eps, ws);
@@ -342,7 +342,7 @@ extern "C" int rfx_stft_loss_reduce(const float* xc, const float* yc, int32_t R,
 }
 extern "C" int rfx_stft_loss_grad(const float* xc, const float* yc, int32_t R, int64_t n, float eps,
                                   const float* sums, float w_sc, float w_lm, const float* gup, float* gxc, void* stream) {
-  if (!xc || !yc || !sums || !gxc || R <= 0 || n <= 0) return -1;
+  if (!xc || !yc || !sums || !gxc || R <= 0 || R > RFX_LOSS_MAX_ROWS || n <= 0) return -1;
   hipLaunchKernelGGL(stft_loss_grad_kernel, dim3(grid_x(n), R), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)xc, (const float2*)yc, (const float*)nullptr, n, eps, sums, w_sc, w_lm, gup, (float2*)gxc);
   RFX_CHECK_LAUNCH();
@@ -350,7 +350,7 @@ extern "C" int rfx_stft_loss_grad(const float* xc, const float* yc, int32_t R, i
 }
 extern "C" int rfx_stft_loss_grad_m(const float* xc, const float* ymag, int32_t R, int64_t n, float eps,
                                     const float* sums, float w_sc, float w_lm, const float* gup, float* gxc, void* stream) {
-  if (!xc || !ymag || !sums || !gxc || R <= 0 || n <= 0) return -1;
+  if (!xc || !ymag || !sums || !gxc || R <= 0 || R > RFX_LOSS_MAX_ROWS || n <= 0) return -1;
   hipLaunchKernelGGL(stft_loss_grad_kernel, dim3(grid_x(n), R), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)xc, (const float2*)nullptr, ymag, n, eps, sums, w_sc, w_lm, gup, (float2*)gxc);
   RFX_CHECK_LAUNCH();
@@ -364,7 +364,7 @@ extern "C" int rfx_l1_grad(const float* a, const float* b, int64_t n, float w, c
 }
 extern "C" int rfx_sisdr_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs,
                               int64_t t_rs, double* ws, double* sums, void* stream) {
-  if (!x || !t || !sums || !ws || R <= 0 || L <= 0) return -1;
+  if (!x || !t || !sums || !ws || R <= 0 || R > RFX_LOSS_MAX_ROWS || L <= 0) return -1;
   int g = grid_x(L);
   g = g > RFX_SISDR_SLOTS ? RFX_SISDR_SLOTS : g;
   hipLaunchKernelGGL(sisdr_sums_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream, x, t, L, x_rs, t_rs, ws);
@@ -399,7 +399,7 @@ extern "C" int64_t rfx_stft_scaled_loss_ws(int32_t R, int32_t frames) {
 extern "C" int rfx_stft_scaled_loss(const float* xc, const float* yc, int32_t R, int32_t frames, int32_t bins, const int32_t* fb_idx,
                                     const float* fb_w, int32_t n_out, int32_t n_w, float eps, double* ws, double* sums, float* mx,
                                     float* my, void* stream) {
-  if (!xc || !yc || !sums || !ws || R <= 0 || frames <= 0 || bins <= 0 || (!mx) != (!my)) return -1;
+  if (!xc || !yc || !sums || !ws || R <= 0 || R > RFX_LOSS_MAX_ROWS || frames <= 0 || bins <= 0 || (!mx) != (!my)) return -1;
   if (fb_idx ? (!fb_w || n_out <= 0 || n_w <= 0) : (n_out != bins)) return -1;
   const size_t lds = fb_idx ? scaled_lds(bins, n_w) : 0;
   if (lds > RFX_SCALED_LDS_MAX) return -1;
@@ -415,7 +415,7 @@ extern "C" int rfx_stft_scaled_loss_grad(const float* xc, const float* mx, const
                                          const int32_t* fbt_idx, const float* fbt_w, int32_t n_out, float eps, const double* sums,
                                          int32_t per_example_sc, float w_sc, float w_lm, float w_lin, const float* gup, float* gxc,
                                          void* stream) {
-  if (!xc || !mx || !my || !sums || !gxc || R <= 0 || frames <= 0 || bins <= 0 || n_out <= 0) return -1;
+  if (!xc || !mx || !my || !sums || !gxc || R <= 0 || R > RFX_LOSS_MAX_ROWS || frames <= 0 || bins <= 0 || n_out <= 0) return -1;
   if (fbt_idx ? !fbt_w : (n_out != bins)) return -1;
   const size_t lds = (size_t)n_out * sizeof(float);
   if (lds > RFX_SCALED_LDS_MAX) {
@@ -555,7 +555,7 @@ __global__ __launch_bounds__(64) void time_loss_rows_kernel(const double* __rest
     if (coef) { coef[3 * r] = ca; coef[3 * r + 1] = cb; coef[3 * r + 2] = cc; }
   }
   acc = rfx_wave_sum_d(acc);
-  if (lane == 0 && out) {
+  if (lane == 0 && out && reduction != RFX_REDUCE_NONE) {   // "none": out stays untouched, as the header promises
     const double tot = logk ? -acc : acc;
     out[0] = (float)(reduction == RFX_REDUCE_MEAN ? tot / (double)R : tot);
   }
@@ -731,7 +731,7 @@ extern "C" int64_t rfx_time_sums_ws(int32_t R, int64_t L) {
 }
 extern "C" int rfx_time_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, int32_t has_taps,
                              double h_prev, double h_cur, double h_next, double* ws, double* sums, void* stream) {
-  if (!x || !t || !sums || !ws || R <= 0 || L <= 0) return -1;
+  if (!x || !t || !sums || !ws || R <= 0 || R > RFX_LOSS_MAX_ROWS || L <= 0) return -1;
   const int g = time_sums_grid(L);                       // the grid of rfx_sisdr_sums: without taps, its kernel and its bits
   if (has_taps)
     hipLaunchKernelGGL(time_sums_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream, x, t, L, x_rs, t_rs, h_prev, h_cur, h_next, ws);
@@ -754,7 +754,7 @@ extern "C" int rfx_time_loss_rows(const double* sums, int32_t R, int64_t L, int3
 extern "C" int rfx_time_loss_grad(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, const double* coef,
                                   int32_t has_taps, double h_prev, double h_cur, double h_next, const float* gup, int32_t reduction,
                                   float* gx, void* stream) {
-  if (!x || !t || !coef || !gup || !gx || R <= 0 || L <= 0 || !time_red_ok(reduction)) return -1;
+  if (!x || !t || !coef || !gup || !gx || R <= 0 || R > RFX_LOSS_MAX_ROWS || L <= 0 || !time_red_ok(reduction)) return -1;
   if ((((uintptr_t)x | (uintptr_t)t | (uintptr_t)gx) & 3) != 0) return -1;
   TimeGradArgs p;
   p.x = x; p.t = t; p.gx = gx; p.coef = coef; p.gup = gup; p.L = L; p.xs = x_rs; p.ts = t_rs;
@@ -771,7 +771,7 @@ extern "C" int64_t rfx_logcosh_ws(int32_t R, int64_t L) {
 }
 extern "C" int rfx_logcosh_rows(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, double a, double eps,
                                 double* ws, double* sums, void* stream) {
-  if (!x || !t || !sums || !ws || R <= 0 || L <= 0 || !(a > 0.0)) return -1;
+  if (!x || !t || !sums || !ws || R <= 0 || R > RFX_LOSS_MAX_ROWS || L <= 0 || !(a > 0.0)) return -1;
   const int g = time_sums_grid(L);
   hipLaunchKernelGGL(logcosh_rows_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream, x, t, L, x_rs, t_rs, a, eps, ws);
   RFX_CHECK_LAUNCH();
@@ -781,7 +781,7 @@ extern "C" int rfx_logcosh_rows(const float* x, const float* t, int32_t R, int64
 }
 extern "C" int rfx_logcosh_grad(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs, double a, double eps,
                                 const float* gup, int32_t reduction, float* gx, void* stream) {
-  if (!x || !t || !gup || !gx || R <= 0 || L <= 0 || !(a > 0.0) || !time_red_ok(reduction)) return -1;
+  if (!x || !t || !gup || !gx || R <= 0 || R > RFX_LOSS_MAX_ROWS || L <= 0 || !(a > 0.0) || !time_red_ok(reduction)) return -1;
   hipLaunchKernelGGL(logcosh_grad_kernel, dim3(time_stream_grid(L, R), R), dim3(256), 0, (hipStream_t)stream, x, t, R, L, x_rs, t_rs, a,
                      eps, gup, reduction, gx);
   RFX_CHECK_LAUNCH();
