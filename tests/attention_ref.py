@@ -24,7 +24,7 @@ import math
 
 import torch
 
-from tests.lstm_ref import FLIP_PERTURB, FLOOR_PERTURB, MARGIN, bf16_rne
+from tests.ref_common import bf16_rne, ulp
 
 RULES = ("exact", "bf16")
 # name -> rule sets it applies to
@@ -185,6 +185,7 @@ def sizes(ref):
     return float(ref.double().norm()), float(ref.double().abs().max())
 
 
+FLOOR_PERTURB, FLIP_PERTURB, MARGIN = 1e-7, 1e-4, 8.0        # lstm_ref.floors' construction, restated: its values and their meaning
 TINY = 2.0 ** -126                          # smallest normal fp32: sigmoid(-100) is 0 in fp32 and 4e-44 in fp64 (regime e, dqd)
 
 
@@ -194,7 +195,7 @@ def bound(floor):
 
 def _ulp_bf16(x):
     a = x.abs().double()
-    return torch.where(a > 0, torch.exp2(torch.floor(torch.log2(a.clamp_min(1e-300))) - 7), torch.zeros_like(a))
+    return torch.where(a > 0, ulp(a, 7, 1e-300), torch.zeros_like(a))
 
 
 def _flip_allowance(ref, q, k, cont, gout, heads, rules_round):

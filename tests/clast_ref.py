@@ -17,7 +17,7 @@ in: it adds half a bf16 ulp of that value times the derivative of what follows (
 store + res).
 
 BOUND.  Per element |got - ref| <= K eps32 magnitude (+ half a bf16 ulp of the value being rounded per 16-bit store), against the
-unrounded fp64 value; K = 8 floor + 8 (norm_ref.k_of).  magnitude = conv(|a|, |b|) + |bias| + |res| pushed through GELU / GLU and
+unrounded fp64 value; K = 8 floor + 8 (k_of).  magnitude = conv(|a|, |b|) + |bias| + |res| pushed through GELU / GLU and
 their backward with the derivative weights of 4.15 (cdf = 0.5 + 0.5 |erf|, 1 - sigmoid = 1 + sigmoid).  floor = an fp32 RESTATEMENT
 on the CPU against this reference, never a kernel: restate_conv / restate_wgrad / restate_rowsum below; FLOORS holds them."""
 import contextlib
@@ -27,7 +27,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-from tests.norm_ref import EPS32, bf16_rne, k_of, worst  # noqa: F401
+from tests.kernel_harness import GUARD, Arena  # noqa: F401
+from tests.ref_common import EPS32, bf16_rne, ulp16, worst  # noqa: F401
 
 SQRT1_2 = 0.7071067811865476
 
@@ -43,14 +44,9 @@ def bf_trunc(t):
     return (u & -65536).view(torch.float32).double()
 
 
-def _ulp16(v):
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
-    return torch.exp2(e - 7)
-
-
 def half16(val, t):
     """half a bf16 ulp of the value a kernel rounded: it is within t of val"""
-    return 0.5 * _ulp16(val.abs() + t)
+    return 0.5 * ulp16(val.abs() + t)
 
 
 def cdf(u):
@@ -600,7 +596,7 @@ def restate_conv(case, inp, form, mutate=None):
             if k != "cm":
                 flat = out[k].clone().reshape(-1)
                 i = int(flat.abs().argmax())
-                flat[i] = flat[i] + _ulp16(flat[i].double()).float()
+                flat[i] = flat[i] + ulp16(flat[i].double()).float()
                 out[k] = flat.view(out[k].shape)
     return {k: t.to(f32) for k, t in out.items()}
 
@@ -921,6 +917,11 @@ FLOORS = {
 }
 
 
+def k_of(floor):
+    """the bound in units of eps32 * magnitude: 8 x floor + 16 fp32 half-ulps"""
+    return 8.0 * floor + 8.0
+
+
 def K_conv(case):
     return k_of(FLOORS[case.mode])
 
@@ -1004,41 +1005,13 @@ def recorder(dry_run, splits=None):
         _lib.lib, ops.raw_stream, clast.cl_tensor, clast.TRACE, clast.CLW_SPLITS = saved
 
 
-GUARD = 4096
-
-
-class Arena:
-    """output buffers of the GPU test: NaN-filled body (or `fill`) between two NaN guards of GUARD elements"""
-
-    def __init__(self, dev):
-        self.dev, self.bufs = dev, []
-
-    def alloc(self, shape, dtype, fill=None):
-        n = 1
-        for s in shape:
-            n *= s
-        buf = torch.full((n + 2 * GUARD,), float("nan"), device=self.dev, dtype=dtype)
-        body = buf[GUARD:GUARD + n]
-        if fill is not None:
-            body.fill_(fill)
-        self.bufs.append((buf, n))
-        return body.view(shape)
-
-    def intact(self):
-        return all(bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + n:]).all()) for buf, n in self.bufs)
-
-    def check(self):
-        assert self.intact(), "guard overwritten"
-
-
 def store_guarded(out_cm, rows, arena, stray_wins):
     """What the GPU test would fetch had a kernel stored the channel-major result out_cm (N, C, rows [+ stray rows], B) into the test's dense
     guarded channels-last buffer of `rows` rows per sample: a row past the last lands on row 0 of the next sample -- it races with that row's
     own store, `stray_wins` says who comes last -- and, from the last sample, on the guard behind the buffer.  -> the fetched (N, C, rows, B)"""
     N, C, R, B = out_cm.shape
     body = arena.alloc((N, rows, B, C), torch.float32)
-    buf, n = arena.bufs[-1]
-    flat = buf[GUARD:]                                              # body + the guard behind it
+    flat = arena.bufs[-1].buf[GUARD:]                                              # body + the guard behind it
     x = cl(out_cm.float())
     for first in ((False, True) if stray_wins else (True, False)):  # pass 1 then pass 2: the later store stays
         for nn in range(N):

@@ -32,7 +32,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from tests.norm_ref import EPS32, bf16_rne, k_of, worst  # noqa: F401
+from tests.ref_common import EPS32, bf16_rne, bf16_trunc, gelu_cdf, gelu_pdf, ulp, worst  # noqa: F401
 
 T = 256
 GEN_EPS = 1e-5
@@ -55,18 +55,8 @@ MUTATIONS = (
 )
 
 
-def _ulp(v, mant):
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
-    return torch.exp2(e - mant)
-
-
 def _half_ulp16(ref, t):
-    return 0.5 * _ulp(ref.abs() + t, 7)
-
-
-def bf16_trunc(x):
-    u = x.to(torch.float32).contiguous().view(torch.int32)
-    return (u & -65536).view(torch.float32).to(x.dtype)
+    return 0.5 * ulp(ref.abs() + t, 7)
 
 
 # ---- the two arithmetics ---------------------------------------------------------------------------------------------------------------
@@ -189,14 +179,6 @@ def _conv_t(dh, W, dil):
     return out
 
 
-def _cdf(u):
-    return 0.5 * (1.0 + torch.erf(u * (0.5 ** 0.5)))
-
-
-def _pdf(u):
-    return torch.exp(-0.5 * u * u) * (1.0 / math.sqrt(2.0 * math.pi))
-
-
 def stats(t, eps=GEN_EPS):
     """fp64 mean, rstd per sample of (N, L, Cn), two-pass variance: the truth, not the algorithm"""
     r = t.double().reshape(t.shape[0], -1)
@@ -260,7 +242,7 @@ def forward(inp, dil, ar=Exact, rounding=True, stats1=None, a_in=None, stats2=No
         m1, r1 = c(stats1[0]), c(stats1[1])
     hh = h * _b(r1) + _b(-m1 * r1)
     u = hh * g1w + g1b
-    o["a_pre"] = u * _cdf(u)
+    o["a_pre"] = u * gelu_cdf(u)
     o["a"] = rnd(o["a_pre"])
     a = o["a"] if a_in is None else c(a_in)
     z = a @ W2.transpose(0, 1) + b2
@@ -288,14 +270,14 @@ def forward(inp, dil, ar=Exact, rounding=True, stats1=None, a_in=None, stats2=No
     if mutate == "one_ulp":
         o["y"] = o["y"].clone()
         e = o["y"][N - 1, L // 2, Cc // 3]
-        o["y"][N - 1, L // 2, Cc // 3] = e + _ulp(e.double(), 7).to(ar.dtype)
+        o["y"][N - 1, L // 2, Cc // 3] = e + ulp(e.double(), 7).to(ar.dtype)
     if ar is Exact:
         mh = _conv(x.abs(), W1.abs(), dil) + b1.abs()
         o["mag:hpre"] = mh
         o["mag:mean1"], o["mag:rstd1"] = stat_mag(h, mh, eps)
         Au = (mh + _b(m1.abs())) * _b(r1) * g1w.abs() + g1b.abs()
         cdfm = 0.5 + 0.5 * torch.erf(u.abs() * (0.5 ** 0.5))
-        o["mag:a"] = Au * (2.0 * cdfm + u.abs() * _pdf(u))
+        o["mag:a"] = Au * (2.0 * cdfm + u.abs() * gelu_pdf(u))
         mz = a.abs() @ W2.abs().transpose(0, 1) + b2.abs()
         o["mag:mean2"], o["mag:rstd2"] = stat_mag(z, mz, eps)
         Az = (mz + _b(m2.abs())) * _b(r2)
@@ -349,7 +331,7 @@ def backward(inp, sv, dil, passes, ar=Exact, rounding=True, dz_in=None, dh_in=No
         da = dz @ W2
         hh = hpre * _b(r1) + _b(-m1 * r1)
         u = hh * g1w + g1b
-        gp = _cdf(u) + u * _pdf(u)
+        gp = gelu_cdf(u) + u * gelu_pdf(u)
         dhn = da * gp
         q_pre = dhn * g1w
         q = rnd(q_pre) if passes else q_pre
@@ -374,7 +356,7 @@ def backward(inp, sv, dil, passes, ar=Exact, rounding=True, dz_in=None, dh_in=No
     if mutate == "one_ulp":
         o["dx"] = o["dx"].clone()
         e = o["dx"][N - 1, L // 2, Cc // 3]
-        o["dx"][N - 1, L // 2, Cc // 3] = e + _ulp(e.double(), 7).to(ar.dtype)
+        o["dx"][N - 1, L // 2, Cc // 3] = e + ulp(e.double(), 7).to(ar.dtype)
     f2 = lambda t: t.reshape(-1, t.shape[-1])                   # noqa: E731
     o["dw2"] = f2(dzk).transpose(0, 1) @ f2(a)
     o["db2"] = f2(dzk).sum(0)
@@ -396,14 +378,14 @@ def backward(inp, sv, dil, passes, ar=Exact, rounding=True, dz_in=None, dh_in=No
         M1 = mp.reshape(N, -1).mean(1)
         M2 = (mp * zh.abs() + p.abs() * Az).reshape(N, -1).mean(1)
         o["mag:dz"] = _b(r2) * (mp + _b(M1) + zh.abs() * _b(M2) + Az * _b(pm2.abs()))
-        o["park:dz"] = _b(r2) * 0.5 * _ulp(p_pre, 7) if rounding else torch.zeros_like(p)
+        o["park:dz"] = _b(r2) * 0.5 * ulp(p_pre, 7) if rounding else torch.zeros_like(p)
 
         def hidden_mag(r, dz):
             mda = dz.abs() @ W2.abs()
             hh, u = r["hh"], r["u"]
             Ah = (hpre.abs() + _b(m1.abs())) * _b(r1)
             Au = Ah * g1w.abs() + g1b.abs()
-            pdf = _pdf(u)
+            pdf = gelu_pdf(u)
             cdfm = 0.5 + 0.5 * torch.erf(u.abs() * (0.5 ** 0.5))
             mdhn = mda * (cdfm + u.abs() * pdf) + r["da"].abs() * pdf * (2.0 - u * u).abs() * Au
             mq = mdhn * g1w.abs()
@@ -413,10 +395,10 @@ def backward(inp, sv, dil, passes, ar=Exact, rounding=True, dz_in=None, dh_in=No
                     _b(r1) * (mq + _b(Q1) + hh.abs() * _b(Q2) + Ah * _b(r["qm2"].abs())))
         o["mag:dgn1b"], o["mag:dgn1w"], _ = hidden_mag(own, o["dz"])
         _, _, o["mag:dh"] = hidden_mag(hd, dzk)
-        o["park:dh"] = _b(r1) * 0.5 * _ulp(hd["q_pre"], 7) if (passes and rounding) else torch.zeros_like(hd["q"])
+        o["park:dh"] = _b(r1) * 0.5 * ulp(hd["q_pre"], 7) if (passes and rounding) else torch.zeros_like(hd["q"])
         o["mag:dx"] = gy.abs() + _conv_t(dhk.abs(), W1.abs(), dil)
         if passes and rounding:
-            o["park:dx"] = 0.5 * _ulp(cv, 7)
+            o["park:dx"] = 0.5 * ulp(cv, 7)
         o["mag:dw2"] = f2(dzk.abs()).transpose(0, 1) @ f2(a.abs())
         o["mag:db2"] = f2(dzk.abs()).sum(0)
         xa = xp.abs()
@@ -525,6 +507,11 @@ FLOORS = {
     "bwd-sat": {"dz": 0.25, "dh": 0.25, "dx": 0.25, "dw2": 38.75, "db2": 0.5, "dw1": 1.5, "db1": 0.25, "dscale": 0.25, "dgn2w": 0.25,
                 "dgn2b": 0.25, "dgn1w": 10.0, "dgn1b": 5.75},
 }
+
+
+def k_of(floor):
+    """the bound in units of eps32 * magnitude: 8 x floor + 16 fp32 half-ulps"""
+    return 8.0 * floor + 8.0
 
 
 def K_of(case):

@@ -23,7 +23,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-EPS32 = 2.0 ** -23
+from tests.ref_common import EPS32, f32, worst  # noqa: F401
+
 CHUNK = 4096                      # CX_CHUNK
 MARGIN = 8.0
 FP32_HALF_ULPS = 16
@@ -35,22 +36,8 @@ GRID_CAP = 4096 * 1024            # cx_grid: 4096 workgroups x 256 threads x 4 -
 MASK_SMALL = 1e-2                 # below it tanh(a) / a and its derivative come from series (no cancelling quotient)
 
 
-def f32(v):
-    """the value a C float argument carries, as a Python double"""
-    return float(torch.tensor(v, dtype=torch.float32))
-
-
 def k_of(floor):
     return MARGIN * floor + FP32_HALF_ULPS / 2
-
-
-def worst(got, ref, tol):
-    """(error / tolerance, flat index) of the worst element; NaN / inf count as infinitely wrong"""
-    e = (got.double() - ref).abs()
-    q = torch.where(torch.isfinite(e), e / tol.clamp_min(1e-300), torch.full_like(e, float("inf")))
-    q = torch.where((e == 0) & (tol == 0), torch.zeros_like(q), q)
-    i = int(q.reshape(-1).argmax()) if q.numel() else 0
-    return (float(q.reshape(-1)[i]) if q.numel() else 0.0), i
 
 
 def floor_of(x32, ref, mag, slack=0.0):

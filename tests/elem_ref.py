@@ -24,7 +24,8 @@ import math
 import numpy as np
 import torch
 
-EPS32 = 2.0 ** -23
+from tests.ref_common import EPS32, f32  # noqa: F401
+
 HALF = 2.0 ** -24
 TINY = 2.0 ** -149
 MINNORM = 2.0 ** -126             # 1 / (1 + expf(-v)) returns 0 once expf overflows: results below the smallest normal are not formed
@@ -43,10 +44,6 @@ FLOOR = {"gelu": 5.0, "gelu_grad": 4.5, "tanh": 1.0, "tanh_grad": 1.0, "sigmoid"
 
 def k_of(name):
     return 8.0 * FLOOR[name] + 8.0
-
-
-def f32(v):
-    return float(np.float32(v))
 
 
 # ---- activations -------------------------------------------------------------------------------------------------------------------

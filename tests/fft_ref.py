@@ -27,8 +27,8 @@ import numpy as np
 import torch
 
 from tests import fft_any_ref
+from tests.ref_common import EPS32, f32  # noqa: F401
 
-EPS32 = 2.0 ** -23
 HALF = 2.0 ** -24
 COMPLEX, CAC, MAG, POW, MAGPOW, FM = range(6)
 MODE_NAMES = ("complex", "cac", "mag", "pow", "magpow", "complex_fm")
@@ -54,10 +54,6 @@ def klass(kind, n_fft):
     if n_fft in FFT_SIZES:
         return kind + "_fft"
     return f"{kind}_any_{len(str(n_fft)) - 1}"
-
-
-def f32(v):
-    return float(np.float32(v))
 
 
 # ---- descriptor --------------------------------------------------------------------------------------------------------------------

@@ -27,12 +27,12 @@ Staged outputs (judged from the kernel's OWN stored values, as DESIGN.md 4.16): 
 `mutate` (restate_*): a deliberately wrong kernel, what the bound has to reject (tests/test_gemm_ref_cpu.py)."""
 import contextlib
 import dataclasses
-import math
 
 import torch
 import torch.nn.functional as F
 
-EPS32 = 2.0 ** -23
+from tests.ref_common import EPS32, bf16_rne, bf16_trunc, gelu_cdf, gelu_pdf, ulp, worst  # noqa: F401
+
 MARGIN = 8.0
 EXTRA = 8.0                       # in units of eps32 magnitude: the undocumented order inside an MFMA, v_exp / v_rcp at 1 ulp, the erf polynomial
 SIGN_SHARE = 1e-3                 # at most this share of a case's elements may carry sign-flip slack
@@ -40,22 +40,6 @@ ACTS = ("relu", "gelu", "tanh", "prelu", "leaky", "sigmoid")
 
 
 # ---- number formats -------------------------------------------------------------------------------------------------------------------
-def bf16_rne(x):
-    """nearest bf16, ties to even, of the fp32 value of x, in the dtype of x"""
-    u = x.to(torch.float32).contiguous().view(torch.int32)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) & -65536).view(torch.float32).to(x.dtype)
-
-
-def bf16_trunc(x):
-    u = x.to(torch.float32).contiguous().view(torch.int32)
-    return (u & -65536).view(torch.float32).to(x.dtype)
-
-
-def _ulp(v, mant):
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
-    return torch.exp2(e - mant)
-
-
 def arith(mode, gathered_channels, rows, merged=False, wgrad=False):
     """arithmetic a launch runs in: exact fp32 below 8 gathered channels (no tap-major table) and on the thin path"""
     if wgrad:
@@ -116,14 +100,6 @@ def bilinear(op, a, b, ar, drop=None):
     return val, mag
 
 
-def _cdf(u):
-    return 0.5 * (1.0 + torch.erf(u * (0.5 ** 0.5)))
-
-
-def _pdf(u):
-    return torch.exp(-0.5 * u * u) * (1.0 / math.sqrt(2.0 * math.pi))
-
-
 def act_fwd(u, A, act, slope=None):
     """(act(u), magnitude) -- A = magnitude of u"""
     if act is None:
@@ -135,7 +111,7 @@ def act_fwd(u, A, act, slope=None):
         return torch.where(u >= 0, u, s * u), torch.where(u >= 0, A, s.abs() * A)
     if act == "gelu":
         cdfm = 0.5 + 0.5 * torch.erf(u.abs() * (0.5 ** 0.5))
-        return u * _cdf(u), A * (2.0 * cdfm + u.abs() * _pdf(u))
+        return u * gelu_cdf(u), A * (2.0 * cdfm + u.abs() * gelu_pdf(u))
     if act == "tanh":
         t = torch.tanh(u)
         return t, t.abs() + (1.0 - t * t) * A
@@ -153,9 +129,9 @@ def act_bwd(u, A, G, act, slope=None):
         d = torch.where(pos, torch.ones_like(u), s.expand_as(u))
         return G * d, (G * d).abs(), (G.abs() * (1.0 - s).abs(), A)
     if act == "gelu":
-        pdf = _pdf(u)
+        pdf = gelu_pdf(u)
         cdfm = 0.5 + 0.5 * torch.erf(u.abs() * (0.5 ** 0.5))
-        return G * (_cdf(u) + u * pdf), G.abs() * (cdfm + u.abs() * pdf + pdf * (2.0 - u * u).abs() * A), None
+        return G * (gelu_cdf(u) + u * pdf), G.abs() * (cdfm + u.abs() * pdf + pdf * (2.0 - u * u).abs() * A), None
     if act == "tanh":
         t = torch.tanh(u)
         return G * (1.0 - t * t), G.abs() * (1.0 + t * t + 2.0 * t.abs() * (1.0 - t * t) * A), None
@@ -663,17 +639,8 @@ def tolerance(r, K):
     if r.slack is not None:
         t = t + r.slack
     if r.store16:
-        t = t + 0.5 * _ulp(r.ref.abs() + t, 7)                      # RNE store: half a bf16 ulp of the value the kernel rounded
+        t = t + 0.5 * ulp(r.ref.abs() + t, 7)                      # RNE store: half a bf16 ulp of the value the kernel rounded
     return t
-
-
-def worst(got, ref, tol):
-    """(error / tolerance, flat index) of the worst element; NaN counts as infinitely wrong"""
-    e = (got.double() - ref).abs()
-    q = torch.where(torch.isfinite(e), e / tol.clamp_min(1e-300), torch.full_like(e, float("inf")))
-    q = torch.where((e == 0) & (tol == 0), torch.zeros_like(q), q)
-    i = int(q.reshape(-1).argmax()) if q.numel() else 0
-    return (float(q.reshape(-1)[i]) if q.numel() else 0.0), i
 
 
 def measure(case, inp, got):
@@ -685,7 +652,7 @@ def measure(case, inp, got):
         if r.slack is not None:
             e = e - r.slack
         if r.store16:
-            e = e - 0.5 * _ulp(r.ref.abs() + e, 7)
+            e = e - 0.5 * ulp(r.ref.abs() + e, 7)
         fl[k] = float((e / (EPS32 * r.mag).clamp_min(1e-300)).clamp_min(0).max())
     return fl
 

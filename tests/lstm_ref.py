@@ -18,6 +18,8 @@ multiplied by 1 + perturb * N(0, 1) -- a model of 1-ulp exp / rcp and of another
 `mutate`: one of MUTATIONS, a deliberately wrong recurrence (the faults the tight bound of the GPU tests has to see)."""
 import torch
 
+from tests.ref_common import bf16_rne, bf16_trunc  # noqa: F401
+
 MODES = ("exact", "bf16", "bf16x3")
 # name -> modes it applies to, sweeps it applies to
 MUTATIONS = {
@@ -38,16 +40,6 @@ def _f32_bits(x):
 
 def _from_bits(u, like):
     return u.view(torch.float32).to(like.dtype)
-
-
-def bf16_rne(x):
-    """nearest bf16, ties to even (lstm_bf16_rne, v_cvt_pk_bf16_f32), of the fp32 value of x"""
-    u = _f32_bits(x)
-    return _from_bits((u + 0x7FFF + ((u >> 16) & 1)) & -65536, x)
-
-
-def bf16_trunc(x):
-    return _from_bits(_f32_bits(x) & -65536, x)
 
 
 def split_w(w):

@@ -20,13 +20,13 @@ The bound of every output is  K * eps32 * magnitude (+ slack),  K = MARGIN * flo
 
 `mutate`: one of MUTATIONS, a deliberately wrong kernel (what the bound has to see; tests/test_norm_ref_cpu.py)."""
 import dataclasses
-import math
 
 import torch
 import torch.nn.functional as F
 
+from tests.ref_common import EPS32, bf16_rne, gelu_cdf, gelu_pdf, ulp, worst  # noqa: F401
+
 MODES = {"none": 0, "gelu": 1, "glu": 2, "glu_scale_res": 3, "relu": 4}
-EPS32 = 2.0 ** -23
 CHUNK = 4096                      # GN_CHUNK
 MARGIN = 8.0
 FP32_HALF_ULPS = 16               # as tests/lstm_ref.py: 16 fp32 half-ulps = 8 eps32 for what a CPU fp32 evaluation does not have --
@@ -49,18 +49,6 @@ MUTATIONS = (
 
 def is_glu(mode):
     return mode in ("glu", "glu_scale_res")
-
-
-def bf16_rne(x):
-    """nearest bf16, ties to even, of the fp32 value of x (what rfx_st1 / rfx_st4 store)"""
-    u = x.to(torch.float32).contiguous().view(torch.int32)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) & -65536).view(torch.float32).to(x.dtype)
-
-
-def _ulp(v, mant):
-    """spacing of a format with `mant` explicit mantissa bits at |v| (fp64 tensor)"""
-    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
-    return torch.exp2(e - mant)
 
 
 # ---- sums: exact (fp64) and the kernels' decomposition in fp32 --------------------------------------------------------------------
@@ -214,14 +202,6 @@ def _pre(x, gamma, beta, mean, rstd, kind, G, mutate=None):
     return xh, u, r
 
 
-def _cdf(u):
-    return 0.5 * (1.0 + torch.erf(u * (0.5 ** 0.5)))
-
-
-def _pdf(u):
-    return torch.exp(-0.5 * u * u) * (1.0 / math.sqrt(2.0 * math.pi))
-
-
 def forward(x, gamma, beta, mean, rstd, mode="none", res=None, scale=None, kind="gn", G=1, mutate=None, prefill=0.0):
     """y in the dtype of x: (N, C, S), GLU modes (N, C / 2, S)"""
     assert mode in MODES and (mutate is None or mutate in MUTATIONS)
@@ -232,7 +212,7 @@ def forward(x, gamma, beta, mean, rstd, mode="none", res=None, scale=None, kind=
     elif mode == "relu":
         y = u.clamp_min(0)
     elif mode == "gelu":
-        y = u * _cdf(u)
+        y = u * gelu_cdf(u)
     else:
         ua, ub = u[:, :C // 2], u[:, C // 2:]
         if mutate == "glu_halves_swapped":
@@ -266,8 +246,8 @@ def _du(x, gamma, beta, mean, rstd, gy, mode, scale, kind, G, mutate, want_mag):
             mdu = du.abs()
             slack = gy.abs() * (u.abs() <= U_BAND * EPS32 * A).to(x.dtype)
     elif mode == "gelu":
-        pdf = _pdf(u)
-        du = gy * (_cdf(u) + u * pdf)
+        pdf = gelu_pdf(u)
+        du = gy * (gelu_cdf(u) + u * pdf)
         if want_mag:
             cdfm = 0.5 + 0.5 * torch.erf(u.abs() * (0.5 ** 0.5))
             mdu = gy.abs() * (cdfm + u.abs() * pdf + pdf * (2.0 - u * u).abs() * A)
@@ -341,7 +321,7 @@ def magnitudes(x, gamma, beta, mean, rstd, mode="none", res=None, scale=None, gy
         my = A
     elif mode == "gelu":
         cdfm = 0.5 + 0.5 * torch.erf(u.abs() * (0.5 ** 0.5))
-        my = A * (2.0 * cdfm + u.abs() * _pdf(u))
+        my = A * (2.0 * cdfm + u.abs() * gelu_pdf(u))
     else:
         Co = C // 2
         sg = torch.sigmoid(u[:, Co:])
@@ -393,17 +373,8 @@ def tolerance(name, ref, mag, slack, fl, x16=False):
     """absolute tolerance per element of output `name`"""
     t = k_of(fl[name]) * EPS32 * mag[name] + slack.get(name, 0.0)
     if x16 and name == "dx":
-        t = t + 0.5 * _ulp(ref[name].abs() + t, 7)             # RNE store: half a bf16 ulp of the value the kernel rounded
+        t = t + 0.5 * ulp(ref[name].abs() + t, 7)             # RNE store: half a bf16 ulp of the value the kernel rounded
     return t
-
-
-def worst(got, ref, tol):
-    """(error / tolerance, flat index) of the worst element; NaN counts as infinitely wrong"""
-    e = (got.double() - ref).abs()
-    q = torch.where(torch.isfinite(e), e / tol.clamp_min(1e-300), torch.full_like(e, float("inf")))
-    q = torch.where((e == 0) & (tol == 0), torch.zeros_like(q), q)
-    i = int(q.reshape(-1).argmax()) if q.numel() else 0
-    return (float(q.reshape(-1)[i]) if q.numel() else 0.0), i
 
 
 # ---- workspace sizes, restated from the header comment ------------------------------------------------------------------------------

@@ -23,18 +23,13 @@ Bounds, eps32 = 2^-23, one half-ulp = eps32 / 2 relative:
            test uses 4 x that count."""
 import math
 
-import torch
+from tests.ref_common import EPS32, f32  # noqa: F401
 
-EPS32 = 2.0 ** -23
 FP32_HALF_ULPS = 16
 SLOTS = 4096                      # RFX_SUMSQ_SLOTS
 HYPER = dict(betas=(0.95, 0.999), eps=1e-6, wd=1e-3)
 SUMSQ_N = (0, 1, 3, 4, 5, 1023, 1025, 4_194_304 + 1027)
 ADAMW_N = (1, 5, 1025, 4_194_304 + 1027)
-
-
-def f32(v):
-    return float(torch.tensor(v, dtype=torch.float32))
 
 
 def gridn(n):

@@ -336,7 +336,7 @@ def test_every_conv_case_has_power(case):
         assert float(v["tol32"].max()) <= 1e-3 * rms, (case.id, k, float(v["tol32"].max()) / rms)
         if k == "cm":
             continue
-        ulp = R._ulp16(ref)
+        ulp = R.ulp16(ref)
         miss = v["tol32"] >= 0.5 * ulp
         mag = v["tol32"] / (K * R.EPS32)
         below = mag < FOLD * ref.abs()

@@ -97,12 +97,12 @@ BRANCH_SHARE = {"y": 2.5, "dx": 12.5}
 
 def _power(ref, slack, mag, K, ceiling, what, at_rms=True):
     rms = float(ref.double().pow(2).mean().sqrt())
-    ulp = R._ulp(ref, 7)
+    ulp = R.ulp(ref, 7)
     miss = slack >= 0.5 * ulp
     share = 100.0 * float(miss.double().mean())
-    print(f"{what}: K {K:.0f}; slack / half an ulp at the RMS {float(slack.max()) / (0.5 * float(R._ulp(torch.tensor(rms), 7))):.3f}; "
+    print(f"{what}: K {K:.0f}; slack / half an ulp at the RMS {float(slack.max()) / (0.5 * float(R.ulp(torch.tensor(rms), 7))):.3f}; "
           f"slack above half the element's own ulp in {share:.2f} % (ceiling {ceiling} %)")
-    assert not at_rms or float(slack.max()) < 0.5 * float(R._ulp(torch.tensor(rms), 7)), what
+    assert not at_rms or float(slack.max()) < 0.5 * float(R.ulp(torch.tensor(rms), 7)), what
     below = mag < FOLD * ref.abs()
     assert not bool((miss & below).any()), f"{what}: an element that cancels less than {FOLD:.0f}-fold has a bound of an ulp or more"
     assert K < 2.0 ** 14 / FOLD, (what, K)

@@ -11,10 +11,9 @@ import torch
 from tests import attention_ref as A
 from tests.attention_ref import B, GEN, HEADS, LDS, MFMA, MHA
 from tests.conftest import check
+from tests.kernel_harness import Guarded, stop_after_a_device_error  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
-
-GUARD = 4096                                                   # floats of NaN on both sides of every output
 
 
 def test_case_table_reaches_every_form():
@@ -48,25 +47,6 @@ def test_case_table_reaches_every_form():
     assert all(c in have for c in A.REGIME_CASES)
 
 
-def _guarded(n, dev):
-    buf = torch.full((n + 2 * GUARD,), float("nan"), device=dev, dtype=torch.float32)
-    return buf, buf[GUARD:GUARD + n]
-
-
-def _guards_intact(buf, what):
-    assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all()), f"{what}: guard overwritten"
-
-
-def _owned(buf, what):
-    """every addressed element written with a finite value, nothing outside touched"""
-    _guards_intact(buf, what)
-    assert bool(torch.isfinite(buf[GUARD:-GUARD]).all()), f"{what}: element not written or not finite"
-
-
-def _untouched(buf, what):
-    assert bool(torch.isnan(buf).all()), f"{what}: written by a rejected call"
-
-
 def launch(fam, ch, T, nd, inputs, batch=B, heads=HEADS, save_w=True):
     """forward and backward of one family on the current stream through the C ABI; returns CPU tensors"""
     from remfx_amd import _lib
@@ -76,54 +56,57 @@ def launch(fam, ch, T, nd, inputs, batch=B, heads=HEADS, save_w=True):
     dev = torch.device("cuda", torch.cuda.current_device())
     q, k, cont, qd, gout = (t.to(dev).contiguous() if t is not None else None for t in inputs)
     n, nq, nbt = batch * heads * ch * T, batch * heads * nd * T, batch * heads * T
-    bufs = {name: _guarded(n, dev) for name in ("out", "dq", "dk", "dcont")}
+    bufs = {name: Guarded(n, what=name, device=dev) for name in ("out", "dq", "dk", "dcont")}
     if nd:
-        bufs["dqd"] = _guarded(nq, dev)
-    p = {name: _ptr(v[1]) for name, v in bufs.items()}
+        bufs["dqd"] = Guarded(nq, what="dqd", device=dev)
+    p = {name: _ptr(b.t) for name, b in bufs.items()}
     res = {}
     if fam == LDS:
-        wb, w = _guarded(nbt * T, dev) if save_w else (None, None)
+        wb = Guarded(nbt * T, what="w", device=dev) if save_w else None
+        w = wb.t if save_w else None
         rc(L.rfx_localstate_fwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), batch, heads, ch, T, nd, _ptr(w), p["out"], _stream()),
            "rfx_localstate_fwd")
-        _owned(bufs["out"][0], "out")
+        bufs["out"].owned()
         if not save_w:
-            return {"out": bufs["out"][1].cpu().view(batch, heads * ch, T)}
-        _owned(wb, "w")
+            return {"out": bufs["out"].t.cpu().view(batch, heads * ch, T)}
+        wb.owned()
         rc(L.rfx_localstate_bwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), _ptr(w), _ptr(gout), batch, heads, ch, T, nd, p["dq"], p["dk"],
                                 p["dcont"], p["dqd"], _stream()), "rfx_localstate_bwd")
         res["w"] = w.cpu().view(batch, heads, T, T)
     elif fam == MFMA:
         assert L.rfx_localstate_mfma_ok(batch, heads, ch, T, nd) == 1
-        sb, stat = _guarded(nbt * 4, dev)
+        sb = Guarded(nbt * 4, what="stat", device=dev)
+        stat = sb.t
         assert stat.data_ptr() % 16 == 0
         rc(L.rfx_localstate_mfma_fwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), batch, heads, ch, T, nd, p["out"], _stream()),
            "rfx_localstate_mfma_fwd")
-        _owned(bufs["out"][0], "out")
+        bufs["out"].owned()
         rc(L.rfx_localstate_mfma_bwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), _ptr(gout), batch, heads, ch, T, nd, p["dq"], p["dk"],
                                      p["dcont"], p["dqd"], _ptr(stat), _stream()), "rfx_localstate_mfma_bwd")
-        _owned(sb, "stat")                                     # (max, 1 / sum, delta, D) of every query column
+        sb.owned()                                             # (max, 1 / sum, delta, D) of every query column
     else:
-        sb, stat = _guarded(nbt * 4, dev)
+        sb = Guarded(nbt * 4, what="stat", device=dev)
+        stat = sb.t
         if fam == GEN:
             rc(L.rfx_localstate_gen_fwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), batch, heads, ch, T, nd, _ptr(stat), p["out"], _stream()),
                "rfx_localstate_gen_fwd")
         else:
             rc(L.rfx_mha_fwd(_ptr(q), _ptr(k), _ptr(cont), batch, heads, ch, T, _ptr(stat), p["out"], _stream()), "rfx_mha_fwd")
-        _owned(bufs["out"][0], "out")
-        _guards_intact(sb, "stat")
+        bufs["out"].owned()
+        sb.guards_intact()
         res["stat_fwd"] = stat.cpu().view(nbt, 4)
-        out = bufs["out"][1]
+        out = bufs["out"].t
         if fam == GEN:
             rc(L.rfx_localstate_gen_bwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), _ptr(stat), _ptr(out), _ptr(gout), batch, heads, ch, T, nd,
                                         p["dq"], p["dk"], p["dcont"], p["dqd"], _stream()), "rfx_localstate_gen_bwd")
         else:
             rc(L.rfx_mha_bwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(stat), _ptr(out), _ptr(gout), batch, heads, ch, T, p["dq"], p["dk"],
                              p["dcont"], _stream()), "rfx_mha_bwd")
-        _guards_intact(sb, "stat")
+        sb.guards_intact()
         res["stat"] = stat.cpu().view(nbt, 4)
-    for name, (buf, v) in bufs.items():
-        _owned(buf, name)
-        res[name] = v.cpu().view(batch, -1, T)
+    for name, b in bufs.items():
+        b.owned()
+        res[name] = b.t.cpu().view(batch, -1, T)
     return res
 
 
@@ -252,9 +235,9 @@ def test_rejections_launch_nothing():
         # q, k, cont, gout, out / w (inputs of the backward sweeps), each large enough for any form the entry point could launch
         x = [torch.zeros(max(B * HEADS * max(ch, 96) * T, nbt * T), device=dev) for _ in range(5)]
         qd = torch.zeros(nq, device=dev)
-        o = {name: torch.full((m,), float("nan"), device=dev) for name, m in
+        o = {name: Guarded(m, what=(fam, ch, T, nd, sweep, name), device=dev) for name, m in
              (("out", n), ("dq", n), ("dk", n), ("dcont", n), ("dqd", nq), ("w", nbt * T), ("stat", nbt * 4))}
-        P = {name: _ptr(t) for name, t in o.items()}
+        P = {name: _ptr(b.t) for name, b in o.items()}
         q, k, c, g, oin = (_ptr(t) for t in x)
         s = _stream()
         if (fam, sweep) == (LDS, "fwd"):
@@ -275,8 +258,8 @@ def test_rejections_launch_nothing():
             r = L.rfx_mha_bwd(q, k, c, P["stat"], oin, g, B, HEADS, ch, T, P["dq"], P["dk"], P["dcont"], s)
         assert r == -1, (fam, ch, T, nd, sweep, r)
         torch.cuda.synchronize()
-        for name, t in o.items():
-            _untouched(t, (fam, ch, T, nd, sweep, name))
+        for b in o.values():
+            b.untouched()                                      # a rejected call writes nothing
 
     for sweep in ("fwd", "bwd"):
         for ch, T, nd in ((16, 257, 4), (16, 33, 9), (12289, 1, 4), (97, 127, 4), (48, 257, 4)):

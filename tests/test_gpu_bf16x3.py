@@ -88,7 +88,7 @@ def test_hdemucs_full_forward_bf16x3():
 
 def test_hdemucs_small_grads_bf16x3():
     """whole-network gradients in bf16x3 mode vs autograd over the fp32 CPU oracle."""
-    from tests.test_gpu_hdemucs import _pair
+    from tests.hdemucs_pair import pair as _pair
     ref, net = _pair(8)
     g = torch.Generator().manual_seed(1)
     x = torch.randn(2, 1, 20000, generator=g) * 0.5

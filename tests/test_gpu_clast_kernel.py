@@ -7,22 +7,14 @@ import pytest
 import torch
 
 from tests import clast_ref as R
+from tests.kernel_harness import Arena, stop_after_a_device_error  # noqa: F401
+from tests.kernel_harness import guarded as _guarded
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
 
 CONV = R.conv_cases()
 WGRAD = R.wgrad_cases()
 DEV = "cuda:0"
-
-
-def _guarded(fn, what):
-    """run a launch sequence; a launch error or a device fault ends the session: nothing more is started on this device"""
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-        return out
-    except RuntimeError as e:
-        pytest.exit(f"{what}: {e}", returncode=3)
 
 
 def _fetch(out, what):
@@ -33,7 +25,7 @@ def _fetch(out, what):
 
 
 def _run_conv(case, inp):
-    arena = R.Arena(DEV)
+    arena = Arena(DEV)
     with R.recorder(False) as tr:
         out, spare = _guarded(lambda: R.launch_conv(case, inp, DEV, arena.alloc), case.id)
         codes = list(tr)
@@ -69,7 +61,7 @@ def test_conv_form(case):
 
 
 def _run_wgrad(case, inp):
-    arena = R.Arena(DEV)
+    arena = Arena(DEV)
     with R.recorder(False, case.splits) as tr:
         out = _guarded(lambda: R.launch_wgrad(case, inp, DEV, arena.alloc), case.id)
         codes = list(tr)
@@ -125,7 +117,7 @@ def test_from_cm(mode, res, C, B, src16):
     Co = 2 * C if mode == "dglu" else C
     outs = []
     for rep in range(2):
-        arena = R.Arena(DEV)
+        arena = Arena(DEV)
         wide = arena.alloc((N, A, B, Co + 16), torch.bfloat16)                      # the destination is a channel slice
         dst = wide[..., 8:8 + Co]
         src = _cm_src(x, torch.bfloat16 if src16 else torch.float32, strided=(C == 40))
@@ -154,7 +146,7 @@ def test_to_cm(dst16, aux, C, B):
     outs = []
     dt = torch.bfloat16 if dst16 else torch.float32
     for rep in range(2):
-        arena = R.Arena(DEV)
+        arena = Arena(DEV)
         wide = arena.alloc((N, C + 1, A + 1, B), dt)                                  # a strided destination
         dst = wide[:, :C, :A]
         z16 = None
@@ -209,7 +201,7 @@ def test_rowsum(N, A, XA, C, B, acc):
     base = _rand((A, C), 3, bf16=False) * 50
     outs = []
     for rep in range(2):
-        arena = R.Arena(DEV)
+        arena = Arena(DEV)
         out = arena.alloc((A, C), torch.float32)
         out.copy_(base.to(DEV)) if acc else None
         _guarded(lambda: clchain.rowsum(xd, A, C, out, scale=0.5, accumulate=acc), "rowsum")

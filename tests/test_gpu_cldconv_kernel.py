@@ -26,39 +26,31 @@ import pytest
 import torch
 
 from tests import cldconv_ref as R
+from tests.kernel_harness import Guarded, stop_after_a_device_error  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]          # the kernels have one arithmetic mode
 
-GUARD = 4096
 EPS = R.GEN_EPS
 CHILD_MARK = "RFX_TEST_CLDCONV_FOUR_WAVE_CHILD"                # set by test_four_wave_form_in_a_child_process alone, for its child
 FOUR = os.environ.get(CHILD_MARK) == "1"
 FWD_CASES = R.forward_cases()
 BWD_CASES = R.four_wave_cases() if FOUR else R.backward_cases()
-_FILL = {torch.float32: (torch.int32, 0x7FC00000), torch.bfloat16: (torch.int16, 0x7FC0)}
 PARAMS = ("W1", "b1", "g1w", "g1b", "W2", "b2", "g2w", "g2b", "scale")
 
 
 class _Alloc:
-    """the allocator handed to layer_forward / layer_backward: NaN-filled buffers between NaN guards"""
+    """the allocator handed to layer_forward / layer_backward: every tensor the launch path writes is a Guarded"""
 
     def __init__(self):
         self.bufs = {}
 
     def __call__(self, name, shape, dtype, device):
-        n = math.prod(shape)
-        buf = torch.full((2 * GUARD + n,), float("nan"), device=device, dtype=dtype)
-        self.bufs[name] = (buf, n)
-        return buf[GUARD:GUARD + n].view(shape)
+        self.bufs[name] = Guarded(math.prod(shape), dtype, name, device=device)
+        return self.bufs[name].t.view(shape)
 
     def check(self, outputs):
-        for name, (buf, n) in self.bufs.items():
-            it, pat = _FILL[buf.dtype]
-            bits = buf.view(it)
-            assert bool((bits[:GUARD] == pat).all()) and bool((bits[GUARD + n:] == pat).all()), f"{name}: guard overwritten"
-            if name in outputs:
-                bad = ~torch.isfinite(buf[GUARD:GUARD + n].float())
-                assert not bool(bad.any()), f"{name}: element {int(bad.nonzero()[0])} of {n} not written or not finite"
+        for name, b in self.bufs.items():
+            b.owned() if name in outputs else b.guards_intact()
 
 
 def _layout(case):

@@ -13,45 +13,25 @@ Buffers: every output is NaN-filled between two NaN guards of 4096 elements; `ws
 NaN-filled and followed by a guard (every slot has to be written: it comes back finite).  A sliced output is a channel slice of a wider
 NaN-filled buffer whose neighbouring channels must keep their bits; a sliced gy is read from one (a read outside the slice returns NaN).
 Every case runs twice into fresh buffers: plain slot stores and ordered sums, the same bits."""
+import functools
+
 import pytest
 import torch
 
 from tests import cplx_ref as R
+from tests.kernel_harness import Guarded, api, bits, judge, stop_after_a_device_error  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]          # no GEMM inside: the arithmetic modes agree
 
-GUARD = 4096
 EPS = R.GEN_EPS
-_FILL = {torch.float32: (torch.int32, 0x7FC00000), torch.float64: (torch.int64, 0x7FF8000000000000)}
-
-
-class _Buf:
-    """n elements of NaN with a NaN guard behind and (outputs) in front"""
-
-    def __init__(self, n, dtype=torch.float32, front=True, what="", init=None):
-        self.lo, self.what = (GUARD if front else 0), what
-        self.buf = torch.full((self.lo + n + GUARD,), float("nan"), device="cuda", dtype=dtype)
-        self.t = self.buf[self.lo:self.lo + n]
-        if init is not None:
-            self.t.copy_(init.reshape(-1))
-
-    def guards_intact(self):
-        it, pat = _FILL[self.buf.dtype]
-        bits = self.buf.view(it)
-        assert bool((bits[:self.lo] == pat).all()) and bool((bits[self.lo + self.t.numel():] == pat).all()), f"{self.what}: guard overwritten"
-
-    def owned(self):
-        """every element written with a finite value, nothing outside touched"""
-        self.guards_intact()
-        bad = ~torch.isfinite(self.t)
-        assert not bool(bad.any()), f"{self.what}: element {int(bad.nonzero()[0])} of {self.t.numel()} not written or not finite"
+_judge = functools.partial(judge, exact="value")                        # bound 0: the error is 0, -0 == +0
 
 
 class _Sliced:
     """(N, 2C, S) as the channels [Cx, Cx + 2C) of a NaN-filled (N, 2C + 2Cx, S) buffer between guards"""
 
     def __init__(self, N, C, S, Cx, what, init=None):
-        self.b = _Buf(N * (2 * C + 2 * Cx) * S, what=what)
+        self.b = Guarded(N * (2 * C + 2 * Cx) * S, what=what)
         self.wide = self.b.t.view(N, 2 * C + 2 * Cx, S)
         self.t = self.wide[:, Cx:Cx + 2 * C]
         self.ns, self.Cx, self.C = (2 * C + 2 * Cx) * S, Cx, C
@@ -60,43 +40,21 @@ class _Sliced:
 
     def owned(self):
         self.b.guards_intact()
-        it, pat = _FILL[torch.float32]
-        nb = torch.cat([self.wide[:, :self.Cx], self.wide[:, self.Cx + 2 * self.C:]], 1).contiguous().view(it)
-        assert bool((nb == pat).all()), f"{self.b.what}: a neighbouring channel of the slice was written"
+        nb = bits(torch.cat([self.wide[:, :self.Cx], self.wide[:, self.Cx + 2 * self.C:]], 1))
+        assert bool((nb == self.b.fill).all()), f"{self.b.what}: a neighbouring channel of the slice was written"
         bad = ~torch.isfinite(self.t)
         assert not bool(bad.any()), f"{self.b.what}: element {tuple(bad.nonzero()[0].tolist())} of the slice not written or not finite"
 
 
-def _api():
-    from remfx_amd import _lib
-    from remfx_amd.ops import _ptr, _stream
-    return _lib.lib(), _ptr, _stream
-
-
-def _where(i, shape):
-    out = []
-    for d in reversed(shape):
-        out.append(i % d)
-        i //= d
-    return tuple(reversed(out))
-
-
-def _judge(entry, case_id, name, got, ref, tol, extra=""):
-    q, i = R.worst(got.cpu(), ref, tol)
-    assert q <= 1.0, (entry, case_id, name, "element", _where(i, tuple(ref.shape)), "error / bound", q, "got", float(got.reshape(-1)[i]),
-                      "ref", float(ref.reshape(-1)[i]), extra)
-    return q
-
-
 # ---- the four streaming kernels ---------------------------------------------------------------------------------------------------------
 def launch_stream(case, inp, coef, cm):
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     N, C, S = case.N, case.C, case.S
     x, coef_d, cm_d = inp["x"].cuda(), coef.cuda().contiguous(), cm.cuda().contiguous()
     assert L.rfx_cplx_slots(N, S) == R.slots(N, S)
     got = {}
-    ws = _Buf(R.moments_ws(N, C, S), torch.float64, front=False, what="moments ws")
-    sums = _Buf(5 * C, torch.float64, what="sums")
+    ws = Guarded(R.moments_ws(N, C, S), torch.float64, front=False, what="moments ws")
+    sums = Guarded(5 * C, torch.float64, what="sums")
     assert L.rfx_cplx_moments(_ptr(x), N, C, S, _ptr(ws.t), _ptr(sums.t), _stream()) == 0
     torch.cuda.synchronize()
     ws.owned(); sums.owned()
@@ -106,16 +64,16 @@ def launch_stream(case, inp, coef, cm):
         gy = _Sliced(N, C, S, case.Cx, "gy", init=inp["gy"].cuda())
         y_ns, gy_ns = y.ns, gy.ns
     else:
-        y = _Buf(N * 2 * C * S, what="y")
-        gy = _Buf(N * 2 * C * S, what="gy", init=inp["gy"].cuda())
+        y = Guarded(N * 2 * C * S, what="y")
+        gy = Guarded(N * 2 * C * S, what="gy", init=inp["gy"].cuda())
         y_ns = gy_ns = 2 * C * S
     assert L.rfx_cplx_affine_act_fwd(_ptr(x), _ptr(coef_d), N, C, S, R.SLOPE, _ptr(y.t), y_ns, C, _stream()) == 0
     torch.cuda.synchronize()
     y.owned()
     got["y"] = y.t.reshape(N, 2 * C, S).cpu()
-    gx = _Buf(N * 2 * C * S, what="gx")
-    ws2 = _Buf(R.affine_bwd_ws(N, C, S), torch.float64, front=False, what="affine_act_bwd ws")
-    gcoef = _Buf(6 * C, what="gcoef")
+    gx = Guarded(N * 2 * C * S, what="gx")
+    ws2 = Guarded(R.affine_bwd_ws(N, C, S), torch.float64, front=False, what="affine_act_bwd ws")
+    gcoef = Guarded(6 * C, what="gcoef")
     gy_bits = gy.b.buf.clone() if case.sliced else gy.buf.clone()
     assert L.rfx_cplx_affine_act_bwd(_ptr(x), _ptr(coef_d), _ptr(gy.t), gy_ns, C, N, C, S, R.SLOPE, _ptr(gx.t), _ptr(ws2.t), _ptr(gcoef.t),
                                      _stream()) == 0
@@ -123,7 +81,7 @@ def launch_stream(case, inp, coef, cm):
     gx.owned(); ws2.owned(); gcoef.owned()
     assert torch.equal((gy.b.buf if case.sliced else gy.buf).view(torch.int32), gy_bits.view(torch.int32)), "gy was written"
     got["gx"], got["gcoef"] = gx.t.view(N, 2 * C, S).cpu(), gcoef.t.view(6, C).cpu()
-    gx2 = _Buf(N * 2 * C * S, what="gx (moments_bwd)", init=inp["gx0"].cuda())
+    gx2 = Guarded(N * 2 * C * S, what="gx (moments_bwd)", init=inp["gx0"].cuda())
     assert L.rfx_cplx_moments_bwd(_ptr(x), _ptr(cm_d), N, C, S, _ptr(gx2.t), _stream()) == 0
     torch.cuda.synchronize()
     gx2.owned()
@@ -144,7 +102,7 @@ def test_streaming_kernels(case):
     got = launch_stream(case, inp, coef, cm)
     ref, mag, slack, fl = R.floors_stream(case, inp, coef.double(), cm.double())
     for name in ref:
-        _judge(ENTRY[name], case.id, name, got[name], ref[name], R.tolerance(name, mag, slack, fl), ("floor", fl[name], case.forms()))
+        _judge(got[name], ref[name], R.tolerance(name, mag, slack, fl), ctx=(ENTRY[name], case.id, name, "floor", fl[name], case.forms()))
     again = launch_stream(case, inp, coef, cm)
     for k in got:
         assert torch.equal(got[k], again[k]), (case.id, k, "second run differs")
@@ -152,21 +110,21 @@ def test_streaming_kernels(case):
 
 # ---- coefficient kernels ------------------------------------------------------------------------------------------------------------------
 def launch_coef(ci, C, train):
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     d = lambda t, dt=torch.float32: t.to(dt).contiguous().cuda()              # noqa: E731
     W, B = [d(w) for w in ci["W"]], [d(b) for b in ci["B"]]
     wp = [_ptr(t) for t in W + B]
-    coef = _Buf(6 * C, what="coef")
-    gw = _Buf(5 * C, what="gw")
+    coef = Guarded(6 * C, what="coef")
+    gw = Guarded(5 * C, what="gw")
     gcoef = d(ci["gcoef"])
     got = {}
     if train:
         sums = d(ci["sums"], torch.float64)
-        stats = _Buf(5 * C, what="stats_out")
-        run = [_Buf(C, what=f"running[{q}]", init=ci["running"][q].cuda()) for q in range(5)]
+        stats = Guarded(5 * C, what="stats_out")
+        run = [Guarded(C, what=f"running[{q}]", init=ci["running"][q].cuda()) for q in range(5)]
         assert L.rfx_cplx_coef_fwd(_ptr(sums), ci["inv"], None, *wp, EPS, C, _ptr(coef.t), _ptr(stats.t), *[_ptr(r.t) for r in run],
                                    R.MOMENTUM, _stream()) == 0
-        cm = _Buf(5 * C, what="cm")
+        cm = Guarded(5 * C, what="cm")
         assert L.rfx_cplx_coef_bwd(_ptr(sums), ci["inv"], None, *wp, EPS, C, _ptr(gcoef), _ptr(gw.t), _ptr(cm.t), _stream()) == 0
         torch.cuda.synchronize()
         for b in [coef, stats, gw, cm] + run:
@@ -195,16 +153,16 @@ def test_coefficient_kernels(C, train):
     st32 = got["stats"] if train else None
     ref, mag, fl = R.floors_coef(ci, train)
     if train:
-        _judge("rfx_cplx_coef_fwd", cid, "stats_out", got["stats"], ref["stats"], R.k_of(fl["stats"]) * R.EPS32 * mag["stats"], fl)
+        _judge(got["stats"], ref["stats"], R.k_of(fl["stats"]) * R.EPS32 * mag["stats"], ctx=("rfx_cplx_coef_fwd", cid, "stats_out", fl))
         ref, mag, _ = R.floors_coef(ci, train, st32=st32)                        # the floors stay the CPU's
-        _judge("rfx_cplx_coef_fwd", cid, "running", got["running"], ref["running"], R.k_of(fl["running"]) * R.EPS32 * mag["running"], fl)
-    _judge("rfx_cplx_coef_fwd", cid, "coef", got["coef"], ref["coef"], R.k_of(fl["coef"]) * R.EPS32 * mag["coef"], fl)
+        _judge(got["running"], ref["running"], R.k_of(fl["running"]) * R.EPS32 * mag["running"], ctx=("rfx_cplx_coef_fwd", cid, "running", fl))
+    _judge(got["coef"], ref["coef"], R.k_of(fl["coef"]) * R.EPS32 * mag["coef"], ctx=("rfx_cplx_coef_fwd", cid, "coef", fl))
     st = st32.double() if train else ci["running"].float().double()
     gw, cm = R.coef_bwd(st, ci["W"], R.f32(EPS), ci["gcoef"], ci["inv"] if train else None, v32=True)
     k = R.k_of(0.5)                                               # fp64 inside: what is left is the rounding of the result
-    _judge("rfx_cplx_coef_bwd", cid, "gw", got["gw"], gw, k * R.EPS32 * R.coef_bwd_mag(gw))
+    _judge(got["gw"], gw, k * R.EPS32 * R.coef_bwd_mag(gw), ctx=("rfx_cplx_coef_bwd", cid, "gw"))
     if train:
-        _judge("rfx_cplx_coef_bwd", cid, "cm", got["cm"], cm, k * R.EPS32 * R.coef_bwd_mag(cm))
+        _judge(got["cm"], cm, k * R.EPS32 * R.coef_bwd_mag(cm), ctx=("rfx_cplx_coef_bwd", cid, "cm"))
     again = launch_coef(ci, C, train)
     for name in got:
         assert torch.equal(got[name], again[name]), (cid, name, "second run differs")
@@ -212,11 +170,11 @@ def test_coefficient_kernels(C, train):
 
 def test_coefficient_argument_guards():
     """both or neither of sums / stats_in, and a partial set of running pointers, are refused without a launch"""
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     C = 3
     f = lambda n, dt=torch.float32: torch.ones(n, device="cuda", dtype=dt)       # noqa: E731
     w = [_ptr(f(C)) for _ in range(5)]
-    sums, st, coef, gc, gw = f(5 * C, torch.float64), f(5 * C), _Buf(6 * C, what="coef"), f(6 * C), _Buf(5 * C, what="gw")
+    sums, st, coef, gc, gw = f(5 * C, torch.float64), f(5 * C), Guarded(6 * C, what="coef"), f(6 * C), Guarded(5 * C, what="gw")
     run = [f(C) for _ in range(5)]
     none5 = [None] * 5
     assert L.rfx_cplx_coef_fwd(_ptr(sums), 0.5, _ptr(st), *w, EPS, C, _ptr(coef.t), None, *none5, 0.1, _stream()) != 0
@@ -229,18 +187,17 @@ def test_coefficient_argument_guards():
     assert L.rfx_cplx_coef_bwd(_ptr(sums), 0.5, _ptr(st), *w, EPS, C, _ptr(gc), _ptr(gw.t), None, _stream()) != 0
     assert L.rfx_cplx_coef_bwd(None, 0.5, None, *w, EPS, C, _ptr(gc), _ptr(gw.t), None, _stream()) != 0
     torch.cuda.synchronize()
-    it, pat = _FILL[torch.float32]
-    assert bool((coef.buf.view(it) == pat).all()) and bool((gw.buf.view(it) == pat).all()), "a refused call wrote"
+    coef.untouched(); gw.untouched()                             # a refused call writes nothing
 
 
 # ---- masks --------------------------------------------------------------------------------------------------------------------------------
 def launch_bound_mask(bi, N, P):
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     m, g = bi["m"].cuda().contiguous(), bi["g"].cuda().contiguous()
     tf_ns = 2 * P + 5                                             # the product passes tf.stride(0) of a wider tensor
     tfb = torch.full((N, tf_ns), float("nan"), device="cuda")
     tfb[:, :2 * P] = bi["tf"].reshape(N, 2 * P).cuda()
-    out, gm = _Buf(N * 2 * P, what="out"), _Buf(N * 2 * P, what="gm")
+    out, gm = Guarded(N * 2 * P, what="out"), Guarded(N * 2 * P, what="gm")
     assert L.rfx_bound_mask_fwd(_ptr(m), _ptr(tfb), _ptr(out.t), N, P, 2 * P, tf_ns, 2 * P, _stream()) == 0
     assert L.rfx_bound_mask_bwd(_ptr(m), _ptr(tfb), _ptr(g), _ptr(gm.t), N, P, 2 * P, tf_ns, 2 * P, 2 * P, _stream()) == 0
     torch.cuda.synchronize()
@@ -258,7 +215,7 @@ def test_bound_mask(NP):
     got = launch_bound_mask(bi, N, P)
     ref, mag, fl = R.floors_bound_mask(bi)
     for name, entry in (("out", "rfx_bound_mask_fwd"), ("gm", "rfx_bound_mask_bwd")):
-        q = _judge(entry, f"{N}x{P}", name, got[name], ref[name], R.k_of(fl[name]) * R.EPS32 * mag[name], ("floor", fl[name]))
+        q = _judge(got[name], ref[name], R.k_of(fl[name]) * R.EPS32 * mag[name], ctx=(entry, f"{N}x{P}", name, "floor", fl[name]))
         print(f"\nBOUNDMASK {N}x{P} {name}: worst error / bound {q:.3f}, CPU float32 floor {fl[name]:.2f}")
     again = launch_bound_mask(bi, N, P)
     for k in got:
@@ -275,9 +232,9 @@ def test_bound_mask_at_zero():
 
 
 def launch_phase_mask(pi, n):
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     xc, mg, g = pi["xc"].cuda(), pi["mag"].cuda(), pi["g"].cuda().contiguous()
-    out, gmag = _Buf(2 * n, what="out"), _Buf(n, what="gmag")
+    out, gmag = Guarded(2 * n, what="out"), Guarded(n, what="gmag")
     assert L.rfx_phase_mask_fwd(_ptr(mg), _ptr(xc), _ptr(out.t), n, _stream()) == 0
     assert L.rfx_phase_mask_bwd(_ptr(xc), _ptr(g), _ptr(gmag.t), n, _stream()) == 0
     torch.cuda.synchronize()
@@ -293,7 +250,7 @@ def test_phase_mask(n):
     got = launch_phase_mask(pi, n)
     ref, mag, fl = R.floors_phase_mask(pi)
     for name, entry in (("out", "rfx_phase_mask_fwd"), ("gmag", "rfx_phase_mask_bwd")):
-        q = _judge(entry, n, name, got[name], ref[name], R.k_of(fl[name]) * R.EPS32 * mag[name], ("floor", fl[name]))
+        q = _judge(got[name], ref[name], R.k_of(fl[name]) * R.EPS32 * mag[name], ctx=(entry, n, name, "floor", fl[name]))
         print(f"\nPHASEMASK {n} {name}: worst error / bound {q:.3f}, CPU float32 floor {fl[name]:.2f}")
     z = (pi["xc"] == 0).all(1)
     if bool(z.any()):

@@ -5,126 +5,25 @@ their constants come from are in elem_ref's docstring and DESIGN.md 4.21; none i
 Buffers: every input and output sits between NaN guards of 4096 elements, outputs are NaN-filled, workspaces are exactly the size the
 _ws / _slots call returns; inputs have to come back bit for bit; every case runs twice into fresh buffers: the same bits.  A failure
 names the entry point, the output and the element."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from tests import elem_ref as E
+from tests.kernel_harness import Guarded, api, bits, judge, report, stop_after_a_device_error, twice  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
 
-GUARD = 4096
-_INT = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
-
-
-def _bits(t):
-    return t.contiguous().view(_INT[t.element_size()])
-
-
-class _Buf:
-    """n elements `off` elements into the space between two NaN guards (off = 0: aligned to 8 KiB at least)"""
-
-    def __init__(self, n, dtype=torch.float32, what="", init=None, off=0):
-        self.what, self.n = what, n
-        ftype = {torch.int32: torch.float32}.get(dtype, dtype)
-        self.buf = torch.full((GUARD + off + n + GUARD,), float("nan"), device="cuda", dtype=ftype)
-        self.fill = _bits(self.buf[:1]).clone()
-        self.t = self.buf[GUARD + off:GUARD + off + n]
-        if dtype != ftype:
-            self.t = self.t.view(dtype)
-        if init is not None:
-            self.t.copy_(init.reshape(-1).to(dtype))
-        self.before = self.buf.clone()
-
-    def ptr(self, elements=0):
-        return C.c_void_p(self.t.data_ptr() + elements * self.t.element_size())
-
-    def unchanged(self):
-        assert torch.equal(_bits(self.buf), _bits(self.before)), f"{self.what} was written"
-
-    def guards_intact(self):
-        b, lo = _bits(self.buf), self.buf.numel() - GUARD
-        inside = slice(self.buf.numel() - GUARD - self.n, lo)
-        assert bool((b[:inside.start] == self.fill).all()) and bool((b[lo:] == self.fill).all()), f"{self.what}: guard overwritten"
-
-    def untouched(self):
-        assert bool((_bits(self.buf) == self.fill).all()), f"{self.what}: written by a call that had to leave it alone"
-
-    def cpu(self):
-        self.guards_intact()
-        return self.t.cpu()
-
-    def still_fill(self, got_cpu, where):
-        """the elements `where` (bool, cpu) of the payload must still hold the NaN fill"""
-        b = _bits(got_cpu)
-        bad = where & (b != self.fill.cpu())
-        assert not bool(bad.any()), f"{self.what}: element {int(bad.nonzero()[0])} is outside the result and was written"
-
-
-def _api():
-    from remfx_amd import _lib
-    from remfx_amd.ops import _stream
-    return _lib.lib(), _stream
-
-
-def _within(entry, output, got, ref, bound, info=()):
-    """per element |got - ref| <= bound; -> the largest error / bound"""
-    got, ref, bound = got.double().reshape(-1), ref.double().reshape(-1), bound.double().reshape(-1)
-    bad = ~torch.isfinite(got)
-    assert not bool(bad.any()), (entry, output, "element", int(bad.nonzero()[0]), "of", got.numel(), "not written / not finite", *info)
-    q = (got - ref).abs() / bound.clamp_min(1e-300)
-    j = int(q.argmax())
-    assert float(q[j]) <= 1.0, (entry, output, "element", j, "of", got.numel(), "error / bound", float(q[j]), "got", float(got[j]), "ref",
-                                float(ref[j]), "bound", float(bound[j]), *info)
-    return float(q[j])
-
-
-def _exact(entry, output, got, ref, info=()):
-    """bit for bit against the fp64 value rounded once to the output's type"""
-    got = got.reshape(-1)
-    ref = ref.reshape(-1).to(got.dtype)
-    bad = _bits(got) != _bits(ref)
-    if bool(bad.any()):
-        j = int(bad.nonzero()[0])
-        raise AssertionError((entry, output, "element", j, "of", got.numel(), "got", float(got[j]), "ref", float(ref[j]), "differing",
-                              int(bad.sum()), *info))
-    return 0.0
-
-
-def _judge(entry, output, got, ref, bound, info=()):
-    if float(bound.max()) == 0.0:
-        return _exact(entry, output, got, ref, info)
-    return _within(entry, output, got, ref, bound, info)
-
-
-def _twice(run):
-    a, b = run(), run()
-    for k in a:
-        assert torch.equal(_bits(a[k]), _bits(b[k])), (k, "second run differs")
-    return a
-
-
-def _report(entry, ratios):
-    """ratios: error / bound figures, or (label, figure) pairs"""
-    pairs = [r if isinstance(r, tuple) else ("", r) for r in ratios]
-    best = {}
-    for k, v in pairs:
-        best[k] = max(best.get(k, 0.0), v)
-    print(f"\nELEM {entry}: largest error / bound " + ", ".join(f"{k} {v:.3f}".strip() for k, v in best.items()) if best else f"\nELEM {entry}: refused")
-
-
 # ---- flat activations --------------------------------------------------------------------------------------------------------------
 def _flat(entry, code, n, off, x, other):
-    L, stream = _api()
-    X = _Buf(n, what="x", init=x, off=off)
-    Y = _Buf(n, what="y", off=off)
+    L, _, stream = api()
+    X = Guarded(n, what="x", init=x, off=off)
+    Y = Guarded(n, what="y", off=off)
     if entry == "rfx_act_fwd":
         rc = L.rfx_act_fwd(X.ptr(), Y.ptr(), n, code, stream())
         ins = (X,)
     else:
-        O = _Buf(n, what="gy" if entry == "rfx_act_bwd" else "res", init=other, off=off)
+        O = Guarded(n, what="gy" if entry == "rfx_act_bwd" else "res", init=other, off=off)
         fn = L.rfx_act_bwd if entry == "rfx_act_bwd" else L.rfx_act_add_fwd
         rc = fn(X.ptr(), O.ptr(), Y.ptr(), n, code, stream())
         ins = (X, O)
@@ -155,15 +54,15 @@ def test_flat_activations(code, n):
                 rc, Y = _flat(entry, code, n, off, x, other)
                 assert rc == 0, (entry, rc)
                 return {"y": Y.cpu()}
-            got = _twice(run)["y"]
+            got = twice(run)[0]["y"]
             if entry == "rfx_act_fwd":
                 ref, bound = E.act(x, code), E.act_bound(x, code)
             elif entry == "rfx_act_bwd":
                 ref, bound = gy.double() * E.act_grad(x, code), E.act_grad_bound(x, gy, code)
             else:
                 ref, bound = E.act(x, code) + res.double(), E.act_add_bound(x, res, code)
-            ratios.append((entry, _judge(entry, "y", got, ref, bound, (E.ACT_NAMES[code], "n", n, "offset", off, sorted(E.forms_flat("", n))))))
-    _report(f"flat {E.ACT_NAMES[code]} n={n}", ratios)
+            ratios.append((entry, judge(got, ref, bound, ctx=(entry, "y", E.ACT_NAMES[code], "n", n, "offset", off, sorted(E.forms_flat("", n))))))
+    report("ELEM", f"flat {E.ACT_NAMES[code]} n={n}", ratios)
 
 
 # ---- act_rows ----------------------------------------------------------------------------------------------------------------------
@@ -196,7 +95,7 @@ def _gather(flat, D, st, T):
 
 def _rows(x16, bwd, D, T, code, falsify=None, seed=5):
     """-> (logical result, largest error / bound)"""
-    L, stream = _api()
+    L, _, stream = api()
     lay = E.rows_layout(D, T, x16, falsify)
     xl, gl = _rows_data(D, T, x16, seed + T)
     xdt = torch.bfloat16 if x16 else torch.float32
@@ -209,9 +108,9 @@ def _rows(x16, bwd, D, T, code, falsify=None, seed=5):
     entry = "rfx_act_rows16" if x16 else "rfx_act_rows"
 
     def run():
-        X = _Buf(lay["x_len"], xdt, "x", xflat, lay["x_off"])
-        G = _Buf(lay["out_len"], torch.float32, "gy", gflat, lay["gy_off"]) if bwd else None
-        O = _Buf(lay["out_len"], odt, "out", None, lay["out_off"])
+        X = Guarded(lay["x_len"], xdt, "x", xflat, lay["x_off"])
+        G = Guarded(lay["out_len"], torch.float32, "gy", gflat, lay["gy_off"]) if bwd else None
+        O = Guarded(lay["out_len"], odt, "out", None, lay["out_off"])
         fn = L.rfx_act_rows16 if x16 else L.rfx_act_rows
         rc = fn(X.ptr(), *lay["xs"], G.ptr() if bwd else None, *(lay["gs"] if bwd else (0, 0, 0)), O.ptr(), *lay["os"], *D, T, code, stream())
         torch.cuda.synchronize()
@@ -224,7 +123,7 @@ def _rows(x16, bwd, D, T, code, falsify=None, seed=5):
         return {"out": got}
     ref = E.act_rows(xflat, D, lay["xs"], lay["os"], T, code, torch.full((lay["out_len"],), float("nan"), dtype=torch.float64),
                      gflat if bwd else None, lay["gs"])
-    got = _twice(run)["out"]
+    got = twice(run)[0]["out"]
     inside = ~torch.isnan(ref)
     xo = _place(torch.zeros(lay["out_len"]), xl, D, lay["os"], T)[inside]
     if not bwd:
@@ -234,7 +133,7 @@ def _rows(x16, bwd, D, T, code, falsify=None, seed=5):
         if x16:                                                  # the fp32 value (one rounding for the exact forms), then its bf16 rounding
             b32 = bound + E.HALF * ref[inside].abs()
             bound = b32 + E.bf16_half_ulp(ref[inside].abs() + b32)
-    r = _judge(entry, "out", got[inside], ref[inside], bound, info)
+    r = judge(got[inside], ref[inside], bound, ctx=(entry, "out", *info))
     return _gather(got, D, lay["os"], T), r
 
 
@@ -261,45 +160,45 @@ def test_act_rows(x16, bwd):
         ratios.append(r)
         scalar.append((fal, out))
     for fal, out in scalar[1:]:
-        assert torch.equal(_bits(out), _bits(scalar[0][1])), ("the scalar form's result differs between", scalar[0][0], "and", fal)
-    L, stream = _api()
-    X, O = _Buf(64, what="x"), _Buf(64, what="out")
+        assert torch.equal(bits(out), bits(scalar[0][1])), ("the scalar form's result differs between", scalar[0][0], "and", fal)
+    L, _, stream = api()
+    X, O = Guarded(64, what="x"), Guarded(64, what="out")
     fn = L.rfx_act_rows16 if x16 else L.rfx_act_rows
     assert fn(X.ptr(), 0, 0, 8, None, 0, 0, 0, O.ptr(), 0, 0, 8, 1, 1, 2, 8, E.PRELU, stream()) != 0
     torch.cuda.synchronize()
     O.untouched()
-    _report(f"act_rows x16={x16} bwd={bwd}", ratios)
+    report("ELEM", f"act_rows x16={x16} bwd={bwd}", ratios)
 
 
 # ---- mul / prelu -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", E.MUL_N)
 def test_mul(n):
     """rfx_mul bit for bit: the 16-byte body, the tail of 1 - 3, past the cap of 4096 workgroups, and one view a float off alignment"""
-    L, stream = _api()
+    L, _, stream = api()
     a, b = E.act_data(n, 21 + n).clamp(-12, 12), E.signs_data(n, 22 + n)
     for off in ((0, 1) if n == 1027 else (0,)):
         def run():
-            A, B, Y = _Buf(n, what="a", init=a, off=off), _Buf(n, what="b", init=b, off=off), _Buf(n, what="y", off=off)
+            A, B, Y = Guarded(n, what="a", init=a, off=off), Guarded(n, what="b", init=b, off=off), Guarded(n, what="y", off=off)
             assert L.rfx_mul(A.ptr(), B.ptr(), Y.ptr(), n, stream()) == 0
             torch.cuda.synchronize()
             A.unchanged(); B.unchanged()
             return {"y": Y.cpu()}
-        _exact("rfx_mul", "y", _twice(run)["y"], a.double() * b.double(), ("n", n, "offset", off, sorted(E.forms_mul(n))))
+        judge(twice(run)[0]["y"], a.double() * b.double(), 0.0, ctx=("rfx_mul", "y", "n", n, "offset", off, sorted(E.forms_mul(n))))
 
 
 @pytest.mark.parametrize("shape", E.PRELU_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_prelu(shape):
     """rfx_prelu_fwd / _bwd: y and gx bit for bit (slopes of both signs and 0, x with +-0: the >= side is part of the contract), gslope by
     the K rule on sum |g v|; ws is N C doubles and every one is written"""
-    L, stream = _api()
+    L, _, stream = api()
     N, Cc, Ln = shape
     x, gy, slope = E.prelu_data(N, Cc, Ln, 31 + Ln)
     info = (shape, sorted(E.forms_prelu(*shape)))
 
     def run():
-        X, G, S = _Buf(x.numel(), what="x", init=x), _Buf(x.numel(), what="gy", init=gy), _Buf(Cc, what="slope", init=slope)
-        Y, GX, GS = _Buf(x.numel(), what="y"), _Buf(x.numel(), what="gx"), _Buf(Cc, what="gslope")
-        WS = _Buf(N * Cc, torch.float64, "ws")
+        X, G, S = Guarded(x.numel(), what="x", init=x), Guarded(x.numel(), what="gy", init=gy), Guarded(Cc, what="slope", init=slope)
+        Y, GX, GS = Guarded(x.numel(), what="y"), Guarded(x.numel(), what="gx"), Guarded(Cc, what="gslope")
+        WS = Guarded(N * Cc, torch.float64, "ws")
         assert L.rfx_prelu_fwd(X.ptr(), S.ptr(), Y.ptr(), N, Cc, Ln, stream()) == 0
         assert L.rfx_prelu_bwd(X.ptr(), G.ptr(), S.ptr(), GX.ptr(), WS.ptr(), GS.ptr(), N, Cc, Ln, stream()) == 0
         torch.cuda.synchronize()
@@ -308,20 +207,20 @@ def test_prelu(shape):
         ws = WS.cpu()
         assert bool(torch.isfinite(ws).all()), ("rfx_prelu_bwd", "ws", "slot", int((~torch.isfinite(ws)).nonzero()[0]), "not written")
         return {"y": Y.cpu(), "gx": GX.cpu(), "gslope": GS.cpu()}
-    got = _twice(run)
-    _exact("rfx_prelu_fwd", "y", got["y"], E.act(x, E.PRELU, slope.double().view(1, -1, 1)), info)
+    got, _ = twice(run)
+    judge(got["y"], E.act(x, E.PRELU, slope.double().view(1, -1, 1)), 0.0, ctx=("rfx_prelu_fwd", "y", *info))
     gx, gs, mag = E.prelu_bwd(x, gy, slope)
-    _exact("rfx_prelu_bwd", "gx", got["gx"], gx, info)
-    r = _within("rfx_prelu_bwd", "gslope", got["gslope"], gs, E.k_of("gslope") * E.EPS32 * mag + E.TINY, info)
-    _report(f"prelu_bwd gslope {shape}", [r])
+    judge(got["gx"], gx, 0.0, ctx=("rfx_prelu_bwd", "gx", *info))
+    r = judge(got["gslope"], gs, E.k_of("gslope") * E.EPS32 * mag + E.TINY, ctx=("rfx_prelu_bwd", "gslope", *info))
+    report("ELEM", f"prelu_bwd gslope {shape}", [r])
 
 
 # ---- L1 ----------------------------------------------------------------------------------------------------------------------------
 def _l1(a, b, n, scale, w, gup):
-    L, stream = _api()
-    A, B = _Buf(max(n, 1), what="a", init=a if n else None), _Buf(max(n, 1), what="b", init=b if n else None)
-    WS, OUT, GR = _Buf(E.L1_SLOTS, torch.float64, "ws"), _Buf(1, what="out"), _Buf(max(n, 1), what="g")
-    GUP = _Buf(1, what="gup", init=torch.tensor([gup])) if gup is not None else None
+    L, _, stream = api()
+    A, B = Guarded(max(n, 1), what="a", init=a if n else None), Guarded(max(n, 1), what="b", init=b if n else None)
+    WS, OUT, GR = Guarded(E.L1_SLOTS, torch.float64, "ws"), Guarded(1, what="out"), Guarded(max(n, 1), what="g")
+    GUP = Guarded(1, what="gup", init=torch.tensor([gup])) if gup is not None else None
     assert L.rfx_l1_sum(A.ptr(), B.ptr(), n, WS.ptr(), scale, OUT.ptr(), stream()) == 0
     rg = L.rfx_l1_grad(A.ptr(), B.ptr(), n, w, GUP.ptr() if GUP else None, GR.ptr(), stream())
     torch.cuda.synchronize()
@@ -344,16 +243,16 @@ def test_l1(n, gup):
         rg, OUT, GR, slots = _l1(a, b, n, scale, scale, gup)
         assert rg == 0
         return {"out": OUT.cpu(), "g": GR.cpu(), "slots": slots.nan_to_num(-1.0)}
-    got = _twice(run)
+    got, _ = twice(run)
     total = float(E.l1_terms(a, b).sum())
     bound = E.l1_bound(n, total, scale)
-    r = _within("rfx_l1_sum", "out", got["out"], torch.tensor([E.l1_sum(a, b, scale)], dtype=torch.float64),
-                torch.tensor([bound], dtype=torch.float64), ("n", n, sorted(E.forms_l1(n, gup))))
+    r = judge(got["out"], torch.tensor([E.l1_sum(a, b, scale)], dtype=torch.float64), torch.tensor([bound], dtype=torch.float64),
+              ctx=("rfx_l1_sum", "out", "n", n, sorted(E.forms_l1(n, gup))))
     assert 10.0 * scale > bound                                   # leaving the last element out moves the sum by more than the bound
-    _exact("rfx_l1_grad", "g", got["g"], E.l1_grad(a, b, scale, gup), ("n", n, "gup", gup))
+    judge(got["g"], E.l1_grad(a, b, scale, gup), 0.0, ctx=("rfx_l1_grad", "g", "n", n, "gup", gup))
     if n >= 1025:
         assert bool((got["g"][100:200] == 0).all())
-    _report(f"l1_sum n={n}", [r])
+    report("ELEM", f"l1_sum n={n}", [r])
 
 
 def test_l1_n0():
@@ -370,31 +269,31 @@ def test_l1_n0():
 def test_channel_sum(case):
     """rfx_channel_sum with the workspace rfx_channel_sum_ws returns for the same arguments (exactly that many doubles, all written, a
     guard behind): the plane kernel by the K rule on sum |x|, the strided kernel by the fp64-sum bound"""
-    L, stream = _api()
+    L, _, stream = api()
     base, off, (N, Cc, A, B), st = E.channel_view(case, 51)
     view = base[off:].as_strided((N, Cc, A, B), st)
     slots, nseg = E.channel_geometry(case["x_off"], N, Cc, A, B, *st)
     info = (case["name"], "slots", slots, "nseg", nseg, sorted(E.forms_channel(case["x_off"], N, Cc, A, B, *st)))
 
     def run():
-        X = _Buf(base.numel(), what="x", init=base)
+        X = Guarded(base.numel(), what="x", init=base)
         assert X.t.data_ptr() % 16 == 0
         count = L.rfx_channel_sum_ws(X.ptr(off), N, Cc, A, B, *st)
         assert count == Cc * slots, ("rfx_channel_sum_ws", count, Cc * slots, info)
-        WS, OUT = _Buf(count, torch.float64, "ws"), _Buf(Cc, what="out")
+        WS, OUT = Guarded(count, torch.float64, "ws"), Guarded(Cc, what="out")
         assert L.rfx_channel_sum(X.ptr(off), N, Cc, A, B, *st, WS.ptr(), OUT.ptr(), stream()) == 0
         torch.cuda.synchronize()
         X.unchanged()
         ws = WS.cpu()
         assert bool(torch.isfinite(ws).all()), ("rfx_channel_sum", "ws", "slot", int((~torch.isfinite(ws)).nonzero()[0]), "not written", info)
         return {"out": OUT.cpu(), "ws": ws}
-    got = _twice(run)["out"]
+    got = twice(run)[0]["out"]
     ref, sabs = E.channel_sum(view)
     bound = E.channel_bound(case["x_off"], N, Cc, A, B, *st, sabs)
     if case["const"]:
         bound[1] = float(E.channel_bound(case["x_off"], N, Cc, A, B, *st, sabs[1], const=True))
     assert bool((view[N - 1, :, A - 1, B - 1].double().abs() > bound).all())      # leaving the last element out moves the sum by more than the bound
-    _report(f"channel_sum {case['name']}", [_within("rfx_channel_sum", "out", got, ref, bound, info)])
+    report("ELEM", f"channel_sum {case['name']}", [judge(got, ref, bound, ctx=("rfx_channel_sum", "out", *info))])
 
 
 # ---- add_bcast ---------------------------------------------------------------------------------------------------------------------
@@ -402,20 +301,20 @@ def test_channel_sum(case):
 def test_add_bcast(case):
     """rfx_add_bcast: the flat form (equal strides; tails, an offset view) and the rows form with every broadcast pattern of the model,
     B in {1, 63, 256, 257}, alpha in {1, -0.5}, 45 rows: 2 half-ulps of |x| + |alpha y| (holds with and without an FMA)"""
-    L, stream = _api()
+    L, _, stream = api()
     N, Cc, A, B, off = case["N"], case["C"], case["A"], case["B"], case["off"]
     x = torch.randn(N, Cc, A, B, generator=torch.Generator().manual_seed(61))
     y, st = E.add_y(case, 62)
     alpha = case["alpha"]
 
     def run():
-        X, Y, O = _Buf(x.numel(), what="x", init=x, off=off), _Buf(y.numel(), what="y", init=y, off=off), _Buf(x.numel(), what="out", off=off)
+        X, Y, O = Guarded(x.numel(), what="x", init=x, off=off), Guarded(y.numel(), what="y", init=y, off=off), Guarded(x.numel(), what="out", off=off)
         assert L.rfx_add_bcast(X.ptr(), Y.ptr(), O.ptr(), N, Cc, A, B, *st, alpha, stream()) == 0
         torch.cuda.synchronize()
         X.unchanged(); Y.unchanged()
         return {"out": O.cpu()}
     ref, mag = E.add_bcast(x, y, st, alpha)
-    _report(f"add_bcast {case['name']}", [_within("rfx_add_bcast", "out", _twice(run)["out"], ref, E.EPS32 * mag, (case["name"], sorted(E.forms_add(case))))])
+    report("ELEM", f"add_bcast {case['name']}", [judge(twice(run)[0]["out"], ref, E.EPS32 * mag, ctx=("rfx_add_bcast", "out", case["name"], sorted(E.forms_add(case))))])
 
 
 # ---- span_mask ---------------------------------------------------------------------------------------------------------------------
@@ -423,21 +322,21 @@ def test_add_bcast(case):
 def test_span_mask(case):
     """rfx_span_mask in place on a random BIT pattern: +0 inside the spans, every bit kept outside (spans inside, empty, covering F,
     t0 < 0, t1 > T, longer than the 256-thread stride, a row in both)"""
-    L, stream = _api()
+    L, _, stream = api()
     R, F, T = case["R"], case["F"], case["T"]
-    bits = torch.randint(-2 ** 31, 2 ** 31 - 1, (R * F * T,), generator=torch.Generator().manual_seed(71), dtype=torch.int64).to(torch.int32)
+    pattern = torch.randint(-2 ** 31, 2 ** 31 - 1, (R * F * T,), generator=torch.Generator().manual_seed(71), dtype=torch.int64).to(torch.int32)
 
     def run():
-        X = _Buf(R * F * T, what="x")
-        X.t.view(torch.int32).copy_(bits)
-        sp = [_Buf(R, torch.int32, k, torch.tensor(case[k], dtype=torch.int32)) for k in ("f0", "f1", "t0", "t1")]
+        X = Guarded(R * F * T, what="x")
+        X.t.view(torch.int32).copy_(pattern)
+        sp = [Guarded(R, torch.int32, k, torch.tensor(case[k], dtype=torch.int32)) for k in ("f0", "f1", "t0", "t1")]
         assert L.rfx_span_mask(X.ptr(), R, F, T, *(s.ptr() for s in sp), stream()) == 0
         torch.cuda.synchronize()
         for s in sp:
             s.unchanged()
         return {"x": X.cpu()}
-    got = _bits(_twice(run)["x"])
-    ref = torch.where(E.span_mask(case).reshape(-1), torch.zeros_like(bits), bits)
+    got = bits(twice(run)[0]["x"])
+    ref = torch.where(E.span_mask(case).reshape(-1), torch.zeros_like(pattern), pattern)
     bad = got != ref
     assert not bool(bad.any()), ("rfx_span_mask", "x", "element", int(bad.nonzero()[0]), "(r, f, t)",
                                  np.unravel_index(int(bad.nonzero()[0]), (R, F, T)), sorted(E.forms_span(case)))
@@ -449,7 +348,7 @@ def test_span_mask(case):
 def test_blstm_frames(case, mode):
     """rfx_blstm_frames: modes 0, 2 (no skip) and 3 bit for bit (zero where tau >= T), mode 2 with skip one rounding, mode 1
     ceil(width / stride) - 1 half-ulps of its terms added in k order; an odd stride, one frame, whole frames of padding"""
-    L, stream = _api()
+    L, _, stream = api()
     B, Cc, T, nfr, width, stride = case
     nx, nh = B * Cc * T, Cc * width * B * nfr
     nsrc, ndst = (nx, nh) if mode in (0, 3) else (nh, nx)
@@ -458,19 +357,19 @@ def test_blstm_frames(case, mode):
     ratios = []
     for with_skip in ((False, True) if mode == 2 else (False,)):
         def run():
-            S, D = _Buf(nsrc, what="src", init=src), _Buf(ndst, what="dst")
-            K = _Buf(nx, what="skip", init=skip) if with_skip else None
+            S, D = Guarded(nsrc, what="src", init=src), Guarded(ndst, what="dst")
+            K = Guarded(nx, what="skip", init=skip) if with_skip else None
             assert L.rfx_blstm_frames(S.ptr(), K.ptr() if K else None, D.ptr(), B, Cc, T, nfr, width, stride, mode, stream()) == 0
             torch.cuda.synchronize()
             S.unchanged()
             if K:
                 K.unchanged()
             return {"dst": D.cpu()}
-        got = _twice(run)["dst"]
+        got = twice(run)[0]["dst"]
         ref, mag, _ = E.blstm_frames(src, skip if with_skip else None, case, mode)
-        ratios.append(_judge("rfx_blstm_frames", "dst", got, ref, E.blstm_bound(case, mode, with_skip, ref, mag),
-                             ("mode", mode, "skip", with_skip, case, sorted(E.forms_blstm(case, mode, with_skip)))))
-    _report(f"blstm_frames {case} mode {mode}", ratios)
+        ratios.append(judge(got, ref, E.blstm_bound(case, mode, with_skip, ref, mag),
+                            ctx=("rfx_blstm_frames", "dst", "mode", mode, "skip", with_skip, case, sorted(E.forms_blstm(case, mode, with_skip)))))
+    report("ELEM", f"blstm_frames {case} mode {mode}", ratios)
 
 
 # ---- row_moments / row_affine ------------------------------------------------------------------------------------------------------
@@ -480,7 +379,7 @@ def test_row_moments(shape, coef):
     """rfx_row_moments: 1, 2, 3 slots, R not a multiple of the finalize workgroup's four rows, a row at mean / std = 1e3 and a constant
     row (std == 0 exactly, a == 1 / eps); sums is 2 R rfx_row_moments_slots(L) doubles, all written.  coef_a / coef_b are judged as
     functions of the fp32 mean / std the kernel stored."""
-    L, stream = _api()
+    L, _, stream = api()
     R, Ln = shape
     x = E.moments_data(R, Ln, 91 + Ln)
     slots = L.rfx_row_moments_slots(Ln)
@@ -488,8 +387,8 @@ def test_row_moments(shape, coef):
     info = (shape, sorted(E.forms_moments(R, Ln, coef)))
 
     def run():
-        X, S = _Buf(R * Ln, what="x", init=x), _Buf(2 * R * slots, torch.float64, "sums")
-        M, D, A, Bc = (_Buf(R, what=k) for k in ("mean", "std", "coef_a", "coef_b"))
+        X, S = Guarded(R * Ln, what="x", init=x), Guarded(2 * R * slots, torch.float64, "sums")
+        M, D, A, Bc = (Guarded(R, what=k) for k in ("mean", "std", "coef_a", "coef_b"))
         assert L.rfx_row_moments(X.ptr(), R, Ln, S.ptr(), M.ptr(), D.ptr(), E.MOMENT_EPS, A.ptr() if coef else None, Bc.ptr() if coef else None,
                                  stream()) == 0
         torch.cuda.synchronize()
@@ -500,30 +399,30 @@ def test_row_moments(shape, coef):
             A.untouched(); Bc.untouched()
             return {"mean": M.cpu(), "std": D.cpu()}
         return {"mean": M.cpu(), "std": D.cpu(), "a": A.cpu(), "b": Bc.cpu()}
-    got = _twice(run)
+    got, _ = twice(run)
     m, sd, bm, bs = E.row_moments(x)
-    ratios = [("mean", _within("rfx_row_moments", "mean", got["mean"], m, bm, info)), ("std", _within("rfx_row_moments", "std", got["std"], sd, bs, info))]
+    ratios = [("mean", judge(got["mean"], m, bm, ctx=("rfx_row_moments", "mean", *info))), ("std", judge(got["std"], sd, bs, ctx=("rfx_row_moments", "std", *info)))]
     if R >= 3:
         assert float(got["std"][R - 1]) == 0.0 and float(got["mean"][R - 1]) == 0.75, "the constant row"
     if coef:
         a, b, ba, bb = E.moments_coef(got["mean"], got["std"], E.MOMENT_EPS)
-        ratios += [("coef_a", _within("rfx_row_moments", "coef_a", got["a"], a, ba, info)), ("coef_b", _within("rfx_row_moments", "coef_b", got["b"], b, bb, info))]
+        ratios += [("coef_a", judge(got["a"], a, ba, ctx=("rfx_row_moments", "coef_a", *info))), ("coef_b", judge(got["b"], b, bb, ctx=("rfx_row_moments", "coef_b", *info)))]
         if R >= 3:
             assert float(got["a"][R - 1]) == float(np.float32(1.0) / np.float32(E.MOMENT_EPS))
-    _report(f"row_moments {shape}", ratios)
+    report("ELEM", f"row_moments {shape}", ratios)
 
 
 @pytest.mark.parametrize("with_b", (False, True), ids=("nob", "b"))
 @pytest.mark.parametrize("shape", E.AFFINE_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_row_affine(shape, with_b):
     """rfx_row_affine: b == NULL bit for bit (one rounded product); with b 2 half-ulps of |x a| + |b| (holds with and without an FMA)"""
-    L, stream = _api()
+    L, _, stream = api()
     R, Ln = shape
     g = torch.Generator().manual_seed(95 + Ln)
     x, a, b = torch.randn(R, Ln, generator=g), torch.randn(R, generator=g) + 2.0, torch.randn(R, generator=g)
 
     def run():
-        X, A, Bc, O = _Buf(R * Ln, what="x", init=x), _Buf(R, what="a", init=a), _Buf(R, what="b", init=b), _Buf(R * Ln, what="out")
+        X, A, Bc, O = Guarded(R * Ln, what="x", init=x), Guarded(R, what="a", init=a), Guarded(R, what="b", init=b), Guarded(R * Ln, what="out")
         assert L.rfx_row_affine(X.ptr(), A.ptr(), Bc.ptr() if with_b else None, O.ptr(), R, Ln, stream()) == 0
         torch.cuda.synchronize()
         for t in (X, A, Bc):
@@ -531,7 +430,7 @@ def test_row_affine(shape, with_b):
         return {"out": O.cpu()}
     ref, mag = E.row_affine(x, a, b if with_b else None)
     bound = E.EPS32 * mag if with_b else torch.zeros_like(mag)
-    _report(f"row_affine {shape} b={with_b}", [_judge("rfx_row_affine", "out", _twice(run)["out"], ref, bound, (shape, sorted(E.forms_affine(R, Ln, with_b))))])
+    report("ELEM", f"row_affine {shape} b={with_b}", [judge(twice(run)[0]["out"], ref, bound, ctx=("rfx_row_affine", "out", shape, sorted(E.forms_affine(R, Ln, with_b))))])
 
 
 # ---- dropout -----------------------------------------------------------------------------------------------------------------------
@@ -541,36 +440,36 @@ def test_row_affine(shape, with_b):
 def test_dropout(n, p, seed):
     """rfx_dropout: the mask and the kept values bit for bit against the integer restatement of the draw (p = 0 keeps everything, times
     exactly 1); a second launch on a gradient with the same seed keeps the same elements"""
-    L, stream = _api()
+    L, _, stream = api()
     x, g = E.signs_data(n, 101 + n), E.signs_data(n, 102 + n)
 
     def run():
         out = {}
         for k, v in (("x", x), ("g", g)):
-            X, O = _Buf(n, what=k, init=v), _Buf(n, what="out")
+            X, O = Guarded(n, what=k, init=v), Guarded(n, what="out")
             assert L.rfx_dropout(X.ptr(), O.ptr(), n, p, seed, stream()) == 0
             torch.cuda.synchronize()
             X.unchanged()
             out[k] = O.cpu()
         return out
-    got = _twice(run)
+    got, _ = twice(run)
     info = ("n", n, "p", p, "seed", hex(seed), sorted(E.forms_dropout(n, p)))
     refx, keep = E.dropout(x, p, seed)
-    _exact("rfx_dropout", "out", got["x"], refx, info)
-    _exact("rfx_dropout", "out (gradient)", got["g"], E.dropout(g, p, seed)[0], info)
+    judge(got["x"], refx, 0.0, ctx=("rfx_dropout", "out", *info))
+    judge(got["g"], E.dropout(g, p, seed)[0], 0.0, ctx=("rfx_dropout", "out (gradient)", *info))
     assert torch.equal(got["g"] != 0, keep) and torch.equal(got["x"] != 0, keep)
     if p == 0.0:
-        assert torch.equal(_bits(got["x"]), _bits(x))
+        assert torch.equal(bits(got["x"]), bits(x))
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------
 def test_refusals_write_nothing():
     """every argument check of every entry point returns nonzero and writes nothing: NULL pointers, non-positive sizes, L <= 1, one of
     coef_a / coef_b, mode outside 0 - 3, T beyond the frames, p outside [0, 1) and NaN; n == 0 returns 0 and touches nothing"""
-    L, stream = _api()
-    bufs = [_Buf(64, what=f"buf{i}") for i in range(6)]
-    wsd = _Buf(1024, torch.float64, "ws")
-    ints = [_Buf(4, torch.int32, f"int{i}") for i in range(4)]
+    L, _, stream = api()
+    bufs = [Guarded(64, what=f"buf{i}") for i in range(6)]
+    wsd = Guarded(1024, torch.float64, "ws")
+    ints = [Guarded(4, torch.int32, f"int{i}") for i in range(4)]
     p = [b.ptr() for b in bufs]
     ip = [b.ptr() for b in ints]
     w, s, Z = wsd.ptr(), stream(), None

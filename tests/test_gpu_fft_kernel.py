@@ -10,24 +10,17 @@ inputs have to come back bit for bit; every case runs twice into fresh buffers: 
 (fft_synthesis_kernel<*, *, atomic>: the order of fp32 atomics is not fixed).  A failure names the entry point, the forms, the output
 and the element (row, frame, bin or sample).  Every case is one the contract allows."""
 import ctypes as C
+import functools
 
 import pytest
 import torch
 
 from tests import fft_ref as F
-from tests.test_gpu_elem_kernel import _Buf, _api, _bits
+from tests.kernel_harness import Guarded, api, bits, judge, report, same_bits, stop_after_a_device_error  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
 
-
-@pytest.fixture(autouse=True)
-def _stop_after_a_device_error():
-    """nothing more is launched on a device that reported an error: the session ends with the test that met it"""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"device error, no further launches: {e}", returncode=3)
+_judge = functools.partial(judge, exact="value")                        # bound 0: the fp64 value rounded once, -0 == +0
 
 
 def _cdesc(d):
@@ -38,44 +31,20 @@ def _cdesc(d):
     return c
 
 
-def _judge(entry, forms, output, got, ref, bound, where):
-    """per element |got - ref| <= bound; bound 0: the fp64 value rounded once, exactly (-0 == +0) -> the largest error / bound"""
-    got, ref, bound = got.double().reshape(-1), ref.double().reshape(-1), bound.double().reshape(-1)
-    assert got.numel() == ref.numel() == bound.numel(), (entry, output, got.numel(), ref.numel(), bound.numel())
-    bad = ~torch.isfinite(got)
-    assert not bool(bad.any()), (entry, forms, output, where(int(bad.nonzero()[0])), "not written / not finite", int(bad.sum()), "of", got.numel())
-    exact = bound == 0
-    q = torch.where(exact, torch.where(got == ref.float().double(), 0.0, float("inf")), (got - ref).abs() / bound.clamp_min(1e-300))
-    j = int(q.argmax())
-    assert float(q[j]) <= 1.0, (entry, forms, output, where(j), "error / bound", float(q[j]), "got", float(got[j]), "ref", float(ref[j]), "bound",
-                                float(bound[j]), "elements over", int((q > 1).sum()), "of", got.numel())
-    return float(q[j])
-
-
-def _same_bits(a, b, what, exempt=False):
-    for k in a:
-        if not exempt:
-            assert torch.equal(_bits(a[k]), _bits(b[k])), (what, k, "second run differs")
-
-
 def _forms_label(forms):
     return sorted(f for f in forms if "<" in f)
 
 
-def _report(entry, name, forms, ratios):
-    print(f"\nFFT {entry} {name} {_forms_label(forms)}: largest error / bound " + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
-
-
 # ---- analysis ----------------------------------------------------------------------------------------------------------------------
 def _run_analysis(d, x, w, mul, x_off):
-    L, stream = _api()
-    X = _Buf(x.numel(), what="x", init=x, off=x_off)
-    W = _Buf(w.numel(), what="window", init=w)
-    M = _Buf(mul.numel(), what="mul", init=mul) if mul is not None else None
+    L, _, stream = api()
+    X = Guarded(x.numel(), what="x", init=x, off=x_off)
+    W = Guarded(w.numel(), what="window", init=w)
+    M = Guarded(mul.numel(), what="mul", init=mul) if mul is not None else None
     n_out = 1
     for s in F.layout_shape(d):
         n_out *= s
-    O = _Buf(n_out, what="out")
+    O = Guarded(n_out, what="out")
     cd = _cdesc(d)
     rc = L.rfx_fft_analysis(C.byref(cd), X.ptr(), W.ptr(), M.ptr() if M else None, O.ptr(), stream())
     torch.cuda.synchronize()
@@ -104,28 +73,24 @@ def test_analysis(name):
             assert rc == 0, ("rfx_fft_analysis", name, rc)
             return {"out": O.cpu()}
         a, b = run(), run()
-        _same_bits(a, b, ("rfx_fft_analysis", name, F.MODE_NAMES[mode]))
-        r = _judge("rfx_fft_analysis", sorted(forms), "out", a["out"], ref, bound, lambda j: F.cell_index(d, j))
-        _report("rfx_fft_analysis", name, forms, {F.MODE_NAMES[mode]: r})
+        same_bits(a, b, ("rfx_fft_analysis", name, F.MODE_NAMES[mode]))
+        r = _judge(a["out"], ref, bound, ctx=("rfx_fft_analysis", sorted(forms), "out"))
+        report("FFT", "rfx_fft_analysis", {F.MODE_NAMES[mode]: r}, f"{name} {_forms_label(forms)}")
 
 
 # ---- synthesis ---------------------------------------------------------------------------------------------------------------------
-def _sample_index(d, j):
-    return f"row {j // d.T} sample {j % d.T}"
-
-
 def _ws_buf(L, cd, d):
     n = int(L.rfx_fft_synthesis_ws(C.byref(cd)))
     assert n == F.syn_ws_floats(d), ("rfx_fft_synthesis_ws", n, F.syn_ws_floats(d))
-    return _Buf(n, what="ws")
+    return Guarded(n, what="ws")
 
 
 def _run_synthesis(d, spec, w, mul, out0):
-    L, stream = _api()
-    S = _Buf(spec.numel(), what="spec", init=spec)
-    W = _Buf(w.numel(), what="window", init=w)
-    M = _Buf(mul.numel(), what="mul", init=mul) if mul is not None else None
-    O = _Buf(d.R * d.T, what="out", init=out0)
+    L, _, stream = api()
+    S = Guarded(spec.numel(), what="spec", init=spec)
+    W = Guarded(w.numel(), what="window", init=w)
+    M = Guarded(mul.numel(), what="mul", init=mul) if mul is not None else None
+    O = Guarded(d.R * d.T, what="out", init=out0)
     cd = _cdesc(d)
     WS = _ws_buf(L, cd, d)
     rc = L.rfx_fft_synthesis(C.byref(cd), S.ptr(), W.ptr(), M.ptr() if M else None, WS.ptr(), O.ptr(), stream())
@@ -154,20 +119,21 @@ def test_synthesis(name):
         assert rc == 0, ("rfx_fft_synthesis", name, rc)
         return {"out": O.cpu()}
     a, b = run(), run()
-    _same_bits(a, b, ("rfx_fft_synthesis", name), exempt=any(",atomic>" in f for f in forms))
-    r = _judge("rfx_fft_synthesis", sorted(forms), "out", a["out"], ref, bound, lambda j: _sample_index(d, j))
-    _report("rfx_fft_synthesis", name, forms, {"out": r})
+    if not any(",atomic>" in f for f in forms):
+        same_bits(a, b, ("rfx_fft_synthesis", name))
+    r = _judge(a["out"], ref, bound, ctx=("rfx_fft_synthesis", sorted(forms), "out"))
+    report("FFT", "rfx_fft_synthesis", {"out": r}, f"{name} {_forms_label(forms)}")
 
 
 # ---- loss gradient inside the synthesis --------------------------------------------------------------------------------------------
 def _run_lossgrad(d, xspec, ymag, sums, gup, w, out0):
-    L, stream = _api()
-    X = _Buf(xspec.numel(), what="xspec", init=xspec)
-    Y = _Buf(ymag.numel(), what="ymag", init=ymag)
-    SM = _Buf(sums.numel(), what="sums", init=sums)
-    G = _Buf(1, what="gup", init=torch.tensor([gup])) if gup is not None else None
-    W = _Buf(w.numel(), what="window", init=w)
-    O = _Buf(d.R * d.T, what="out", init=out0)
+    L, _, stream = api()
+    X = Guarded(xspec.numel(), what="xspec", init=xspec)
+    Y = Guarded(ymag.numel(), what="ymag", init=ymag)
+    SM = Guarded(sums.numel(), what="sums", init=sums)
+    G = Guarded(1, what="gup", init=torch.tensor([gup])) if gup is not None else None
+    W = Guarded(w.numel(), what="window", init=w)
+    O = Guarded(d.R * d.T, what="out", init=out0)
     cd = _cdesc(d)
     WS = _ws_buf(L, cd, d)
     rc = L.rfx_fft_synthesis_lossgrad(C.byref(cd), X.ptr(), Y.ptr(), SM.ptr(), F.LG_W_SC, F.LG_W_LM, F.LG_EPS, G.ptr() if G else None, W.ptr(),
@@ -201,7 +167,8 @@ def test_synthesis_lossgrad(name):
         assert rc == 0, ("rfx_fft_synthesis_lossgrad", name, rc)
         return {"out": O.cpu()}
     a, b = run(), run()
-    _same_bits(a, b, ("rfx_fft_synthesis_lossgrad", name), exempt=any(",atomic>" in f for f in forms))
+    if not any(",atomic>" in f for f in forms):
+        same_bits(a, b, ("rfx_fft_synthesis_lossgrad", name))
     # the two lone one-ulp cells of row 0: the sign of the log term is -1 / +1 if the hardware square root returns |X| = 0.625 exactly
     # (the reference), 0 if it lands on ymag; each frame's two outcomes are closed forms, any of the four combinations is accepted and
     # every other sample is judged the same way under each
@@ -209,8 +176,8 @@ def test_synthesis_lossgrad(name):
     last = None
     for drop in ((), (0,), (1,), (0, 1)):
         try:
-            r = _judge("rfx_fft_synthesis_lossgrad", sorted(forms), "out", a["out"], ref - sum(deltas[i] for i in drop), bound, lambda j: _sample_index(d, j))
-            _report("rfx_fft_synthesis_lossgrad", name, forms, {"out": r, "one-ulp cells with sign 0": float(len(drop))})
+            r = _judge(a["out"], ref - sum(deltas[i] for i in drop), bound, ctx=("rfx_fft_synthesis_lossgrad", sorted(forms), "out"))
+            report("FFT", "rfx_fft_synthesis_lossgrad", {"out": r, "one-ulp cells with sign 0": float(len(drop))}, f"{name} {_forms_label(forms)}")
             return
         except AssertionError as e:
             last = last or e
@@ -219,18 +186,18 @@ def test_synthesis_lossgrad(name):
 
 # ---- pair loss ---------------------------------------------------------------------------------------------------------------------
 def _run_pair(d, x, y, w, store, scale=1.0):
-    L, stream = _api()
-    X = _Buf(x.numel(), what="x", init=x)
-    Y = _Buf(y.numel(), what="y", init=y)
-    W = _Buf(w.numel(), what="window", init=w)
+    L, _, stream = api()
+    X = Guarded(x.numel(), what="x", init=x)
+    Y = Guarded(y.numel(), what="y", init=y)
+    W = Guarded(w.numel(), what="window", init=w)
     cd = _cdesc(F.with_(d, scale=scale))
     nws = int(L.rfx_stft_pair_loss_ws(C.byref(cd)))
     assert nws == 3 * d.R * F.pair_geometry(d)[1], ("rfx_stft_pair_loss_ws", nws)
-    WS = _Buf(nws, dtype=torch.float64, what="ws")
-    SM = _Buf(3 * d.R, what="sums")
+    WS = Guarded(nws, dtype=torch.float64, what="ws")
+    SM = Guarded(3 * d.R, what="sums")
     cells = d.R * d.frames_out * d.bins
-    XS = _Buf(2 * cells, what="xspec") if store else None
-    YM = _Buf(cells, what="ymag") if store else None
+    XS = Guarded(2 * cells, what="xspec") if store else None
+    YM = Guarded(cells, what="ymag") if store else None
     rc = L.rfx_stft_pair_loss(C.byref(cd), X.ptr(), Y.ptr(), W.ptr(), F.EPS, WS.ptr(), SM.ptr(), XS.ptr() if store else None,
                               YM.ptr() if store else None, stream())
     torch.cuda.synchronize()
@@ -262,19 +229,16 @@ def test_pair_loss(name):
                 out.update(xspec=XS.cpu(), ymag=YM.cpu())
             return out
         a, b = run(), run()
-        _same_bits(a, b, ("rfx_stft_pair_loss", name, store))
+        same_bits(a, b, ("rfx_stft_pair_loss", name, store))
         tag = "stored" if store else "sums_only"
-        ratios["sums " + tag] = _judge("rfx_stft_pair_loss", sorted(forms), "sums", a["sums"], ref["sums"], ref["sums_bound"],
-                                       lambda j: f"row {j // 3} sum {j % 3}")
+        ratios["sums " + tag] = _judge(a["sums"], ref["sums"], ref["sums_bound"], ctx=("rfx_stft_pair_loss", sorted(forms), "sums"))
         if d.R > 1:
             s = a["sums"].view(d.R, 3)
             assert float(s[0, 0]) == 0.0 and float(s[0, 2]) == 0.0, ("rfx_stft_pair_loss", name, "row 0 has y == x", s[0].tolist())
         if store:
-            ratios["xspec"] = _judge("rfx_stft_pair_loss", sorted(forms), "xspec", a["xspec"], ref["xspec"], ref["xspec_bound"],
-                                     lambda j: F.cell_index(dfm, j))
-            ratios["ymag"] = _judge("rfx_stft_pair_loss", sorted(forms), "ymag", a["ymag"], ref["ymag"], ref["ymag_bound"],
-                                    lambda j: F.cell_index(dfm, 2 * j))
-    _report("rfx_stft_pair_loss", name, F.forms_pair(d, True), ratios)
+            ratios["xspec"] = _judge(a["xspec"], ref["xspec"], ref["xspec_bound"], ctx=("rfx_stft_pair_loss", sorted(forms), "xspec"))
+            ratios["ymag"] = _judge(a["ymag"], ref["ymag"], ref["ymag_bound"], ctx=("rfx_stft_pair_loss", sorted(forms), "ymag"))
+    report("FFT", "rfx_stft_pair_loss", ratios, f"{name} {_forms_label(F.forms_pair(d, True))}")
 
 
 @pytest.mark.parametrize("name", [c["name"] for c in F.PAIR_NB_CASES])
@@ -300,32 +264,22 @@ def test_pair_loss_many_batches(name):
         assert bool(torch.isfinite(XS.t).all()) and bool(torch.isfinite(YM.t).all()), ("rfx_stft_pair_loss", name, "a stored element is not finite / not written")
         runs.append((SM.t.clone(), XS.t, YM.t))
     for k in range(3):
-        assert torch.equal(_bits(runs[0][k]), _bits(runs[1][k])), ("rfx_stft_pair_loss", name, ("sums", "xspec", "ymag")[k], "second run differs")
+        assert torch.equal(bits(runs[0][k]), bits(runs[1][k])), ("rfx_stft_pair_loss", name, ("sums", "xspec", "ymag")[k], "second run differs")
     sums, XS, YM = runs[0]
     X4, Y3 = XS.view(d.R, d.frames_out, d.bins, 2), YM.view(d.R, d.frames_out, d.bins)
     rows, fr = torch.tensor(ref["rows"], device="cuda"), ref["frames"].cuda()
-    ratios = {"sums": _judge("rfx_stft_pair_loss", forms, "sums", sums.cpu(), ref["sums"], ref["sums_bound"], lambda j: f"row {j // 3} sum {j % 3}")}
+    ratios = {"sums": _judge(sums.cpu(), ref["sums"], ref["sums_bound"], ctx=("rfx_stft_pair_loss", forms, "sums"))}
     assert float(sums.view(d.R, 3)[0, 0]) == 0.0 and float(sums.view(d.R, 3)[0, 2]) == 0.0, ("row 0 has y == x", sums[:3].tolist())
 
-    def where_row(j, per):
-        r, rest = divmod(j, d.frames_out * d.bins * per)
-        f, rest = divmod(rest, d.bins * per)
-        return f"row {ref['rows'][r]} frame {f} bin {rest // per}" + (" im" if per == 2 and rest % 2 else "")
-
-    def where_fr(j, per):
-        r, rest = divmod(j, len(ref["frames"]) * d.bins * per)
-        f, rest = divmod(rest, d.bins * per)
-        return f"row {r} frame {int(ref['frames'][f])} bin {rest // per}" + (" im" if per == 2 and rest % 2 else "")
     ex = lambda b: b[..., None].expand(*b.shape, 2).contiguous()                                # noqa: E731
-    ratios["xspec rows"] = _judge("rfx_stft_pair_loss", forms, "xspec", X4[rows].cpu(), ref["row_x"], ex(ref["row_bx"]), lambda j: where_row(j, 2))
-    ratios["ymag rows"] = _judge("rfx_stft_pair_loss", forms, "ymag", Y3[rows].cpu(), ref["row_ym"], ref["row_bym"], lambda j: where_row(j, 1))
-    ratios["xspec boundaries"] = _judge("rfx_stft_pair_loss", forms, "xspec", X4[:, fr].cpu(), ref["fr_x"], ex(ref["fr_bx"]), lambda j: where_fr(j, 2))
-    ratios["ymag boundaries"] = _judge("rfx_stft_pair_loss", forms, "ymag", Y3[:, fr].cpu(), ref["fr_ym"], ref["fr_bym"], lambda j: where_fr(j, 1))
+    ratios["xspec rows"] = _judge(X4[rows].cpu(), ref["row_x"], ex(ref["row_bx"]), ctx=("rfx_stft_pair_loss", forms, "xspec", "rows", ref["rows"]))
+    ratios["ymag rows"] = _judge(Y3[rows].cpu(), ref["row_ym"], ref["row_bym"], ctx=("rfx_stft_pair_loss", forms, "ymag", "rows", ref["rows"]))
+    ratios["xspec boundaries"] = _judge(X4[:, fr].cpu(), ref["fr_x"], ex(ref["fr_bx"]), ctx=("rfx_stft_pair_loss", forms, "xspec", "frames", ref["frames"].tolist()))
+    ratios["ymag boundaries"] = _judge(Y3[:, fr].cpu(), ref["fr_ym"], ref["fr_bym"], ctx=("rfx_stft_pair_loss", forms, "ymag", "frames", ref["frames"].tolist()))
     rc, SM, _, _ = _run_pair(d, x, y, w, False)
     assert rc == 0
-    ratios["sums, nothing stored"] = _judge("rfx_stft_pair_loss", sorted(F.forms_pair(d, False)), "sums", SM.cpu(), ref["sums"], ref["sums_bound"],
-                                            lambda j: f"row {j // 3} sum {j % 3}")
-    _report("rfx_stft_pair_loss", name, F.forms_pair(d, True), ratios)
+    ratios["sums, nothing stored"] = _judge(SM.cpu(), ref["sums"], ref["sums_bound"], ctx=("rfx_stft_pair_loss", sorted(F.forms_pair(d, False)), "sums"))
+    report("FFT", "rfx_stft_pair_loss", ratios, f"{name} {_forms_label(F.forms_pair(d, True))}")
 
 
 # ---- the cell kernels of losses.hip ------------------------------------------------------------------------------------------------
@@ -341,25 +295,25 @@ def test_loss_reduce(R, n):
     spectra are the inputs, so no cell carries an interval.  n = 1 ... one
     more than a whole unroll-by-eight round (the clamped index at n - 1), several slots and a second grid-stride round; X = 0 and
     |X|^2 at, just below and just above eps are among the cells."""
-    L, stream = _api()
+    L, _, stream = api()
     X, Y, _, _ = F.cell_inputs(R, n, 100 * R + n)
     z = torch.zeros(R, n, dtype=torch.float64)
     ref = F.loss_sums(X, Y, F.CELL_EPS)
     bound = F.loss_sums_bound(X.to(torch.complex128), Y.to(torch.complex128), z, z, F.CELL_EPS, group=8)
 
     def run():
-        XB, YB = _Buf(2 * R * n, what="xc", init=_pairs(X)), _Buf(2 * R * n, what="yc", init=_pairs(Y))
-        WS = _Buf(3 * R * F.REDUCE_SLOTS, dtype=torch.float64, what="ws")
-        SM = _Buf(3 * R, what="sums")
+        XB, YB = Guarded(2 * R * n, what="xc", init=_pairs(X)), Guarded(2 * R * n, what="yc", init=_pairs(Y))
+        WS = Guarded(3 * R * F.REDUCE_SLOTS, dtype=torch.float64, what="ws")
+        SM = Guarded(3 * R, what="sums")
         rc = L.rfx_stft_loss_reduce(XB.ptr(), YB.ptr(), R, n, F.CELL_EPS, WS.ptr(), SM.ptr(), stream())
         torch.cuda.synchronize()
         assert rc == 0, ("rfx_stft_loss_reduce", rc)
         XB.unchanged(), YB.unchanged(), WS.guards_intact()
         return {"sums": SM.cpu()}
     a, b = run(), run()
-    _same_bits(a, b, ("rfx_stft_loss_reduce", R, n))
+    same_bits(a, b, ("rfx_stft_loss_reduce", R, n))
     forms = F.forms_cells(n, "reduce")
-    r = _judge("rfx_stft_loss_reduce", sorted(forms), "sums", a["sums"], ref, bound, lambda j: f"row {j // 3} sum {j % 3}")
+    r = _judge(a["sums"], ref, bound, ctx=("rfx_stft_loss_reduce", sorted(forms), "sums"))
     print(f"\nFFT rfx_stft_loss_reduce R={R} n={n} {sorted(forms)}: largest error / bound {r:.3f}")
 
 
@@ -373,7 +327,7 @@ def test_loss_grad_cells(kernel, R, n):
     gives exactly 0 (the sign is 0 and so is the difference); ymag one ulp above / below |X| gives the log term's sign -- exact for
     the magnitude form, while the spectrum form takes its sign from logf(|X|) - logf(|Y|), which may be 0 within an ulp: there either
     closed form is accepted.  gup null and set; a row whose A is 0."""
-    L, stream = _api()
+    L, _, stream = api()
     X, Y, ymag, sums = F.cell_inputs(R, n, 100 * R + n)
     ratios = {}
     for gup in (None, 1.7):
@@ -384,11 +338,11 @@ def test_loss_grad_cells(kernel, R, n):
         ref, bound = _pairs(G), (F.k_cell() * F.EPS32 * mag)[..., None].expand(-1, -1, 2).contiguous()
 
         def run():
-            XB = _Buf(2 * R * n, what="xc", init=_pairs(X))
-            TB = _Buf(2 * R * n, what="yc", init=_pairs(Y)) if kernel == "yc" else _Buf(R * n, what="ymag", init=ymag)
-            SM = _Buf(3 * R, what="sums", init=sums)
-            U = _Buf(1, what="gup", init=torch.tensor([gup])) if gup is not None else None
-            O = _Buf(2 * R * n, what="gxc")
+            XB = Guarded(2 * R * n, what="xc", init=_pairs(X))
+            TB = Guarded(2 * R * n, what="yc", init=_pairs(Y)) if kernel == "yc" else Guarded(R * n, what="ymag", init=ymag)
+            SM = Guarded(3 * R, what="sums", init=sums)
+            U = Guarded(1, what="gup", init=torch.tensor([gup])) if gup is not None else None
+            O = Guarded(2 * R * n, what="gxc")
             fn = L.rfx_stft_loss_grad if kernel == "yc" else L.rfx_stft_loss_grad_m
             rc = fn(XB.ptr(), TB.ptr(), R, n, F.CELL_EPS, SM.ptr(), F.LG_W_SC, F.LG_W_LM, U.ptr() if U else None, O.ptr(), stream())
             torch.cuda.synchronize()
@@ -397,7 +351,7 @@ def test_loss_grad_cells(kernel, R, n):
                 bb.unchanged()
             return {"gxc": O.cpu()}
         a, b = run(), run()
-        _same_bits(a, b, ("stft_loss_grad_kernel", kernel, R, n))
+        same_bits(a, b, ("stft_loss_grad_kernel", kernel, R, n))
         got = a["gxc"].view(R, n, 2).clone()
         if kernel == "yc" and n >= 255:
             # the two one-ulp cells of the spectrum form: the sign term may be absent (logf(|X|) == logf(|Y|)); the other closed form
@@ -407,8 +361,7 @@ def test_loss_grad_cells(kernel, R, n):
                 use_alt = ((got[:, c].double() - alt).abs() <= bound[:, c]).all(-1)
                 ref[:, c] = torch.where(use_alt[:, None], alt, ref[:, c])
         forms = F.forms_cells(n, kernel, gup is not None)
-        ratios["gup" if gup else "no_gup"] = _judge("rfx_stft_loss_grad" + ("_m" if kernel == "ymag" else ""), sorted(forms), "gxc", got, ref, bound,
-                                                    lambda j: f"row {j // (2 * n)} cell {j % (2 * n) // 2} {'im' if j % 2 else 're'}")
+        ratios["gup" if gup else "no_gup"] = _judge(got, ref, bound, ctx=("rfx_stft_loss_grad" + ("_m" if kernel == "ymag" else ""), sorted(forms), "gxc"))
         if n >= 255:
             c = F.DESIGNATED_COL
             assert bool((got[:, c:c + 3] == 0).all()) and bool((got[:, c + 4] == 0).all()), (kernel, "designated cells", got[:, c:c + 7].tolist())
@@ -420,11 +373,11 @@ def test_refusals():
     """What the entry points refuse returns its code and writes nothing (a refusal launches nothing): a null descriptor, an output mode
     the synthesis has no layout for, xspec without ymag, and for the pair loss n_fft = 4096, extra pads, frame0 != 0, short bins and
     scale != 1 (the kernel applies no scale); rfx_fft_synthesis_ws and rfx_stft_pair_loss_ws return -1 for descriptors no kernel covers."""
-    L, stream = _api()
+    L, _, stream = api()
     d = F.desc(3, 3000, 512, 128, 512, mode=F.FM)
     x, w = F.signal(3, 3000, 1), F.hann(512)
-    X, W = _Buf(x.numel(), what="x", init=x), _Buf(512, what="window", init=w)
-    O = _Buf(3 * d.frames_out * d.bins * 2, what="out")
+    X, W = Guarded(x.numel(), what="x", init=x), Guarded(512, what="window", init=w)
+    O = Guarded(3 * d.frames_out * d.bins * 2, what="out")
     assert L.rfx_fft_analysis(None, X.ptr(), W.ptr(), None, O.ptr(), stream()) != 0
     assert L.rfx_fft_synthesis_ws(None) == -1 and L.rfx_stft_pair_loss_ws(None) == -1
     for bad in (F.with_(d, n_fft=500), F.with_(d, n_fft=8), F.with_(d, win=513), F.with_(d, bins=258), F.with_(d, hop=0), F.with_(d, frames_out=0)):
@@ -432,9 +385,9 @@ def test_refusals():
         assert L.rfx_fft_analysis(C.byref(cd), X.ptr(), W.ptr(), None, O.ptr(), stream()) != 0, vars(bad)
         assert L.rfx_fft_synthesis_ws(C.byref(cd)) == -1, vars(bad)
     assert L.rfx_stft_pair_loss_ws(C.byref(_cdesc(F.with_(d, n_fft=4096, win=4096, bins=2049)))) == -1
-    spec = _Buf(3 * d.frames_out * d.bins * 2, what="spec", init=torch.randn(3 * d.frames_out * d.bins * 2))
-    T = _Buf(3 * 3000, what="signal out")
-    WS = _Buf(F.syn_ws_floats(d), what="ws")
+    spec = Guarded(3 * d.frames_out * d.bins * 2, what="spec", init=torch.randn(3 * d.frames_out * d.bins * 2))
+    T = Guarded(3 * 3000, what="signal out")
+    WS = Guarded(F.syn_ws_floats(d), what="ws")
     assert L.rfx_fft_synthesis(None, spec.ptr(), W.ptr(), None, WS.ptr(), T.ptr(), stream()) != 0
     for mode in (F.MAG, F.POW, F.MAGPOW, 6, -1):
         for n_fft in (512, 256):
@@ -442,16 +395,16 @@ def test_refusals():
             assert L.rfx_fft_synthesis(C.byref(cd), spec.ptr(), W.ptr(), None, WS.ptr(), T.ptr(), stream()) == -1, (mode, n_fft)
     cd = _cdesc(d)
     assert L.rfx_fft_synthesis(C.byref(cd), spec.ptr(), W.ptr(), None, None, T.ptr(), stream()) == -1          # the ownership form without scratch
-    ym, sm = _Buf(3 * d.frames_out * d.bins, what="ymag", init=torch.ones(3 * d.frames_out * d.bins)), _Buf(9, what="sums", init=torch.ones(9))
+    ym, sm = Guarded(3 * d.frames_out * d.bins, what="ymag", init=torch.ones(3 * d.frames_out * d.bins)), Guarded(9, what="sums", init=torch.ones(9))
     assert L.rfx_fft_synthesis_lossgrad(C.byref(cd), spec.ptr(), None, sm.ptr(), 1.0, 1.0, F.EPS, None, W.ptr(), WS.ptr(), T.ptr(), stream()) == -1
     assert L.rfx_fft_synthesis_lossgrad(C.byref(cd), spec.ptr(), ym.ptr(), None, 1.0, 1.0, F.EPS, None, W.ptr(), WS.ptr(), T.ptr(), stream()) == -1
     assert L.rfx_fft_synthesis_lossgrad(C.byref(_cdesc(F.with_(d, mode=F.COMPLEX))), spec.ptr(), ym.ptr(), sm.ptr(), 1.0, 1.0, F.EPS, None, W.ptr(),
                                         WS.ptr(), T.ptr(), stream()) == -1
     assert L.rfx_fft_synthesis_lossgrad(None, spec.ptr(), ym.ptr(), sm.ptr(), 1.0, 1.0, F.EPS, None, W.ptr(), WS.ptr(), T.ptr(), stream()) == -1
     # pair loss
-    PW = _Buf(3 * F.pair_geometry(d)[1], dtype=torch.float64, what="pair ws")
-    SM = _Buf(9, what="pair sums")
-    XS, YM = _Buf(3 * d.frames_out * d.bins * 2, what="xspec"), _Buf(3 * d.frames_out * d.bins, what="ymag out")
+    PW = Guarded(3 * F.pair_geometry(d)[1], dtype=torch.float64, what="pair ws")
+    SM = Guarded(9, what="pair sums")
+    XS, YM = Guarded(3 * d.frames_out * d.bins * 2, what="xspec"), Guarded(3 * d.frames_out * d.bins, what="ymag out")
     bads = dict(null=None, n4096=F.with_(d, n_fft=4096, win=4096, bins=2049), pads=F.with_(d, extra_pad_l=3), pad_r=F.with_(d, extra_pad_r=3),
                 frame0=F.with_(d, frame0=1, frames_out=d.frames_out - 1), bins=F.with_(d, bins=256), in_mode=F.with_(d, in_mode=1),
                 scale=F.with_(d, scale=0.5), scale2=F.with_(d, scale=F.f32(1.0 / 512 ** 0.5)))

@@ -10,122 +10,30 @@ judged by the same bound in both runs.  Stages that leave their intermediate res
 limiter's stage 1 and stage 2 envelope, the SoX banks, the phaser's coefficients) are judged there, and the stage after them given those
 very bits.  A failure names the entry point, the forms, the output and the element."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 from tests import fx_ref as X
+from tests.kernel_harness import Guarded, api, host, judge, report, stop_after_a_device_error, sync, twice  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
 
-GUARD = 4096
-_INT = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
-_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32}
-
-
-def _bits(t):
-    return t.contiguous().view(_INT[t.element_size()])
-
-
-class _Buf:
-    """n elements `off` elements into the space between two NaN guards (off = 0: aligned to 8 KiB at least)"""
-
-    def __init__(self, n, dtype=torch.float32, what="", init=None, off=0):
-        self.what, self.n = what, n
-        ftype = {torch.int32: torch.float32}.get(dtype, dtype)
-        self.buf = torch.full((GUARD + off + n + GUARD,), float("nan"), device="cuda", dtype=ftype)
-        self.fill = _bits(self.buf[:1]).clone()
-        self.t = self.buf[GUARD + off:GUARD + off + n]
-        if dtype != ftype:
-            self.t = self.t.view(dtype)
-        if init is not None:
-            self.t.copy_(init.reshape(-1).to(dtype))
-        self.before = self.buf.clone()
-
-    def ptr(self, elements=0):
-        return C.c_void_p(self.t.data_ptr() + elements * self.t.element_size())
-
-    def unchanged(self):
-        assert torch.equal(_bits(self.buf), _bits(self.before)), f"{self.what} was written"
-
-    def guards_intact(self):
-        b, lo = _bits(self.buf), self.buf.numel() - GUARD
-        assert bool((b[:lo - self.n] == self.fill).all()) and bool((b[lo:] == self.fill).all()), f"{self.what}: guard overwritten"
-
-    def untouched(self):
-        assert bool((_bits(self.buf) == self.fill).all()), f"{self.what}: written by a call that had to leave it alone"
-
-    def np(self, shape=None):
-        self.guards_intact()
-        a = self.t.cpu().numpy()
-        return a.reshape(shape) if shape else a
-
-
-def _in(arr, what, off=0):
-    arr = np.ascontiguousarray(arr)
-    return _Buf(arr.size, _TORCH[arr.dtype], what, torch.from_numpy(arr), off)
-
-
-def _api():
-    from remfx_amd import _lib
-    from remfx_amd.ops import _stream
-    return _lib.lib(), _stream
-
-
-def _host(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _judge(entry, output, got, ref, bound, info=()):
-    """per element: |got - ref| <= bound; where the bound is 0, the fp64 value rounded once to the output's type, bit for bit.
-    -> the largest error / bound"""
-    got, ref, bound = np.asarray(got).reshape(-1), np.asarray(ref, np.float64).reshape(-1), np.asarray(bound, np.float64).reshape(-1)
-    assert got.shape == ref.shape == bound.shape, (entry, output, got.shape, ref.shape, bound.shape)
-    same_inf = np.isinf(ref) & (got.astype(np.float64) == ref)
-    bad = ~np.isfinite(got) & ~same_inf
-    assert not bad.any(), (entry, output, "element", int(bad.nonzero()[0][0]), "of", got.size, "not written / not finite", *info)
-    err = np.where(same_inf, 0.0, np.abs(got.astype(np.float64) - np.where(same_inf, 0.0, ref)))
-    exact = bound == 0.0
-    miss = np.where(exact, got != ref.astype(got.dtype), err > bound)
-    if miss.any():
-        j = int(miss.nonzero()[0][0])
-        raise AssertionError((entry, output, "element", j, "of", got.size, "got", float(got[j]), "ref", float(ref[j]), "bound", float(bound[j]),
-                              "error / bound", float(err[j] / max(bound[j], 1e-300)), "missing", int(miss.sum()), *info))
-    return float((err[~exact] / bound[~exact]).max()) if (~exact).any() else 0.0
-
-
-def _twice(run, same_bits=True):
-    a, b = run(), run()
-    if same_bits:
-        for k in a:
-            assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (k, "second run differs")
-    return a, b
-
-
-def _report(entry, ratios):
-    best = {}
-    for k, v in ratios:
-        best[k] = max(best.get(k, 0.0), v)
-    print(f"\nFX {entry}: largest error / bound " + ", ".join(f"{k} {v:.3f}" for k, v in best.items()))
-
+_judge = functools.partial(judge, exact="value", equal_inf=True)       # -0 == +0; an infinity the reference has too is a result
 
 def _ids(c):
     return "-".join(f"{k}{v}" for k, v in c.items() if k in ("B", "C", "Cin", "T", "NS", "chunk", "hop", "sr", "off", "long"))
 
 
-def _sync(rc, entry, info):
-    torch.cuda.synchronize()
-    assert rc == 0, (entry, "returned", rc, *info)
-
-
 # ---- the 16-byte streams: distortion, widener ------------------------------------------------------------------------------------------
 def _run_dist(x, g, off=0, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb, Gb = _in(x, "x", off), _in(g, "gain")
-    Y = Xb if inplace else _Buf(x.size, what="y", off=off)
-    _sync(L.rfx_fx_distortion(Xb.ptr(), Y.ptr(), B, T, Gb.ptr(), stream()), "rfx_fx_distortion", (B, T))
+    Xb, Gb = Guarded.of(x, "x", off), Guarded.of(g, "gain")
+    Y = Xb if inplace else Guarded(x.size, what="y", off=off)
+    sync(L.rfx_fx_distortion(Xb.ptr(), Y.ptr(), B, T, Gb.ptr(), stream()), "rfx_fx_distortion", (B, T))
     Gb.unchanged()
     if not inplace:
         Xb.unchanged()
@@ -138,18 +46,18 @@ def test_distortion(c):
     the grid-stride loop; in place gives the same bits"""
     x, g = X.dist_data(c)
     forms = sorted(X.forms_distortion(c))
-    a, _ = _twice(lambda: _run_dist(x, g, c.get("off", 0)))
-    r = _judge("rfx_fx_distortion", "y", a["y"], X.distortion(x, g), X.distortion_bound(x, g), forms)
+    a, _ = twice(lambda: _run_dist(x, g, c.get("off", 0)))
+    r = _judge(a["y"], X.distortion(x, g), X.distortion_bound(x, g), ctx=("rfx_fx_distortion", "y", *forms))
     assert np.array_equal(_run_dist(x, g, c.get("off", 0), True)["y"], a["y"]), ("rfx_fx_distortion", "in place differs", forms)
-    _report("distortion " + _ids(c), [("y", r)])
+    report("FX", "distortion " + _ids(c), [("y", r)])
 
 
 def _run_wide(x, gm, gs, off=0, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape[0], x.shape[-1]
-    Xb, A, S = _in(x, "x", off), _in(gm, "g_mid"), _in(gs, "g_side")
-    Y = Xb if inplace else _Buf(x.size, what="y", off=off)
-    _sync(L.rfx_fx_widener(Xb.ptr(), Y.ptr(), B, T, A.ptr(), S.ptr(), stream()), "rfx_fx_widener", (B, T))
+    Xb, A, S = Guarded.of(x, "x", off), Guarded.of(gm, "g_mid"), Guarded.of(gs, "g_side")
+    Y = Xb if inplace else Guarded(x.size, what="y", off=off)
+    sync(L.rfx_fx_widener(Xb.ptr(), Y.ptr(), B, T, A.ptr(), S.ptr(), stream()), "rfx_fx_widener", (B, T))
     A.unchanged(), S.unchanged()
     if not inplace:
         Xb.unchanged()
@@ -162,20 +70,20 @@ def test_widener(c):
     test_fx_ref_cpu.py ties to the recorded reference output and to the fp64 statement; in place gives the same bits"""
     x, gm, gs = X.wide_data(c)
     forms = sorted(X.forms_widener(c))
-    a, _ = _twice(lambda: _run_wide(x, gm, gs, c.get("off", 0)))
+    a, _ = twice(lambda: _run_wide(x, gm, gs, c.get("off", 0)))
     ref = X.restate_widener(x, gm, gs)
-    _judge("rfx_fx_widener", "y", a["y"], ref, np.zeros(ref.shape), forms)
+    _judge(a["y"], ref, np.zeros(ref.shape), ctx=("rfx_fx_widener", "y", *forms))
     assert np.array_equal(_run_wide(x, gm, gs, c.get("off", 0), True)["y"], a["y"]), ("rfx_fx_widener", "in place differs", forms)
-    _report("widener " + _ids(c), [("y", 0.0)])
+    report("FX", "widener " + _ids(c), [("y", 0.0)])
 
 
 # ---- scale, delay, volume --------------------------------------------------------------------------------------------------------------
 def _run_scale(x, g, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb, Gb = _in(x, "x"), _in(g, "gain")
-    Y = Xb if inplace else _Buf(x.size, what="y")
-    _sync(L.rfx_fx_scale(Xb.ptr(), Y.ptr(), B, T, Gb.ptr(), stream()), "rfx_fx_scale", (B, T))
+    Xb, Gb = Guarded.of(x, "x"), Guarded.of(g, "gain")
+    Y = Xb if inplace else Guarded(x.size, what="y")
+    sync(L.rfx_fx_scale(Xb.ptr(), Y.ptr(), B, T, Gb.ptr(), stream()), "rfx_fx_scale", (B, T))
     Gb.unchanged()
     if not inplace:
         Xb.unchanged()
@@ -186,17 +94,17 @@ def _run_scale(x, g, inplace=False):
 def test_scale(c):
     """one rounding of the fp64-exact product, bit for bit; the second trip; in place"""
     x, g = X.scale_data(c)
-    a, _ = _twice(lambda: _run_scale(x, g))
-    _judge("rfx_fx_scale", "y", a["y"], X.scale(x, g), np.zeros(x.shape), sorted(X.forms_scale(c)))
+    a, _ = twice(lambda: _run_scale(x, g))
+    _judge(a["y"], X.scale(x, g), np.zeros(x.shape), ctx=("rfx_fx_scale", "y", *sorted(X.forms_scale(c))))
     assert np.array_equal(_run_scale(x, g, True)["y"], a["y"])
 
 
 def _run_delay(x, D, fb, mix):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    bufs = [_in(x, "x"), _in(D, "delay"), _in(fb, "feedback"), _in(mix, "mix")]
-    Y = _Buf(x.size, what="y")
-    _sync(L.rfx_fx_delay(bufs[0].ptr(), Y.ptr(), B, T, bufs[1].ptr(), bufs[2].ptr(), bufs[3].ptr(), stream()), "rfx_fx_delay", (B, T))
+    bufs = [Guarded.of(x, "x"), Guarded.of(D, "delay"), Guarded.of(fb, "feedback"), Guarded.of(mix, "mix")]
+    Y = Guarded(x.size, what="y")
+    sync(L.rfx_fx_delay(bufs[0].ptr(), Y.ptr(), B, T, bufs[1].ptr(), bufs[2].ptr(), bufs[3].ptr(), stream()), "rfx_fx_delay", (B, T))
     for b in bufs:
         b.unchanged()
     return {"y": Y.np((B, T))}
@@ -208,15 +116,15 @@ def test_delay(c):
     D > T (no tap); the second trip with D = 200000"""
     x, D, fb, mix = X.delay_data(c)
     ref, bound = X.delay(x, D, fb, mix)
-    a, _ = _twice(lambda: _run_delay(x, D, fb, mix))
-    _report("delay " + _ids(c), [("y", _judge("rfx_fx_delay", "y", a["y"], ref, bound, sorted(X.forms_delay(c))))])
+    a, _ = twice(lambda: _run_delay(x, D, fb, mix))
+    report("FX", "delay " + _ids(c), [("y", _judge(a["y"], ref, bound, ctx=("rfx_fx_delay", "y", *sorted(X.forms_delay(c)))))])
 
 
 def _run_volume(x, ends, d0, d1):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb, E, A, Z = _in(x, "x"), _in(ends, "seg_end"), _in(d0, "db_start"), _in(d1, "db_end")
-    _sync(L.rfx_fx_volume(Xb.ptr(), B, T, ends.shape[1], E.ptr(), A.ptr(), Z.ptr(), stream()), "rfx_fx_volume", (B, T))
+    Xb, E, A, Z = Guarded.of(x, "x"), Guarded.of(ends, "seg_end"), Guarded.of(d0, "db_start"), Guarded.of(d1, "db_end")
+    sync(L.rfx_fx_volume(Xb.ptr(), B, T, ends.shape[1], E.ptr(), A.ptr(), Z.ptr(), stream()), "rfx_fx_volume", (B, T))
     E.unchanged(), A.unchanged(), Z.unchanged()
     return {"x": Xb.np((B, T))}
 
@@ -227,18 +135,18 @@ def test_volume(c):
     one-sample segments, a table ending before, at and beyond T; the second trip"""
     x, ends, d0, d1 = X.vol_data(c)
     ref, bound = X.volume(x, ends, d0, d1)
-    a, _ = _twice(lambda: _run_volume(x, ends, d0, d1))
-    _report("volume " + _ids(c), [("x", _judge("rfx_fx_volume", "x", a["x"], ref, bound, sorted(X.forms_volume(c))))])
+    a, _ = twice(lambda: _run_volume(x, ends, d0, d1))
+    report("FX", "volume " + _ids(c), [("x", _judge(a["x"], ref, bound, ctx=("rfx_fx_volume", "x", *sorted(X.forms_volume(c)))))])
 
 
 # ---- compressor, limiter ---------------------------------------------------------------------------------------------------------------
 def _run_comp(x, thr, ratio, ca, cr, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    bufs = [_in(x, "x"), _in(thr, "thr"), _in(ratio, "ratio"), _in(ca, "c_attack"), _in(cr, "c_release")]
-    Y = bufs[0] if inplace else _Buf(x.size, what="y")
-    W = _Buf(B * T, what="env_ws")                                    # exactly (B, T)
-    _sync(L.rfx_fx_compressor(bufs[0].ptr(), Y.ptr(), W.ptr(), B, T, *(b.ptr() for b in bufs[1:]), stream()), "rfx_fx_compressor", (B, T))
+    bufs = [Guarded.of(x, "x"), Guarded.of(thr, "thr"), Guarded.of(ratio, "ratio"), Guarded.of(ca, "c_attack"), Guarded.of(cr, "c_release")]
+    Y = bufs[0] if inplace else Guarded(x.size, what="y")
+    W = Guarded(B * T, what="env_ws")                                    # exactly (B, T)
+    sync(L.rfx_fx_compressor(bufs[0].ptr(), Y.ptr(), W.ptr(), B, T, *(b.ptr() for b in bufs[1:]), stream()), "rfx_fx_compressor", (B, T))
     for b in bufs[1 if inplace else 0:]:
         b.unchanged()
     return {"y": Y.np((B, T)), "env": W.np((B, T))}
@@ -252,22 +160,22 @@ def test_compressor(c):
     x, thr, ratio, ca, cr = X.comp_data(c)
     forms = sorted(X.forms_compressor(c))
     env, mag = X.comp_env(x, ca, cr)
-    a, _ = _twice(lambda: _run_comp(x, thr, ratio, ca, cr))
-    r1 = _judge("rfx_fx_compressor", "env_ws", a["env"], env, X.comp_env_bound(mag), forms)
+    a, _ = twice(lambda: _run_comp(x, thr, ratio, ca, cr))
+    r1 = _judge(a["env"], env, X.comp_env_bound(mag), ctx=("rfx_fx_compressor", "env_ws", *forms))
     y, yb = X.compressor_y(x, a["env"], thr, ratio)
-    r2 = _judge("rfx_fx_compressor", "y", a["y"], y, yb, forms)
+    r2 = _judge(a["y"], y, yb, ctx=("rfx_fx_compressor", "y", *forms))
     b = _run_comp(x, thr, ratio, ca, cr, True)
     assert np.array_equal(b["y"], a["y"]) and np.array_equal(b["env"], a["env"]), ("rfx_fx_compressor", "in place differs", forms)
-    _report("compressor " + _ids(c), [("env", r1), ("y", r2)])
+    report("FX", "compressor " + _ids(c), [("env", r1), ("y", r2)])
 
 
 def _run_limit(x, p, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb, P = _in(x, "x"), _in(p, "params")
-    Y = Xb if inplace else _Buf(x.size, what="y")
-    W = _Buf(2 * B * T, what="ws")                                    # exactly 2 B T
-    _sync(L.rfx_fx_limiter(Xb.ptr(), Y.ptr(), W.ptr(), B, T, P.ptr(), stream()), "rfx_fx_limiter", (B, T))
+    Xb, P = Guarded.of(x, "x"), Guarded.of(p, "params")
+    Y = Xb if inplace else Guarded(x.size, what="y")
+    W = Guarded(2 * B * T, what="ws")                                    # exactly 2 B T
+    sync(L.rfx_fx_limiter(Xb.ptr(), Y.ptr(), W.ptr(), B, T, P.ptr(), stream()), "rfx_fx_limiter", (B, T))
     P.unchanged()
     if not inplace:
         Xb.unchanged()
@@ -283,24 +191,24 @@ def test_limiter(c):
     x, p = X.limit_data(c)
     forms = sorted(X.forms_limiter(c))
     y1, b1 = X.limiter_stage1(x, p)
-    a, _ = _twice(lambda: _run_limit(x, p))
-    r1 = _judge("rfx_fx_limiter", "ws stage 1", a["y1"], y1, b1, forms)
+    a, _ = twice(lambda: _run_limit(x, p))
+    r1 = _judge(a["y1"], y1, b1, ctx=("rfx_fx_limiter", "ws stage 1", *forms))
     e2, m2 = X.comp_env(a["y1"], p[6], p[7])
-    r2 = _judge("rfx_fx_limiter", "ws envelope 2", a["env2"], e2, X.comp_env_bound(m2), forms)
+    r2 = _judge(a["env2"], e2, X.comp_env_bound(m2), ctx=("rfx_fx_limiter", "ws envelope 2", *forms))
     y, yb, _ = X.limiter_out(a["y1"], a["env2"], p)
-    r3 = _judge("rfx_fx_limiter", "y", a["y"], y, yb, forms)
+    r3 = _judge(a["y"], y, yb, ctx=("rfx_fx_limiter", "y", *forms))
     assert np.array_equal(_run_limit(x, p, True)["y"], a["y"]), ("rfx_fx_limiter", "in place differs", forms)
-    _report("limiter " + _ids(c), [("stage1", r1), ("env2", r2), ("y", r3)])
+    report("FX", "limiter " + _ids(c), [("stage1", r1), ("env2", r2), ("y", r3)])
 
 
 # ---- chorus, reverb --------------------------------------------------------------------------------------------------------------------
 def _run_chorus(x, sr, prm, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb = _in(x, "x")
-    P = [_in(p, n) for p, n in zip(prm, ("rate", "depth", "centre", "feedback", "mix"))]
-    Y = Xb if inplace else _Buf(x.size, what="y")
-    _sync(L.rfx_fx_chorus(Xb.ptr(), Y.ptr(), B, T, float(sr), *(p.ptr() for p in P), stream()), "rfx_fx_chorus", (B, T, sr))
+    Xb = Guarded.of(x, "x")
+    P = [Guarded.of(p, n) for p, n in zip(prm, ("rate", "depth", "centre", "feedback", "mix"))]
+    Y = Xb if inplace else Guarded(x.size, what="y")
+    sync(L.rfx_fx_chorus(Xb.ptr(), Y.ptr(), B, T, float(sr), *(p.ptr() for p in P), stream()), "rfx_fx_chorus", (B, T, sr))
     for p in P:
         p.unchanged()
     if not inplace:
@@ -317,18 +225,18 @@ def test_chorus(c):
     a_ = X.chorus_data(c)
     forms = sorted(X.forms_chorus(c))
     ref, bound = X.chorus(a_[0], c["sr"], *a_[1:])
-    a, _ = _twice(lambda: _run_chorus(a_[0], c["sr"], a_[1:]))
-    r = _judge("rfx_fx_chorus", "y", a["y"], ref, bound, forms)
+    a, _ = twice(lambda: _run_chorus(a_[0], c["sr"], a_[1:]))
+    r = _judge(a["y"], ref, bound, ctx=("rfx_fx_chorus", "y", *forms))
     assert np.array_equal(_run_chorus(a_[0], c["sr"], a_[1:], True)["y"], a["y"]), ("rfx_fx_chorus", "in place differs", forms)
-    _report("chorus " + _ids(c), [("y", r)])
+    report("FX", "chorus " + _ids(c), [("y", r)])
 
 
 def _run_reverb(x, sr, prm, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb = _in(x, "x")
-    P = [_in(p, n) for p, n in zip(prm, ("damp", "feedback", "wet1", "dry"))]
-    Y = Xb if inplace else _Buf(x.size, what="y")
+    Xb = Guarded.of(x, "x")
+    P = [Guarded.of(p, n) for p, n in zip(prm, ("damp", "feedback", "wet1", "dry"))]
+    Y = Xb if inplace else Guarded(x.size, what="y")
     rc = L.rfx_fx_reverb(Xb.ptr(), Y.ptr(), B, T, int(sr), *(p.ptr() for p in P), stream())
     torch.cuda.synchronize()
     for p in P:
@@ -350,10 +258,10 @@ def test_reverb(c):
         rc, Y = _run_reverb(a_[0], c["sr"], a_[1:], inplace)
         assert rc == 0, ("rfx_fx_reverb", rc, forms)
         return {"y": Y.np(a_[0].shape)}
-    a, _ = _twice(run)
-    r = _judge("rfx_fx_reverb", "y", a["y"], ref, bound, forms)
+    a, _ = twice(run)
+    r = _judge(a["y"], ref, bound, ctx=("rfx_fx_reverb", "y", *forms))
     assert np.array_equal(run(True)["y"], a["y"]), ("rfx_fx_reverb", "in place differs", forms)
-    _report("reverb " + _ids(c), [("y", r)])
+    report("FX", "reverb " + _ids(c), [("y", r)])
 
 
 def test_reverb_rate_range():
@@ -370,18 +278,18 @@ def test_reverb_rate_range():
         rc, Y = _run_reverb(a_[0], sr, a_[1:])
         assert rc == 0, ("rfx_fx_reverb refused", sr, rc)
         ref, bound = X.reverb(a_[0], sr, *a_[1:])
-        _judge("rfx_fx_reverb", "y", Y.np(a_[0].shape), ref, bound, ("rate", sr))
+        _judge(Y.np(a_[0].shape), ref, bound, ctx=("rfx_fx_reverb", "y", "rate", sr))
 
 
 # ---- SoX reverb ------------------------------------------------------------------------------------------------------------------------
 def _run_sox(x, geom, coef, lds, Cin):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape[0], x.shape[-1]
-    Xb, G, Cf = _in(x, "x"), _in(geom, "geom"), _in(coef, "coef")
+    Xb, G, Cf = Guarded.of(x, "x"), Guarded.of(geom, "geom"), Guarded.of(coef, "coef")
     n = int(L.rfx_fx_sox_reverb_ws_floats(B, Cin, T))
     assert n == B * Cin * 2 * T
-    W, Y = _Buf(n, what="ws"), _Buf(B * 2 * T, what="y")
-    _sync(L.rfx_fx_sox_reverb(Xb.ptr(), Y.ptr(), W.ptr(), B, Cin, T, G.ptr(), Cf.ptr(), lds, stream()), "rfx_fx_sox_reverb", (B, Cin, T))
+    W, Y = Guarded(n, what="ws"), Guarded(B * 2 * T, what="y")
+    sync(L.rfx_fx_sox_reverb(Xb.ptr(), Y.ptr(), W.ptr(), B, Cin, T, G.ptr(), Cf.ptr(), lds, stream()), "rfx_fx_sox_reverb", (B, Cin, T))
     Xb.unchanged(), G.unchanged(), Cf.unchanged()
     return {"y": Y.np((B, 2, T)), "ws": W.np((B * Cin * 2, T))}
 
@@ -394,11 +302,11 @@ def test_sox_reverb(c):
     x, geom, coef, lds = X.sox_data(c)
     forms = sorted(X.forms_sox(c))
     ws, wb = X.sox_banks(x, geom, coef)
-    a, _ = _twice(lambda: _run_sox(x, geom, coef, lds, c["Cin"]))
-    r1 = _judge("rfx_fx_sox_reverb", "ws banks", a["ws"], ws, wb, forms)
+    a, _ = twice(lambda: _run_sox(x, geom, coef, lds, c["Cin"]))
+    r1 = _judge(a["ws"], ws, wb, ctx=("rfx_fx_sox_reverb", "ws banks", *forms))
     y, yb = X.sox_mix(x, a["ws"], coef, c["Cin"])
-    r2 = _judge("rfx_fx_sox_reverb", "y", a["y"], y, yb, forms)
-    _report("sox_reverb " + _ids(c), [("banks", r1), ("y", r2)])
+    r2 = _judge(a["y"], y, yb, ctx=("rfx_fx_sox_reverb", "y", *forms))
+    report("FX", "sox_reverb " + _ids(c), [("banks", r1), ("y", r2)])
 
 
 @pytest.mark.parametrize("bad", ("length_0", "beyond_lds"))
@@ -419,20 +327,20 @@ def test_sox_reverb_nan_plan(bad):
     g2 = geom.copy()
     g2[2] = geom[3]                                                        # any valid plan: the row is not judged
     ws, wb = X.sox_banks(x, g2, coef)
-    _judge("rfx_fx_sox_reverb", "ws banks", a["ws"][good], ws[good], wb[good], (bad,))
+    _judge(a["ws"][good], ws[good], wb[good], ctx=("rfx_fx_sox_reverb", "ws banks", bad))
     wsd = np.where(good[:, None], a["ws"], 0.0).astype(np.float32)
     y, yb = X.sox_mix(x, wsd, coef, 1)
     yr, ybr = y.reshape(4, -1), yb.reshape(4, -1)
-    _judge("rfx_fx_sox_reverb", "y", a["y"].reshape(4, -1)[good], yr[good], ybr[good], (bad,))
+    _judge(a["y"].reshape(4, -1)[good], yr[good], ybr[good], ctx=("rfx_fx_sox_reverb", "y", bad))
 
 
 # ---- EQ --------------------------------------------------------------------------------------------------------------------------------
 def _run_eq(x, coef, NS, chunk, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb, Cf = _in(x, "x"), _in(coef, "coef")
-    Y = Xb if inplace else _Buf(x.size, what="y")
-    _sync(L.rfx_fx_eq(Xb.ptr(), Y.ptr(), B, T, NS, chunk, Cf.ptr(), stream()), "rfx_fx_eq", (B, T, NS, chunk))
+    Xb, Cf = Guarded.of(x, "x"), Guarded.of(coef, "coef")
+    Y = Xb if inplace else Guarded(x.size, what="y")
+    sync(L.rfx_fx_eq(Xb.ptr(), Y.ptr(), B, T, NS, chunk, Cf.ptr(), stream()), "rfx_fx_eq", (B, T, NS, chunk))
     Cf.unchanged()
     if not inplace:
         Xb.unchanged()
@@ -446,29 +354,29 @@ def test_eq(c):
     x, sec, coef = X.eq_data(c)
     forms = sorted(X.forms_eq(c))
     ref, bound = X.eq(x, sec)
-    a, _ = _twice(lambda: _run_eq(x, coef, c["NS"], c["chunk"]))
-    r = _judge("rfx_fx_eq", "y", a["y"], ref, bound, forms)
+    a, _ = twice(lambda: _run_eq(x, coef, c["NS"], c["chunk"]))
+    r = _judge(a["y"], ref, bound, ctx=("rfx_fx_eq", "y", *forms))
     assert np.array_equal(_run_eq(x, coef, c["NS"], c["chunk"], True)["y"], a["y"]), ("rfx_fx_eq", "in place differs", forms)
-    _report("eq " + _ids(c), [("y", r)])
+    report("FX", "eq " + _ids(c), [("y", r)])
 
 
 # ---- loudness --------------------------------------------------------------------------------------------------------------------------
 def _run_loud(x, c, coef, inv, joint):
-    L, stream = _api()
+    L, _, stream = api()
     B, Cc, T = x.shape
-    Xb = _in(x, "x")
-    H, Lu, Ga = _Buf(B * Cc * c["nhop"], torch.float64, "hop_ws"), _Buf(B, what="lufs"), _Buf(B, what="gain")
-    tail = (c["chunk"], c["hop"], c["nhop"], c["nblk"], inv, _host(coef), X.LOUD_TARGET, H.ptr(), Lu.ptr(), Ga.ptr(), stream())
+    Xb = Guarded.of(x, "x")
+    H, Lu, Ga = Guarded(B * Cc * c["nhop"], torch.float64, "hop_ws"), Guarded(B, what="lufs"), Guarded(B, what="gain")
+    tail = (c["chunk"], c["hop"], c["nhop"], c["nblk"], inv, host(coef), X.LOUD_TARGET, H.ptr(), Lu.ptr(), Ga.ptr(), stream())
     rc = L.rfx_fx_loudness_joint(Xb.ptr(), B, Cc, T, *tail) if joint else L.rfx_fx_loudness(Xb.ptr(), B, T, *tail)
-    _sync(rc, "rfx_fx_loudness", (B, Cc, T))
+    sync(rc, "rfx_fx_loudness", (B, Cc, T))
     Xb.unchanged()
     return {"hop": H.np((B * Cc, c["nhop"])), "lufs": Lu.np(), "gain": Ga.np()}
 
 
 def _judge_loud(entry, got, res, forms):
-    return [("hop", _judge(entry, "hop_ws", got["hop"], res["hop"], res["hop_bound"], forms)),
-            ("lufs", _judge(entry, "lufs", got["lufs"], res["lufs"], res["lufs_bound"], forms)),
-            ("gain", _judge(entry, "gain", got["gain"], res["gain"], res["gain_bound"], forms))]
+    return [("hop", _judge(got["hop"], res["hop"], res["hop_bound"], ctx=(entry, "hop_ws", *forms))),
+            ("lufs", _judge(got["lufs"], res["lufs"], res["lufs_bound"], ctx=(entry, "lufs", *forms))),
+            ("gain", _judge(got["gain"], res["gain"], res["gain_bound"], ctx=(entry, "gain", *forms)))]
 
 
 @pytest.mark.parametrize("c", X.LOUD_CASES, ids=_ids)
@@ -482,9 +390,9 @@ def test_loudness(c):
     res = X.loudness(x, sec, c)
     ratios = []
     for joint in ((True,) if c["C"] > 1 else (False, True)):
-        for got in _twice(lambda: _run_loud(x, c, coef, inv, joint), same_bits=False):
+        for got in twice(lambda: _run_loud(x, c, coef, inv, joint), same_bits=False):
             ratios += _judge_loud("rfx_fx_loudness_joint" if joint else "rfx_fx_loudness", got, res, forms)
-    _report("loudness " + _ids(c), ratios)
+    report("FX", "loudness " + _ids(c), ratios)
 
 
 @pytest.mark.parametrize("c", X.NORM_CASES, ids=_ids)
@@ -492,7 +400,7 @@ def test_normalize_rows(c):
     """ws of exactly rfx_fx_normalize_ws_bytes: the hop sums, lufs and gain stay readable there; y[rows[i]] = gain[i] x[i] bit for bit
     given that gain, with a permuted table into a larger state whose other rows keep their NaN; without a table, row i, also in
     place of x"""
-    L, stream = _api()
+    L, _, stream = api()
     x, sec, coef, inv = X.loud_data(c)
     n, T, N, nhop = c["B"], c["T"], c["N"], c["nhop"]
     res = X.loudness(x, sec, c)
@@ -501,13 +409,13 @@ def test_normalize_rows(c):
     rows = None if c["rows"] is None else np.asarray(c["rows"], np.int32)
 
     def run(inplace=False):
-        Xb = _in(x, "x")
-        Y = Xb if inplace else _Buf(N * T, what="y")
-        W = _Buf(nbytes // 4, what="ws")
-        R = None if rows is None else _in(rows, "rows")
-        rc = L.rfx_fx_normalize_rows(Xb.ptr(), Y.ptr(), R.ptr() if R else None, n, T, c["chunk"], c["hop"], nhop, c["nblk"], inv, _host(coef),
+        Xb = Guarded.of(x, "x")
+        Y = Xb if inplace else Guarded(N * T, what="y")
+        W = Guarded(nbytes // 4, what="ws")
+        R = None if rows is None else Guarded.of(rows, "rows")
+        rc = L.rfx_fx_normalize_rows(Xb.ptr(), Y.ptr(), R.ptr() if R else None, n, T, c["chunk"], c["hop"], nhop, c["nblk"], inv, host(coef),
                                      X.LOUD_TARGET, W.ptr(), stream())
-        _sync(rc, "rfx_fx_normalize_rows", (n, T))
+        sync(rc, "rfx_fx_normalize_rows", (n, T))
         if R:
             R.unchanged()
         if not inplace:
@@ -517,26 +425,26 @@ def test_normalize_rows(c):
                 "gain": w[n * nhop * 2 + n:]}
     forms = sorted(X.forms_loudness(c))
     ratios = []
-    for got in _twice(run, same_bits=False) + ((run(True),) if rows is None else ()):
+    for got in twice(run, same_bits=False) + ((run(True),) if rows is None else ()):
         ratios += _judge_loud("rfx_fx_normalize_rows", got, res, forms)
         target = list(range(n)) if rows is None else list(rows)
-        _judge("rfx_fx_normalize_rows", "y", got["y"][target], X.scale(x[:, 0], got["gain"]), np.zeros((n, T)), forms)
+        _judge(got["y"][target], X.scale(x[:, 0], got["gain"]), np.zeros((n, T)), ctx=("rfx_fx_normalize_rows", "y", *forms))
         others = [r for r in range(N) if r not in target]
         assert np.isnan(got["y"][others]).all(), "a row outside the table was written"
-    _report("normalize_rows " + _ids(c), ratios)
+    report("FX", "normalize_rows " + _ids(c), ratios)
 
 
 # ---- phaser ----------------------------------------------------------------------------------------------------------------------------
 def _run_phaser(x, prm, inplace=False):
-    L, stream = _api()
+    L, _, stream = api()
     B, T = x.shape
-    Xb = _in(x, "x")
-    P = [_in(p, n) for p, n in zip(prm, ("rate", "depth", "centre", "feedback", "mix"))]
+    Xb = Guarded.of(x, "x")
+    P = [Guarded.of(p, n) for p, n in zip(prm, ("rate", "depth", "centre", "feedback", "mix"))]
     n = int(L.rfx_fx_phaser_ws_floats(B, T))
     assert n == X.phaser_ws_floats(B, T)
-    W = _Buf(n, what="ws")
-    Y = Xb if inplace else _Buf(x.size, what="y")
-    _sync(L.rfx_fx_phaser(Xb.ptr(), Y.ptr(), W.ptr(), B, T, X.PHASER_SR, *(p.ptr() for p in P), stream()), "rfx_fx_phaser", (B, T))
+    W = Guarded(n, what="ws")
+    Y = Xb if inplace else Guarded(x.size, what="y")
+    sync(L.rfx_fx_phaser(Xb.ptr(), Y.ptr(), W.ptr(), B, T, X.PHASER_SR, *(p.ptr() for p in P), stream()), "rfx_fx_phaser", (B, T))
     for p in P:
         p.unchanged()
     if not inplace:
@@ -553,15 +461,15 @@ def test_phaser(c):
     forms = sorted(X.forms_phaser(c))
     M = (c["T"] + 3) // 4
     G, gb = X.phaser_coef(c["T"], X.PHASER_SR, rate, depth, cen)
-    a, _ = _twice(lambda: _run_phaser(x, (rate, depth, cen, fb, mix)))
-    r1 = _judge("rfx_fx_phaser", "ws coefficients", a["G"][:, :M], G, gb, forms)
+    a, _ = twice(lambda: _run_phaser(x, (rate, depth, cen, fb, mix)))
+    r1 = _judge(a["G"][:, :M], G, gb, ctx=("rfx_fx_phaser", "ws coefficients", *forms))
     assert np.isnan(a["G"][:, M:]).all(), "the padding of a coefficient row was written"
     n = c.get("prefix", c["T"])
     y, yb = X.phaser(x[:, :n], a["G"], fb, mix)
-    r2 = _judge("rfx_fx_phaser", "y", a["y"][:, :n], y, yb, forms)
+    r2 = _judge(a["y"][:, :n], y, yb, ctx=("rfx_fx_phaser", "y", *forms))
     assert np.isfinite(a["y"]).all()
     assert np.array_equal(_run_phaser(x, (rate, depth, cen, fb, mix), True)["y"], a["y"]), ("rfx_fx_phaser", "in place differs", forms)
-    _report("phaser " + _ids(c), [("G", r1), ("y", r2)])
+    report("FX", "phaser " + _ids(c), [("G", r1), ("y", r2)])
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------
@@ -569,11 +477,11 @@ def _refusal_table():
     """(entry point, valid arguments, outputs, [(argument index, refused value)]): every -1 condition of the launch code.  The checks are
     on the host: no call of this table launches a kernel"""
     B, T = 2, 8
-    f = lambda n, what: _Buf(n, what=what, init=torch.full((n,), 0.5))                        # noqa: E731
-    i = lambda n, what, v: _Buf(n, torch.int32, what, torch.full((n,), v, dtype=torch.int32))      # noqa: E731
+    f = lambda n, what: Guarded(n, what=what, init=torch.full((n,), 0.5))                        # noqa: E731
+    i = lambda n, what, v: Guarded(n, torch.int32, what, torch.full((n,), v, dtype=torch.int32))      # noqa: E731
     out = []
     nul = lambda idx: [(k, None) for k in idx]                                                # noqa: E731
-    x, y = f(B * T, "x"), _Buf(B * T, what="y")
+    x, y = f(B * T, "x"), Guarded(B * T, what="y")
     g = f(B, "p")
     dims = [(2, 0), (2, -1), (2, 65536), (3, 0), (3, -1)]
     out.append(("rfx_fx_distortion", [x.ptr(), y.ptr(), B, T, g.ptr()], [y], nul((0, 1, 4)) + dims))
@@ -581,54 +489,54 @@ def _refusal_table():
     out.append(("rfx_fx_delay", [x.ptr(), y.ptr(), B, T, d.ptr(), g.ptr(), g.ptr()], [y], nul((0, 1, 4, 5, 6)) + dims + [(1, x.ptr())]))
     out.append(("rfx_fx_chorus", [x.ptr(), y.ptr(), B, T, 48000.0, g.ptr(), g.ptr(), g.ptr(), g.ptr(), g.ptr()], [y],
                 nul((0, 1, 5, 6, 7, 8, 9)) + dims + [(4, 3999.0), (4, 2999.0), (4, 81000.0)]))
-    w = _Buf(2 * B * T, what="ws")
+    w = Guarded(2 * B * T, what="ws")
     out.append(("rfx_fx_compressor", [x.ptr(), y.ptr(), w.ptr(), B, T, g.ptr(), g.ptr(), g.ptr(), g.ptr()], [y, w],
                 nul((0, 1, 2, 5, 6, 7, 8)) + [(3, 0), (3, 65536), (4, 0)]))
     out.append(("rfx_fx_reverb", [x.ptr(), y.ptr(), B, T, 48000, g.ptr(), g.ptr(), g.ptr(), g.ptr()], [y],
                 nul((0, 1, 5, 6, 7, 8)) + dims + [(4, 7999), (4, 192001), (4, 12543), (4, 143527)]))
     p9 = f(9 * B, "params")
     out.append(("rfx_fx_limiter", [x.ptr(), y.ptr(), w.ptr(), B, T, p9.ptr()], [y, w], nul((0, 1, 2, 5)) + [(3, 0), (3, 65536), (4, 0)]))
-    cf = _Buf(B * (10 + 16), torch.float64, "coef", torch.zeros(B * 26, dtype=torch.float64))
+    cf = Guarded(B * (10 + 16), torch.float64, "coef", torch.zeros(B * 26, dtype=torch.float64))
     out.append(("rfx_fx_eq", [x.ptr(), y.ptr(), B, T, 2, 1, cf.ptr()], [y],
                 nul((0, 1, 6)) + dims + [(4, 1), (4, 9), (4, 0), (5, 0), (5, -1)]))
     x64 = f(B * 65, "x65")                                                                     # T = 65 with chunk 1: chunk * 64 < T
     out.append(("rfx_fx_eq", [x64.ptr(), y.ptr(), B, 65, 2, 1, cf.ptr()], [y], [(5, 1)]))
     x2 = f(B * 2 * T, "x stereo")
-    y2 = _Buf(B * 2 * T, what="y stereo")
+    y2 = Guarded(B * 2 * T, what="y stereo")
     out.append(("rfx_fx_widener", [x2.ptr(), y2.ptr(), B, T, g.ptr(), g.ptr()], [y2], nul((0, 1, 4, 5)) + dims))
-    xv = _Buf(B * T, what="x in place")
+    xv = Guarded(B * T, what="x in place")
     e = i(B * 2, "seg_end", 4)
     g2 = f(B * 2, "db")
     out.append(("rfx_fx_volume", [xv.ptr(), B, T, 2, e.ptr(), g2.ptr(), g2.ptr()], [xv],
                 nul((0, 4, 5, 6)) + [(1, 0), (1, 65536), (2, 0), (3, 0), (3, 65), (3, -1)]))
-    pw = _Buf(B * 8, what="phaser ws")
+    pw = Guarded(B * 8, what="phaser ws")
     out.append(("rfx_fx_phaser", [x.ptr(), y.ptr(), pw.ptr(), B, T, 8000.0, g.ptr(), g.ptr(), g.ptr(), g.ptr(), g.ptr()], [y, pw],
                 nul((0, 1, 2, 6, 7, 8, 9, 10)) + [(3, 0), (3, 65536), (4, 0), (5, 0.0), (5, -1.0)]))
     out.append(("rfx_fx_scale", [x.ptr(), y.ptr(), B, T, g.ptr()], [y], nul((0, 1, 4)) + dims))
     geom = i(B * 2 * 16, "geom", 70)
     c4 = f(B * 2 * 4, "coef")
-    ws = _Buf(B * 2 * T, what="sox ws")
+    ws = Guarded(B * 2 * T, what="sox ws")
     out.append(("rfx_fx_sox_reverb", [x.ptr(), y2.ptr(), ws.ptr(), B, 1, T, geom.ptr(), c4.ptr(), 840], [y2, ws],
                 nul((0, 1, 2, 6, 7)) + [(3, 0), (3, 32768), (5, 0), (4, 0), (4, 3), (8, 11), (8, 40961), (1, x.ptr())]))
     coef = np.zeros(28)
-    hop, lu, ga = _Buf(B * 5, torch.float64, "hop_ws"), _Buf(B, what="lufs"), _Buf(B, what="gain")
+    hop, lu, ga = Guarded(B * 5, torch.float64, "hop_ws"), Guarded(B, what="lufs"), Guarded(B, what="gain")
     # T = 8: chunk 1, hop 2, nhop 4, nblk 1
-    la = [x.ptr(), B, T, 1, 2, 4, 1, 0.125, _host(coef), -32.0, hop.ptr(), lu.ptr(), ga.ptr()]
+    la = [x.ptr(), B, T, 1, 2, 4, 1, 0.125, host(coef), -32.0, hop.ptr(), lu.ptr(), ga.ptr()]
     lbad = [(1, 0), (1, 65536), (2, 0), (3, 0), (4, 0), (5, 3), (6, 0), (6, 2)]
     out.append(("rfx_fx_loudness", la, [hop, lu, ga], nul((0, 8, 10, 11, 12)) + lbad))
-    out.append(("rfx_fx_loudness", [x64.ptr(), B, 65, 1, 2, 4, 1, 0.125, _host(coef), -32.0, hop.ptr(), lu.ptr(), ga.ptr()], [hop, lu, ga], [(3, 1)]))
-    lj = [x.ptr(), 1, 2, T, 1, 2, 4, 1, 0.125, _host(coef), -32.0, hop.ptr(), lu.ptr(), ga.ptr()]
+    out.append(("rfx_fx_loudness", [x64.ptr(), B, 65, 1, 2, 4, 1, 0.125, host(coef), -32.0, hop.ptr(), lu.ptr(), ga.ptr()], [hop, lu, ga], [(3, 1)]))
+    lj = [x.ptr(), 1, 2, T, 1, 2, 4, 1, 0.125, host(coef), -32.0, hop.ptr(), lu.ptr(), ga.ptr()]
     out.append(("rfx_fx_loudness_joint", lj, [hop, lu, ga], nul((0, 9, 11, 12, 13)) + [(1, 0), (2, 0), (1, 65536), (3, 0), (4, 0), (5, 0), (6, 3), (7, 0), (7, 2)]))
-    nw = _Buf((B * 4 * 8 + 2 * B * 4) // 4, what="normalize ws")
+    nw = Guarded((B * 4 * 8 + 2 * B * 4) // 4, what="normalize ws")
     rows = i(B, "rows", 0)
-    na = [x.ptr(), y.ptr(), rows.ptr(), B, T, 1, 2, 4, 1, 0.125, _host(coef), -32.0, nw.ptr()]
+    na = [x.ptr(), y.ptr(), rows.ptr(), B, T, 1, 2, 4, 1, 0.125, host(coef), -32.0, nw.ptr()]
     out.append(("rfx_fx_normalize_rows", na, [y, nw], nul((0, 1, 10, 12)) + [(3, 0), (3, 65536), (4, 0), (5, 0), (6, 0), (7, 3), (8, 0), (8, 2), (1, x.ptr())]))
     return out, (coef,)
 
 
 def test_refusals():
     """every -1 condition of the launch code, one call each: the return value is -1 and the outputs keep their NaN fill"""
-    L, stream = _api()
+    L, _, stream = api()
     table, keep = _refusal_table()
     count = 0
     for entry, args, outs, bad in table:

@@ -7,44 +7,18 @@ import pytest
 import torch
 
 from tests import gemm_ref as R
+from tests.kernel_harness import Arena, guarded, stop_after_a_device_error  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
 
 CASES = R.case_table()
-GUARD = 4096
 ATOMIC = ("gparam", "stat")
-
-
-class Arena:
-    """output buffers: body NaN-filled (or `fill` where the kernel accumulates into it) between two NaN guards of GUARD elements"""
-
-    def __init__(self, dev):
-        self.dev, self.bufs = dev, []
-
-    def alloc(self, shape, dtype, fill=None):
-        n = 1
-        for s in shape:
-            n *= s
-        buf = torch.full((n + 2 * GUARD,), float("nan"), device=self.dev, dtype=dtype)
-        body = buf[GUARD:GUARD + n]
-        if fill is not None:
-            body.fill_(fill)
-        self.bufs.append((buf, n))
-        return body.view(shape)
-
-    def check(self):
-        for buf, n in self.bufs:
-            assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[GUARD + n:]).all()), "guard overwritten"
 
 
 def _run(case, inp, dev):
     arena = Arena(dev)
     with R.case_env(case) as (tf, tw), R.recorder(False) as px:
-        try:
-            out = R.launch(case, inp, dev, arena.alloc)
-            torch.cuda.synchronize()
-        except RuntimeError as e:                      # a launch error or a device fault: nothing more is started on this device
-            pytest.exit(f"{case.id}: {e}", returncode=3)
+        out = guarded(lambda: R.launch(case, inp, dev, arena.alloc), case.id)
         fwd, wg = R.forms_of(case, list(tf), list(tw), px.fwd_rows)
     assert tuple(fwd + wg) == case.form, (case.id, fwd, wg)
     arena.check()

@@ -3,6 +3,7 @@ import pytest
 import torch
 
 from tests.conftest import check, mode, tol
+from tests.hdemucs_pair import pair as _pair
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
@@ -11,21 +12,6 @@ DEV = "cuda:0"
 
 def _rms(a, b):
     return float(((a - b) ** 2).mean().sqrt())
-
-
-def _pair(channels, seed=0):
-    from oracle import ref_hdemucs
-    from remfx_amd.hdemucs import HDemucs
-    torch.manual_seed(seed)
-    ref = ref_hdemucs.HDemucs(sources=["mixture"], audio_channels=1, nfft=4096, channels=channels)
-    # make LayerScale / freq-emb paths numerically visible
-    with torch.no_grad():
-        for n, p in ref.named_parameters():
-            if n.endswith(".scale"):
-                p.fill_(0.3)
-    net = HDemucs(sources=["mixture"], audio_channels=1, nfft=4096, channels=channels)
-    net.load_state_dict(ref.state_dict(), strict=True)
-    return ref, net.to(DEV)
 
 
 def test_hdemucs_small_fwd_bwd(monkeypatch):

@@ -2,47 +2,32 @@
 buffers this test allocates, against tests/loss_ref.py (fp64 and exact rational), per element and per launch form.  The bounds and
 where their constants come from are in loss_ref's docstring and DESIGN.md 4.24; none is measured on a kernel.
 
-Buffers (`_Buf` / `_judge` of tests/test_gpu_fx_kernel.py): every input, output and workspace sits between NaN guards of 4096
+Buffers (`Guarded` / `judge` of tests/kernel_harness.py): every input, output and workspace sits between NaN guards of 4096
 elements, outputs and workspaces are NaN-filled, workspaces are exactly the size rfx_time_sums_ws / rfx_logcosh_ws /
 rfx_stft_scaled_loss_ws return (5 R g doubles for rfx_sisdr_sums), inputs have to come back bit for bit, every case runs twice into
 fresh buffers: the same bits (all of these kernels are order-free).  The padding between strided rows holds 1e30, so a halo read across
 a row end shows in the value.  A failure names the entry point, the forms, the output and the element."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 from tests import loss_ref as X
-from tests.test_gpu_fx_kernel import _Buf, _in, _sync, _twice
-from tests.test_gpu_fx_kernel import _judge as _judge_fx
+from tests.kernel_harness import Guarded, api, judge, report, stop_after_a_device_error, sync, twice  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
 
 KIND = {k: i for i, k in enumerate(X.KINDS)}
 RED = {k: i for i, k in enumerate(X.REDUCTIONS)}
 F64 = torch.float64
-
-
-def _api():
-    from remfx_amd import _lib
-    from remfx_amd.ops import _stream
-    return _lib.lib(), _stream
+_judge = functools.partial(judge, exact="value", equal_inf=True)       # -0 == +0; an infinity the reference has too is a result
 
 
 def _mel(sr, n_fft, n_mels):
     from remfx_amd.losses import mel_filterbank
     return mel_filterbank(sr, n_fft, n_mels).numpy()
-
-
-def _judge(entry, output, got, ref, bound, info=()):
-    """_judge of test_gpu_fx_kernel.py; an infinite or NaN bound would pass any value, so every bound has to be finite"""
-    assert np.isfinite(np.asarray(bound, np.float64)).all(), (entry, output, "a bound is not finite", *info)
-    return _judge_fx(entry, output, got, ref, bound, info)
-
-
-def _report(entry, ratios):
-    print(f"\nLOSS {entry}: largest error / bound " + ", ".join(f"{k} {v:.3f}" for k, v in ratios))
 
 
 def _taps(c):
@@ -55,20 +40,20 @@ def _h(taps):
 
 # ---- row sums ----------------------------------------------------------------------------------------------------------------------------
 def _run_sums(c, entry, data=None):
-    L_, stream = _api()
+    L_, _, stream = api()
     R, L = c["R"], c["L"]
     _, _, (xb, xs), (tb, ts) = data or X.time_data(c)
-    Xb, Tb = _in(xb, "x", c["ox"]), _in(tb, "t", c["ot"])
-    S = _Buf(5 * R, F64, "sums")
+    Xb, Tb = Guarded.of(xb, "x", c["ox"]), Guarded.of(tb, "t", c["ot"])
+    S = Guarded(5 * R, F64, "sums")
     if entry == "rfx_sisdr_sums":
-        W = _Buf(5 * R * X.time_sums_grid(L), F64, "ws")
+        W = Guarded(5 * R * X.time_sums_grid(L), F64, "ws")
         rc = L_.rfx_sisdr_sums(Xb.ptr(), Tb.ptr(), R, L, xs, ts, W.ptr(), S.ptr(), stream())
     else:
         n = int(L_.rfx_time_sums_ws(R, L))
         assert n == 5 * R * X.time_sums_grid(L)
-        W = _Buf(n, F64, "ws")
+        W = Guarded(n, F64, "ws")
         rc = L_.rfx_time_sums(Xb.ptr(), Tb.ptr(), R, L, xs, ts, *_h(_taps(c)), W.ptr(), S.ptr(), stream())
-    _sync(rc, entry, (R, L))
+    sync(rc, entry, (R, L))
     Xb.unchanged(), Tb.unchanged()
     ws = W.np()
     assert np.isfinite(ws).all(), (entry, "a slot of the workspace was not written")
@@ -81,26 +66,26 @@ def test_time_sums(c):
     (rfx_sisdr_sums; rfx_time_sums without taps returns its bits)"""
     data = X.time_data(c)
     x, t = data[0], data[1]
-    a, _ = _twice(lambda: _run_sums(c, "rfx_time_sums", data))
+    a, _ = twice(lambda: _run_sums(c, "rfx_time_sums", data))
     ref, bound = X.row_sums(x, t, _taps(c))
-    r1 = _judge("rfx_time_sums", "sums", a["sums"], ref, bound, sorted(X.forms_time_sums(c)))
+    r1 = _judge(a["sums"], ref, bound, ctx=("rfx_time_sums", "sums", *sorted(X.forms_time_sums(c))))
     plain = dict(c, taps=None)
-    b, _ = _twice(lambda: _run_sums(plain, "rfx_sisdr_sums", data))
+    b, _ = twice(lambda: _run_sums(plain, "rfx_sisdr_sums", data))
     ref, bound = X.row_sums(x, t, None)
-    r2 = _judge("rfx_sisdr_sums", "sums", b["sums"], ref, bound, sorted(X.forms_sisdr_sums(c)))
+    r2 = _judge(b["sums"], ref, bound, ctx=("rfx_sisdr_sums", "sums", *sorted(X.forms_sisdr_sums(c))))
     if c["taps"] is None:
         assert np.array_equal(a["sums"].view(np.uint8), b["sums"].view(np.uint8)), "rfx_time_sums without taps is not rfx_sisdr_sums"
-    _report("sums " + X.case_id(c), [("rfx_time_sums", r1), ("rfx_sisdr_sums", r2)])
+    report("LOSS", "sums " + X.case_id(c), [("rfx_time_sums", r1), ("rfx_sisdr_sums", r2)])
 
 
 # ---- per-row losses, the SI-SDR tail ---------------------------------------------------------------------------------------------------
 def _run_rows(sums, L, kind, zm, red, eps=1e-8, coef=True):
-    L_, stream = _api()
+    L_, _, stream = api()
     R = sums.shape[0]
-    S = _in(sums, "sums")
-    Rw, Cf, O = _Buf(R, what="rows"), _Buf(3 * R, F64, "coef"), _Buf(1, what="out")
+    S = Guarded.of(sums, "sums")
+    Rw, Cf, O = Guarded(R, what="rows"), Guarded(3 * R, F64, "coef"), Guarded(1, what="out")
     rc = L_.rfx_time_loss_rows(S.ptr(), R, L, KIND[kind], zm, eps, RED[red], Rw.ptr(), Cf.ptr() if coef else None, O.ptr(), stream())
-    _sync(rc, "rfx_time_loss_rows", (R, L, kind, zm, red))
+    sync(rc, "rfx_time_loss_rows", (R, L, kind, zm, red))
     S.unchanged()
     out = {"rows": Rw.np()}
     if coef:
@@ -115,9 +100,9 @@ def _run_rows(sums, L, kind, zm, red, eps=1e-8, coef=True):
 
 
 def _run_finish(sums, L, zm, eps=1e-8):
-    L_, stream = _api()
-    S, O = _in(sums, "sums"), _Buf(1, what="out")
-    _sync(L_.rfx_sisdr_finish(S.ptr(), sums.shape[0], L, zm, eps, O.ptr(), stream()), "rfx_sisdr_finish", (sums.shape[0], L))
+    L_, _, stream = api()
+    S, O = Guarded.of(sums, "sums"), Guarded(1, what="out")
+    sync(L_.rfx_sisdr_finish(S.ptr(), sums.shape[0], L, zm, eps, O.ptr(), stream()), "rfx_sisdr_finish", (sums.shape[0], L))
     S.unchanged()
     return {"out": O.np()}
 
@@ -141,27 +126,27 @@ def test_time_loss_rows(c):
             for red in X.REDUCTIONS:
                 info = (kind, zm, red, sorted(X.forms_rows(kind, zm, red, c["R"])))
                 ref = X.reduce_rows(base, red)
-                a, _ = _twice(lambda: _run_rows(sums, c["L"], kind, zm, red))
+                a, _ = twice(lambda: _run_rows(sums, c["L"], kind, zm, red))
                 for k in ("rows", "coef") + (("out",) if red != "none" else ()):
-                    ratios[k] = max(ratios.get(k, 0.0), _judge("rfx_time_loss_rows", k, a[k], ref[k], ref[k + "_bound"], info))
+                    ratios[k] = max(ratios.get(k, 0.0), _judge(a[k], ref[k], ref[k + "_bound"], ctx=("rfx_time_loss_rows", k, *info)))
                 if kind == "sisdr" and red == "mean":
-                    f, _ = _twice(lambda: _run_finish(sums, c["L"], zm))
-                    ratios["finish"] = max(ratios.get("finish", 0.0), _judge("rfx_sisdr_finish", "out", f["out"], ref["out"], ref["out_bound"], info))
+                    f, _ = twice(lambda: _run_finish(sums, c["L"], zm))
+                    ratios["finish"] = max(ratios.get("finish", 0.0), _judge(f["out"], ref["out"], ref["out_bound"], ctx=("rfx_sisdr_finish", "out", *info)))
                     assert np.array_equal(f["out"].view(np.uint8), a["out"].view(np.uint8)), "rfx_sisdr_finish differs from SI-SDR mean"
     b = _run_rows(sums, c["L"], "sisdr", 1 if c["L"] > 1 else 0, "none", coef=False)
     assert np.isfinite(b["rows"]).all()
-    _report("rows " + X.case_id(c), sorted(ratios.items()))
+    report("LOSS", "rows " + X.case_id(c), sorted(ratios.items()))
 
 
 # ---- the gradient pass -------------------------------------------------------------------------------------------------------------------
 def _run_grad(c, coef, gup, data=None):
-    L_, stream = _api()
+    L_, _, stream = api()
     R, L = c["R"], c["L"]
     _, _, (xb, xs), (tb, ts) = data or X.time_data(c)
-    Xb, Tb, Cf, G = _in(xb, "x", c["ox"]), _in(tb, "t", c["ot"]), _in(coef, "coef"), _in(gup, "gup")
-    Y = _Buf(R * L, what="gx", off=c["og"])
+    Xb, Tb, Cf, G = Guarded.of(xb, "x", c["ox"]), Guarded.of(tb, "t", c["ot"]), Guarded.of(coef, "coef"), Guarded.of(gup, "gup")
+    Y = Guarded(R * L, what="gx", off=c["og"])
     rc = L_.rfx_time_loss_grad(Xb.ptr(), Tb.ptr(), R, L, xs, ts, Cf.ptr(), *_h(_taps(c)), G.ptr(), RED[c["red"]], Y.ptr(), stream())
-    _sync(rc, "rfx_time_loss_grad", (R, L))
+    sync(rc, "rfx_time_loss_grad", (R, L))
     for b in (Xb, Tb, Cf, G):
         b.unchanged()
     return {"gx": Y.np((R, L))}
@@ -177,9 +162,9 @@ def test_time_loss_grad(c):
     sums, _ = X.row_sums(x, t, _taps(c))
     coef = X.time_loss_rows(sums, c["L"], c["kind"], c["zm"] if c["L"] > 1 else 0, 1e-8, "none")["coef"]
     gup = X.gup_of(c)
-    a, _ = _twice(lambda: _run_grad(c, coef, gup, data))
+    a, _ = twice(lambda: _run_grad(c, coef, gup, data))
     ref, bound = X.time_loss_grad(x, t, coef, _taps(c), gup, c["red"])
-    _report("grad " + X.case_id(c), [("gx", _judge("rfx_time_loss_grad", "gx", a["gx"], ref, bound, sorted(X.forms_time_grad(c))))])
+    report("LOSS", "grad " + X.case_id(c), [("gx", _judge(a["gx"], ref, bound, ctx=("rfx_time_loss_grad", "gx", *sorted(X.forms_time_grad(c)))))])
 
 
 CHAIN = X.TIME_CASES[10]
@@ -194,30 +179,30 @@ def test_time_chain(kind):
     x, t = data[0], data[1]
     s = _run_sums(c, "rfx_time_sums", data)["sums"]
     sref, sb = X.row_sums(x, t, _taps(c))
-    _judge("chain", "sums", s, sref, sb, (kind,))
+    _judge(s, sref, sb, ctx=("chain", "sums", kind))
     r = _run_rows(s, c["L"], kind, c["zm"], c["red"])
     ref = X.time_loss_rows(sref, c["L"], kind, c["zm"], 1e-8, c["red"], sums_err=sb)
-    ratios = [(k, _judge("chain", k, r[k], ref[k], ref[k + "_bound"], (kind,))) for k in ("rows", "coef", "out")]
+    ratios = [(k, _judge(r[k], ref[k], ref[k + "_bound"], ctx=("chain", k, kind))) for k in ("rows", "coef", "out")]
     gup = X.gup_of(c)
     g = _run_grad(c, r["coef"], gup, data)["gx"]
     gref, gb = X.time_loss_grad(x, t, ref["coef"], _taps(c), gup, c["red"], coef_err=ref["coef_bound"])
-    ratios.append(("gx", _judge("chain", "gx", g, gref, gb, (kind,))))
-    _report("chain " + kind, ratios)
+    ratios.append(("gx", _judge(g, gref, gb, ctx=("chain", "gx", kind))))
+    report("LOSS", "chain " + kind, ratios)
 
 
 # ---- log-cosh ------------------------------------------------------------------------------------------------------------------------------
 def _run_logcosh(c, x, t, gup):
-    L_, stream = _api()
+    L_, _, stream = api()
     R, L = c["R"], c["L"]
     xs = L + c.get("xpad", 0)
     xb = np.full(R * xs, 1.0e30, np.float32)
     xb.reshape(R, xs)[:, :L] = x
-    Xb, Tb, G = _in(xb, "x"), _in(t, "t"), _in(gup, "gup")
+    Xb, Tb, G = Guarded.of(xb, "x"), Guarded.of(t, "t"), Guarded.of(gup, "gup")
     n = int(L_.rfx_logcosh_ws(R, L))
     assert n == R * X.time_sums_grid(L)
-    W, S, Y = _Buf(n, F64, "ws"), _Buf(R, F64, "sums"), _Buf(R * L, what="gx")
-    _sync(L_.rfx_logcosh_rows(Xb.ptr(), Tb.ptr(), R, L, xs, L, c["a"], 1e-8, W.ptr(), S.ptr(), stream()), "rfx_logcosh_rows", (R, L))
-    _sync(L_.rfx_logcosh_grad(Xb.ptr(), Tb.ptr(), R, L, xs, L, c["a"], 1e-8, G.ptr(), RED[c["red"]], Y.ptr(), stream()), "rfx_logcosh_grad", (R, L))
+    W, S, Y = Guarded(n, F64, "ws"), Guarded(R, F64, "sums"), Guarded(R * L, what="gx")
+    sync(L_.rfx_logcosh_rows(Xb.ptr(), Tb.ptr(), R, L, xs, L, c["a"], 1e-8, W.ptr(), S.ptr(), stream()), "rfx_logcosh_rows", (R, L))
+    sync(L_.rfx_logcosh_grad(Xb.ptr(), Tb.ptr(), R, L, xs, L, c["a"], 1e-8, G.ptr(), RED[c["red"]], Y.ptr(), stream()), "rfx_logcosh_grad", (R, L))
     for b in (Xb, Tb, G):
         b.unchanged()
     assert np.isfinite(W.np()).all()
@@ -230,31 +215,31 @@ def test_logcosh(c):
     exactly 0), negative z; then rfx_time_loss_rows(kind LOGCOSH) on the device's sums: rows = sums / L, coef zeros, the reduction"""
     x, t = X.logcosh_data(c)
     gup = (0.5 + np.arange(c["R"] if c["red"] == "none" else 1) % 5 * 0.25).astype(np.float32)
-    a, _ = _twice(lambda: _run_logcosh(c, x, t, gup))
+    a, _ = twice(lambda: _run_logcosh(c, x, t, gup))
     forms = sorted(X.forms_logcosh(c))
     ref, bound = X.logcosh_rows(x, t, c["a"])
-    r1 = _judge("rfx_logcosh_rows", "sums", a["sums"], ref, bound, forms)
+    r1 = _judge(a["sums"], ref, bound, ctx=("rfx_logcosh_rows", "sums", *forms))
     gref, gb = X.logcosh_grad(x, t, c["a"], 1e-8, gup, c["red"])
-    r2 = _judge("rfx_logcosh_grad", "gx", a["gx"], gref, gb, forms)
+    r2 = _judge(a["gx"], gref, gb, ctx=("rfx_logcosh_grad", "gx", *forms))
     rows = _run_rows(a["sums"], c["L"], "logcosh", 0, c["red"])
     rr = X.time_loss_rows(ref, c["L"], "logcosh", 0, 1e-8, c["red"], sums_err=bound)
-    r3 = _judge("rfx_time_loss_rows", "rows", rows["rows"], rr["rows"], rr["rows_bound"], forms)
+    r3 = _judge(rows["rows"], rr["rows"], rr["rows_bound"], ctx=("rfx_time_loss_rows", "rows", *forms))
     assert np.array_equal(rows["coef"], np.zeros((c["R"], 3))), "coef of LOGCOSH is zeros"
     if c["red"] != "none":
-        _judge("rfx_time_loss_rows", "out", rows["out"], rr["out"], rr["out_bound"], forms)
-    _report(f"logcosh R{c['R']}-L{c['L']}", [("sums", r1), ("gx", r2), ("rows", r3)])
+        _judge(rows["out"], rr["out"], rr["out_bound"], ctx=("rfx_time_loss_rows", "out", *forms))
+    report("LOSS", f"logcosh R{c['R']}-L{c['L']}", [("sums", r1), ("gx", r2), ("rows", r3)])
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------------
 def test_time_refusals():
     """every -1 condition returns -1 with nothing written: NULL arguments, R / L <= 0, R = 65536 (one grid row per signal row), a bad
     kind or reduction, out == NULL with a reducing reduction, a <= 0 and NaN, pointers off 4-byte alignment"""
-    L_, stream = _api()
+    L_, _, stream = api()
     R, L = 2, 8
-    x, t = _in(np.ones(R * L, np.float32), "x"), _in(np.ones(R * L, np.float32), "t")
-    ws, sums, coef = _Buf(5 * R, F64, "ws"), _Buf(5 * R, F64, "sums"), _Buf(3 * R, F64, "coef")
-    rows, out, gx, gup = _Buf(R, what="rows"), _Buf(1, what="out"), _Buf(R * L, what="gx"), _in(np.ones(R, np.float32), "gup")
-    sin, cin = _in(np.ones(5 * R), "sums in"), _in(np.ones(3 * R), "coef in")
+    x, t = Guarded.of(np.ones(R * L, np.float32), "x"), Guarded.of(np.ones(R * L, np.float32), "t")
+    ws, sums, coef = Guarded(5 * R, F64, "ws"), Guarded(5 * R, F64, "sums"), Guarded(3 * R, F64, "coef")
+    rows, out, gx, gup = Guarded(R, what="rows"), Guarded(1, what="out"), Guarded(R * L, what="gx"), Guarded.of(np.ones(R, np.float32), "gup")
+    sin, cin = Guarded.of(np.ones(5 * R), "sums in"), Guarded.of(np.ones(3 * R), "coef in")
     s = stream()
     P = lambda b: b.ptr()
     nan = float("nan")
@@ -312,10 +297,10 @@ def test_time_refusals():
 
 def test_stft_loss_row_limit():
     """the three STFT-loss cell wrappers (their values are pinned by test_gpu_fft_kernel.py) refuse R = 65536 too, with nothing written"""
-    L_, stream = _api()
+    L_, _, stream = api()
     s = stream()
-    x, m, sums = _in(np.ones(16, np.float32), "spectrum"), _in(np.ones(8, np.float32), "ymag"), _in(np.ones(3, np.float32), "sums in")
-    W, S, G = _Buf(3, F64, "ws"), _Buf(3, what="sums"), _Buf(16, what="gxc")
+    x, m, sums = Guarded.of(np.ones(16, np.float32), "spectrum"), Guarded.of(np.ones(8, np.float32), "ymag"), Guarded.of(np.ones(3, np.float32), "sums in")
+    W, S, G = Guarded(3, F64, "ws"), Guarded(3, what="sums"), Guarded(16, what="gxc")
     eps = float(X.EPS_F)
     assert L_.rfx_stft_loss_reduce(x.ptr(), x.ptr(), 65536, 8, eps, W.ptr(), S.ptr(), s) == -1
     assert L_.rfx_stft_loss_grad(x.ptr(), x.ptr(), 65536, 8, eps, sums.ptr(), 1.0, 1.0, None, G.ptr(), s) == -1
@@ -327,16 +312,16 @@ def test_stft_loss_row_limit():
 
 # ---- combines ------------------------------------------------------------------------------------------------------------------------------
 def _run_combine(sums, n, R, pe, w=None):
-    L_, stream = _api()
-    bufs = [_in(s, f"sums[{k}]") for k, s in enumerate(sums)]
-    O = _Buf(1, what="out")
+    L_, _, stream = api()
+    bufs = [Guarded.of(s, f"sums[{k}]") for k, s in enumerate(sums)]
+    O = Guarded(1, what="out")
     ptrs = (C.c_void_p * len(bufs))(*[b.t.data_ptr() for b in bufs])
     nn = (C.c_int64 * len(n))(*n)
     if w is None:
         rc = L_.rfx_mrstft_combine(ptrs, nn, len(bufs), R, pe, O.ptr(), stream())
     else:
         rc = L_.rfx_mrstft_combine_w(ptrs, nn, len(bufs), R, pe, w[0], w[1], w[2], O.ptr(), stream())
-    _sync(rc, "rfx_mrstft_combine" + ("_w" if w else ""), (len(bufs), R))
+    sync(rc, "rfx_mrstft_combine" + ("_w" if w else ""), (len(bufs), R))
     for b in bufs:
         b.unchanged()
     return {"out": O.np()}
@@ -349,14 +334,14 @@ def test_combines(c):
     ratios = []
     s3, n = X.combine_data(c, 3)
     s3 = [s.astype(np.float32) for s in s3]
-    a, _ = _twice(lambda: _run_combine(s3, n, c["R"], c["pe"]))
+    a, _ = twice(lambda: _run_combine(s3, n, c["R"], c["pe"]))
     ref, bound = X.mrstft_combine(s3, n, c["pe"])
-    ratios.append(("combine", _judge("rfx_mrstft_combine", "out", a["out"], ref, bound, sorted(X.forms_combine(c)))))
+    ratios.append(("combine", _judge(a["out"], ref, bound, ctx=("rfx_mrstft_combine", "out", *sorted(X.forms_combine(c))))))
     s4, n = X.combine_data(c, 4)
     for w in X.COMBINE_WEIGHTS:
-        a, _ = _twice(lambda: _run_combine(s4, n, c["R"], c["pe"], w))
+        a, _ = twice(lambda: _run_combine(s4, n, c["R"], c["pe"], w))
         ref, bound = X.mrstft_combine_w(s4, n, c["pe"], w)
-        ratios.append((f"w{w}", _judge("rfx_mrstft_combine_w", "out", a["out"], ref, bound, sorted(X.forms_combine(c, w)))))
+        ratios.append((f"w{w}", _judge(a["out"], ref, bound, ctx=("rfx_mrstft_combine_w", "out", *sorted(X.forms_combine(c, w))))))
         poisoned = [s.copy() for s in s4]
         for s in poisoned:
             if w[0] == 0.0:
@@ -367,15 +352,15 @@ def test_combines(c):
                 s[:, 3] = np.nan
         b = _run_combine(poisoned, n, c["R"], c["pe"], w)
         assert np.array_equal(a["out"].view(np.uint8), b["out"].view(np.uint8)), ("a term with weight 0 was evaluated", w)
-    _report(f"combines nres{c['nres']}-R{c['R']}", ratios)
+    report("LOSS", f"combines nres{c['nres']}-R{c['R']}", ratios)
 
 
 def test_combine_refusals():
     """nres 0 and 9, R <= 0, n[k] <= 0, a NULL sums[k], NULL arguments: -1 and out untouched"""
-    L_, stream = _api()
+    L_, _, stream = api()
     R = 3
-    f32, f64 = _in(np.ones(3 * R, np.float32), "sums"), _in(np.ones(4 * R), "sums")
-    O = _Buf(1, what="out")
+    f32, f64 = Guarded.of(np.ones(3 * R, np.float32), "sums"), Guarded.of(np.ones(4 * R), "sums")
+    O = Guarded(1, what="out")
     s = stream()
     count = 0
     for fn, buf, extra in ((L_.rfx_mrstft_combine, f32, ()), (L_.rfx_mrstft_combine_w, f64, (1.0, 1.0, 1.0))):
@@ -398,27 +383,27 @@ def test_combine_refusals():
 # ---- the scaled family ---------------------------------------------------------------------------------------------------------------------
 def _run_scaled(c, x, y, fb, mx_in=None, my_in=None, sums_in=None):
     """forward, and the gradient given mx_in / my_in / sums_in when the case stores"""
-    L_, stream = _api()
+    L_, _, stream = api()
     R, frames, bins = c["R"], c["frames"], c["bins"]
     n_out = bins if fb is None else fb.shape[0]
-    Xb, Yb = _in(x, "xc"), _in(y, "yc")
+    Xb, Yb = Guarded.of(x, "xc"), Guarded.of(y, "yc")
     ins = [Xb, Yb]
     idx = w = tidx = tw = None
     n_w = 0
     if fb is not None:
         i, wv = X.pack(fb)
         ti, twv = X.pack(fb.T)
-        idx, w, tidx, tw = _in(i, "fb_idx"), _in(wv, "fb_w"), _in(ti, "fbt_idx"), _in(twv, "fbt_w")
+        idx, w, tidx, tw = Guarded.of(i, "fb_idx"), Guarded.of(wv, "fb_w"), Guarded.of(ti, "fbt_idx"), Guarded.of(twv, "fbt_w")
         n_w = wv.size
         ins += [idx, w, tidx, tw]
     n = int(L_.rfx_stft_scaled_loss_ws(R, frames))
     assert n == 4 * R * X.scaled_grid(frames)
-    W, S = _Buf(n, F64, "ws"), _Buf(4 * R, F64, "sums")
-    MX, MY = _Buf(R * frames * n_out, what="mx"), _Buf(R * frames * n_out, what="my")
+    W, S = Guarded(n, F64, "ws"), Guarded(4 * R, F64, "sums")
+    MX, MY = Guarded(R * frames * n_out, what="mx"), Guarded(R * frames * n_out, what="my")
     p = lambda b: b.ptr() if b is not None else None
     rc = L_.rfx_stft_scaled_loss(Xb.ptr(), Yb.ptr(), R, frames, bins, p(idx), p(w), n_out, n_w, float(X.EPS_F), W.ptr(), S.ptr(),
                                  MX.ptr() if c["store"] else None, MY.ptr() if c["store"] else None, stream())
-    _sync(rc, "rfx_stft_scaled_loss", (R, frames, bins, n_out))
+    sync(rc, "rfx_stft_scaled_loss", (R, frames, bins, n_out))
     ws = W.np()
     out = {"sums": S.np((R, 4))}
     assert np.isfinite(np.delete(ws.reshape(-1, 4), 2, 1)).all(), "a slot of the workspace was not written"
@@ -427,13 +412,13 @@ def _run_scaled(c, x, y, fb, mx_in=None, my_in=None, sums_in=None):
     else:
         MX.untouched(), MY.untouched()
     if mx_in is not None:
-        A, B, Sin = _in(mx_in, "mx in"), _in(my_in, "my in"), _in(sums_in, "sums in")
-        U = _in(np.array([0.75], np.float32), "gup") if c["gup"] else None
-        G = _Buf(x.size, what="gxc")
+        A, B, Sin = Guarded.of(mx_in, "mx in"), Guarded.of(my_in, "my in"), Guarded.of(sums_in, "sums in")
+        U = Guarded.of(np.array([0.75], np.float32), "gup") if c["gup"] else None
+        G = Guarded(x.size, what="gxc")
         wsc, wlm, wlin = c["w"]
         rc = L_.rfx_stft_scaled_loss_grad(Xb.ptr(), A.ptr(), B.ptr(), R, frames, bins, p(tidx), p(tw), n_out, float(X.EPS_F), Sin.ptr(), c["pe"],
                                           wsc, wlm, wlin, p(U), G.ptr(), stream())
-        _sync(rc, "rfx_stft_scaled_loss_grad", (R, frames, bins, n_out))
+        sync(rc, "rfx_stft_scaled_loss_grad", (R, frames, bins, n_out))
         ins += [A, B, Sin] + ([U] if U is not None else [])
         out["gxc"] = G.np(x.shape)
     for b in ins:
@@ -452,15 +437,15 @@ def test_scaled(c):
     f = X.stft_scaled_loss(x, y, fb, adds=X.scaled_adds(c, n_out))
     mx_in, my_in = f["mx"].astype(np.float32), f["my"].astype(np.float32)
     args = (mx_in, my_in, f["sums"]) if c["store"] else ()
-    a, _ = _twice(lambda: _run_scaled(c, x, y, fb, *args))
+    a, _ = twice(lambda: _run_scaled(c, x, y, fb, *args))
     forms = sorted(X.forms_scaled(c, fb))
-    ratios = [("sums", _judge("rfx_stft_scaled_loss", "sums", a["sums"], f["sums"], f["sums_bound"], forms))]
+    ratios = [("sums", _judge(a["sums"], f["sums"], f["sums_bound"], ctx=("rfx_stft_scaled_loss", "sums", *forms)))]
     if c["store"]:
-        ratios += [(k, _judge("rfx_stft_scaled_loss", k, a[k], f[k], f[k + "_bound"], forms)) for k in ("mx", "my")]
+        ratios += [(k, _judge(a[k], f[k], f[k + "_bound"], ctx=("rfx_stft_scaled_loss", k, *forms))) for k in ("mx", "my")]
         ref, bound = X.stft_scaled_loss_grad(x, mx_in, my_in, f["sums"], fb, c["w"], c["pe"], 0.75 if c["gup"] else None)
-        ratios.append(("gxc", _judge("rfx_stft_scaled_loss_grad", "gxc", a["gxc"], ref, bound, forms)))
+        ratios.append(("gxc", _judge(a["gxc"], ref, bound, ctx=("rfx_stft_scaled_loss_grad", "gxc", *forms))))
         assert not a["gxc"][0, 0, 0].any() and not a["gxc"][0, 0, 1].any() and a["gxc"][0, 0, 2].any() == ref[0, 0, 2].any(), "px below / at / above eps"
-    _report("scaled " + X.scaled_id(c), ratios)
+    report("LOSS", "scaled " + X.scaled_id(c), ratios)
 
 
 def test_scaled_empty_band():
@@ -474,25 +459,25 @@ def test_scaled_empty_band():
     f = X.stft_scaled_loss(x, y, fb, adds=X.scaled_adds(c, fb.shape[0]))
     assert not np.isfinite(f["sums"][:, 2]).any()
     mx_in, my_in = f["mx"].astype(np.float32), f["my"].astype(np.float32)
-    a, _ = _twice(lambda: _run_scaled(c, x, y, fb, mx_in, my_in, f["sums"]))
+    a, _ = twice(lambda: _run_scaled(c, x, y, fb, mx_in, my_in, f["sums"]))
     assert not np.isfinite(a["sums"][:, 2]).any()
     keep = [0, 1, 3]
-    r = _judge("rfx_stft_scaled_loss", "sums", a["sums"][:, keep], f["sums"][:, keep], f["sums_bound"][:, keep], ("empty band",))
+    r = _judge(a["sums"][:, keep], f["sums"][:, keep], f["sums_bound"][:, keep], ctx=("rfx_stft_scaled_loss", "sums", "empty band"))
     for k in ("mx", "my"):
-        _judge("rfx_stft_scaled_loss", k, a[k], f[k], f[k + "_bound"], ("empty band",))
+        _judge(a[k], f[k], f[k + "_bound"], ctx=("rfx_stft_scaled_loss", k, "empty band"))
     ref, bound = X.stft_scaled_loss_grad(x, mx_in, my_in, f["sums"], fb, c["w"], c["pe"], 0.75)
     fin = np.isfinite(ref)
     assert fin.any() and (~fin).any()
     assert np.isfinite(a["gxc"][fin]).all() and not np.isfinite(a["gxc"][~fin & (np.abs(x) > 0) & (X.px32(x) > X.EPS_F)[..., None]]).any()
-    r2 = _judge("rfx_stft_scaled_loss_grad", "gxc", a["gxc"][fin], ref[fin], bound[fin], ("empty band",))
-    _report("scaled empty band", [("sums", r), ("gxc", r2)])
+    r2 = _judge(a["gxc"][fin], ref[fin], bound[fin], ctx=("rfx_stft_scaled_loss_grad", "gxc", "empty band"))
+    report("LOSS", "scaled empty band", [("sums", r), ("gxc", r2)])
 
 
 def test_scaled_lds_limits_and_refusals():
     """forward at exactly 65536 bytes of LDS (bins 8191, n_w 2: runs) and at 65540 (bins 8192, n_w 1: -1); the gradient's identity at
     n_out = bins = 16385 (65540 bytes: the raised dynamic-LDS limit, runs) and at n_out = 40961 (163844 bytes: -1); R = 65536, NULL
     arguments, mx without my, n_out != bins for the identity: -1 with nothing written"""
-    L_, stream = _api()
+    L_, _, stream = api()
     s = stream()
     eps = float(X.EPS_F)
     c = X._s(1, 1, 8191, ("hand", 1, (2,)))
@@ -500,12 +485,12 @@ def test_scaled_lds_limits_and_refusals():
     fb[0, 8189:] = (0.5, 0.25)
     x, y = X.scaled_data(c)
     f = X.stft_scaled_loss(x, y, fb, adds=X.scaled_adds(c, 1))
-    a, _ = _twice(lambda: _run_scaled(c, x, y, fb))
-    r = [(k, _judge("rfx_stft_scaled_loss", k, a[k], f[k], f[k + "_bound"], ("lds 65536",))) for k in ("sums", "mx", "my")]
+    a, _ = twice(lambda: _run_scaled(c, x, y, fb))
+    r = [(k, _judge(a[k], f[k], f[k + "_bound"], ctx=("rfx_stft_scaled_loss", k, "lds 65536"))) for k in ("sums", "mx", "my")]
     # 65540 bytes: refused
-    big = _in(np.zeros(2 * 8192 * 2, np.float32), "spectra")
-    idx, w = _in(np.array([[0, 1, 0]], np.int32), "idx"), _in(np.ones(1, np.float32), "w")
-    W, S, MX, MY = _Buf(4, F64, "ws"), _Buf(4, F64, "sums"), _Buf(8, what="mx"), _Buf(8, what="my")
+    big = Guarded.of(np.zeros(2 * 8192 * 2, np.float32), "spectra")
+    idx, w = Guarded.of(np.array([[0, 1, 0]], np.int32), "idx"), Guarded.of(np.ones(1, np.float32), "w")
+    W, S, MX, MY = Guarded(4, F64, "ws"), Guarded(4, F64, "sums"), Guarded(8, what="mx"), Guarded(8, what="my")
     P = lambda b: b.ptr()
     calls = [lambda: L_.rfx_stft_scaled_loss(P(big), P(big), 1, 1, 8192, P(idx), P(w), 1, 1, eps, P(W), P(S), None, None, s),
              lambda: L_.rfx_stft_scaled_loss(P(big), P(big), 65536, 1, 2, None, None, 2, 0, eps, P(W), P(S), None, None, s),
@@ -520,7 +505,7 @@ def test_scaled_lds_limits_and_refusals():
              lambda: L_.rfx_stft_scaled_loss(P(big), P(big), 0, 1, 2, None, None, 2, 0, eps, P(W), P(S), None, None, s),
              lambda: L_.rfx_stft_scaled_loss(P(big), P(big), 1, 0, 2, None, None, 2, 0, eps, P(W), P(S), None, None, s),
              lambda: L_.rfx_stft_scaled_loss(P(big), P(big), 1, 1, 0, None, None, 0, 0, eps, P(W), P(S), None, None, s)]
-    G, Sin = _Buf(8, what="gxc"), _in(np.ones(4), "sums in")
+    G, Sin = Guarded(8, what="gxc"), Guarded.of(np.ones(4), "sums in")
     calls += [lambda: L_.rfx_stft_scaled_loss_grad(P(big), P(big), P(big), 1, 1, 40961, None, None, 40961, eps, P(Sin), 1, 1.0, 1.0, 0.0, None, P(G), s),
               lambda: L_.rfx_stft_scaled_loss_grad(P(big), P(big), P(big), 65536, 1, 2, None, None, 2, eps, P(Sin), 1, 1.0, 1.0, 0.0, None, P(G), s),
               lambda: L_.rfx_stft_scaled_loss_grad(P(big), P(big), P(big), 1, 1, 2, None, None, 3, eps, P(Sin), 1, 1.0, 1.0, 0.0, None, P(G), s),
@@ -545,7 +530,7 @@ def test_scaled_lds_limits_and_refusals():
     x, y = X.scaled_data(cg)
     f = X.stft_scaled_loss(x, y, None, adds=X.scaled_adds(cg, 16385))
     mx_in, my_in = f["mx"].astype(np.float32), f["my"].astype(np.float32)
-    a, _ = _twice(lambda: _run_scaled(cg, x, y, None, mx_in, my_in, f["sums"]))
+    a, _ = twice(lambda: _run_scaled(cg, x, y, None, mx_in, my_in, f["sums"]))
     ref, bound = X.stft_scaled_loss_grad(x, mx_in, my_in, f["sums"], None, cg["w"], 1, None)
-    r.append(("gxc 16385", _judge("rfx_stft_scaled_loss_grad", "gxc", a["gxc"], ref, bound, ("dynamic lds attribute",))))
-    _report(f"scaled lds limits ({len(calls)} refusals)", r)
+    r.append(("gxc 16385", _judge(a["gxc"], ref, bound, ctx=("rfx_stft_scaled_loss_grad", "gxc", "dynamic lds attribute"))))
+    report("LOSS", f"scaled lds limits ({len(calls)} refusals)", r)

@@ -15,12 +15,12 @@ import torch
 
 from tests import lstm_ref as R
 from tests.conftest import check
+from tests.kernel_harness import Guarded, stop_after_a_device_error  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F32, BF16X3, BF16 = 0, 1, 2
 MODE = {BF16X3: "bf16x3", BF16: "bf16"}
-GUARD = 4096                                                   # floats of NaN on both sides of every output
 CLUSTER = (0, 0)                                               # rfx_lstm_set_local: never the single-workgroup form
 
 # (H, T, Bn, pin) -- pin = None: the form as shipped
@@ -98,17 +98,6 @@ class _Pin:
         _lib.lib().rfx_lstm_set_local(-1, -1)
 
 
-def _guarded(n):
-    buf = torch.full((n + 2 * GUARD,), float("nan"), device="cuda", dtype=torch.float32)
-    return buf, buf[GUARD:GUARD + n]
-
-
-def _owned(buf, what):
-    """every addressed element written with a finite value, nothing outside touched"""
-    assert bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all()), f"{what}: guard overwritten"
-    assert bool(torch.isfinite(buf[GUARD:-GUARD]).all()), f"{what}: element not written or not finite"
-
-
 def launch(H, T, Bn, prec, inputs, pin=None, save=True, sweep_back=True):
     """one forward (and backward) sweep on the current stream; returns CPU tensors"""
     from remfx_amd import _lib, lstm
@@ -131,21 +120,22 @@ def launch(H, T, Bn, prec, inputs, pin=None, save=True, sweep_back=True):
         f, b = forms(H, prec, Bn, pin)
         assert L.rfx_lstm_local(H, Bn, prec, 0) == int(f[0].startswith("fwd_local"))     # the mirror of the dispatch holds
         assert L.rfx_lstm_local(H, Bn, prec, 1) == int(b[0].startswith("bwd_local"))
-        ob, out = _guarded(2 * H * P)
-        gb, gates = _guarded(8 * H * P) if save else (None, None)
-        cb, cst = _guarded(2 * H * P) if save else (None, None)
+        ob = Guarded(2 * H * P, what="out")
+        gb, cb = (Guarded(8 * H * P, what="gates"), Guarded(2 * H * P, what="cstate")) if save else (None, None)
+        out, gates, cst = ob.t, (gb.t if save else None), (cb.t if save else None)
         rc(L.rfx_lstm_fwd(_ptr(xp), _ptr(pack), T, Bn, H, _ptr(out), _ptr(gates), _ptr(cst), _ptr(ws), prec, _stream()), "rfx_lstm_fwd")
-        _owned(ob, "out")
+        ob.owned()
         res["out"] = out.cpu().view(2 * H, P)
         if save:
-            _owned(gb, "gates")
-            _owned(cb, "cstate")
+            gb.owned()
+            cb.owned()
             res["gates"], res["cstate"] = gates.cpu().view(2, 4 * H, P), cst.cpu().view(2, H, P)
             if sweep_back:
-                db, dG = _guarded(8 * H * P)
+                db = Guarded(8 * H * P, what="dG")
+                dG = db.t
                 rc(L.rfx_lstm_bwd(_ptr(gout), _ptr(pack), _ptr(gates), _ptr(cst), T, Bn, H, _ptr(dG), _ptr(ws), prec, _stream()),
                    "rfx_lstm_bwd")
-                _owned(db, "dG")
+                db.owned()
                 res["dG"] = dG.cpu().view(2, 4 * H, P)
     return res
 

@@ -20,41 +20,18 @@ import pytest
 import torch
 
 from tests import norm_ref as R
+from tests.kernel_harness import Guarded, stop_after_a_device_error, where  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]          # no GEMM inside: the arithmetic modes agree
 
-GUARD = 4096
 EPS = R.GEN_EPS
 TABLE = R.case_table()
-_FILL = {torch.float32: (torch.int32, 0x7FC00000), torch.bfloat16: (torch.int16, 0x7FC0), torch.float64: (torch.int64, 0x7FF8000000000000)}
-
-
 def _group(name):
     return [c for c in TABLE if c.group == name]
 
 
 def _id(c):
     return c.id
-
-
-class _Buf:
-    """n elements of NaN with a NaN guard behind and (outputs) in front"""
-
-    def __init__(self, n, dtype=torch.float32, front=True, what=""):
-        self.lo, self.what = (GUARD if front else 0), what
-        self.buf = torch.full((self.lo + n + GUARD,), float("nan"), device="cuda", dtype=dtype)
-        self.t = self.buf[self.lo:self.lo + n]
-
-    def guards_intact(self):
-        it, pat = _FILL[self.buf.dtype]
-        bits = self.buf.view(it)
-        assert bool((bits[:self.lo] == pat).all()) and bool((bits[self.lo + self.t.numel():] == pat).all()), f"{self.what}: guard overwritten"
-
-    def owned(self):
-        """every element written with a finite value, nothing outside touched"""
-        self.guards_intact()
-        bad = ~torch.isfinite(self.t.float())
-        assert not bool(bad.any()), f"{self.what}: element {int(bad.nonzero()[0])} of {self.t.numel()} not written or not finite"
 
 
 def _split_sums(s1, s2, k, gen):
@@ -84,29 +61,29 @@ def launch(case, inp):
     res, gy = batch(inp["res"]), batch(inp["gy"])
     scale = None if inp["scale"] is None else inp["scale"].to(dev)
     nstat = C if bn else N * G
-    y = _Buf(N * Co * S, what="y")
+    y = Guarded(N * Co * S, what="y")
     bufs = [y]
     sums = None
     if case.eval:
         g = torch.Generator().manual_seed(C)
         mean_t, rstd_t = torch.randn(C, generator=g).to(dev), torch.rsqrt(torch.rand(C, generator=g) + 0.5).to(dev)
     else:
-        mean, rstd = _Buf(nstat, what="mean"), _Buf(nstat, what="rstd")
+        mean, rstd = Guarded(nstat, what="mean"), Guarded(nstat, what="rstd")
         mean_t, rstd_t = mean.t, rstd.t
         bufs += [mean, rstd]
         if bn:
             slots = L.rfx_batchnorm_stat_slots(N, S)
             assert slots == R.bn_stat_slots(N, S)
-            sums = _Buf(2 * C * slots, torch.float64, front=False, what="sums")
+            sums = Guarded(2 * C * slots, torch.float64, front=False, what="sums")
         elif case.given == -1:
             chunks = L.rfx_groupnorm_stat_chunks(C, S, G)
             assert chunks == R.stat_chunks(C, S, G)
-            sums = _Buf(2 * N * G * chunks, torch.float64, front=False, what="sums")
+            sums = Guarded(2 * N * G * chunks, torch.float64, front=False, what="sums")
         elif case.given == 0:
-            sums = _Buf(2 * N * G, torch.float64, front=False, what="sums")
+            sums = Guarded(2 * N * G, torch.float64, front=False, what="sums")
         else:                                                  # an INPUT: what a GEMM epilogue would have left, (NG, 2) or (NG, k, 2)
             s1, s2, _ = R.moments(inp["x"], case.kind, G)
-            sums = _Buf(2 * N * G * case.given, torch.float64, front=False, what="sums")
+            sums = Guarded(2 * N * G * case.given, torch.float64, front=False, what="sums")
             sums.t.copy_(_split_sums(s1, s2, case.given, torch.Generator().manual_seed(case.given)).reshape(-1))
     sp = _ptr(sums.t) if sums is not None else None
     if bn:
@@ -126,13 +103,13 @@ def launch(case, inp):
     if case.bwd:
         nw = L.rfx_norm_bwd_work_floats(N, C, S, 0 if bn else G)
         assert nw == R.work_floats(N, C, S, 0 if bn else G)
-        work = _Buf(nw, front=False, what="work")
-        dx = _Buf(N * C * S, torch.bfloat16 if case.x16 else torch.float32, what="dx")
-        dgamma, dbeta = _Buf(C, what="dgamma"), _Buf(C, what="dbeta")
+        work = Guarded(nw, front=False, what="work")
+        dx = Guarded(N * C * S, torch.bfloat16 if case.x16 else torch.float32, what="dx")
+        dgamma, dbeta = Guarded(C, what="dgamma"), Guarded(C, what="dbeta")
         outs = [dx, dgamma, dbeta]
         dscale = None
         if case.mode == "glu_scale_res":
-            dscale = _Buf(Co, what="dscale")
+            dscale = Guarded(Co, what="dscale")
             outs.append(dscale)
         if bn:
             rc = L.rfx_batchnorm_bwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean_t), _ptr(rstd_t), _ptr(gy), N, C, S, mode, _ptr(work.t),
@@ -162,14 +139,6 @@ def _pool_stat(v, idx, P):
     return p.reshape(-1)
 
 
-def _where(i, shape):
-    out = []
-    for d in reversed(shape):
-        out.append(i % d)
-        i //= d
-    return tuple(reversed(out))
-
-
 def judge_statistics(case, inp, got):
     x, idx = inp["x"], inp["idx"]
     mk, rk = (_pool_stat(got[k], idx, x.shape[0]).double() for k in ("mean", "rstd"))
@@ -177,7 +146,7 @@ def judge_statistics(case, inp, got):
         # the sums were handed over: fp64 finalize, then ONE rounding to fp32
         m, r = R.finalize(*R.moments(x, case.kind, case.G), EPS)
         for name, k, ref in (("mean", mk, m), ("rstd", rk, r)):
-            q, i = R.worst(k, ref, 0.5 * R._ulp(ref, 23) * (1 + 1e-6) + 1e-300)
+            q, i = R.worst(k, ref, 0.5 * R.ulp(ref, 23) * (1 + 1e-6) + 1e-300)
             assert q <= 1.0, (case.id, name, "not the fp32 rounding of the fp64 value", i, float(k[i]), float(ref[i]))
         return {}
     m, r = R.stats(x, case.kind, case.G, EPS)
@@ -206,9 +175,9 @@ def judge(case, inp, got, last4=False):
                 r, tol = r[idx.to(g.device)], tol[idx.to(g.device)]
             if last4:
                 q, i = R.worst(g[..., -4:], r[..., -4:], tol[..., -4:])
-                assert q <= 1.0, (case.id, names, name, "last 4 samples of row", _where(i, g[..., -4:].shape)[:2], q)
+                assert q <= 1.0, (case.id, names, name, "last 4 samples of row", where(i, g[..., -4:].shape)[:2], q)
         q, i = R.worst(g, r, tol)
-        assert q <= 1.0, (case.id, names, name, "element", _where(i, tuple(g.shape)), "error / bound", q, "got", float(g.reshape(-1)[i]),
+        assert q <= 1.0, (case.id, names, name, "element", where(i, tuple(g.shape)), "error / bound", q, "got", float(g.reshape(-1)[i]),
                           "ref", float(r.reshape(-1)[i]), "floor", fl[name])
     return fl
 
@@ -325,4 +294,4 @@ def test_handed_over_sums_through_the_wrapper():
     for sums in (torch.stack([s1, s2], -1), _split_sums(s1, s2, 16, torch.Generator().manual_seed(1))):
         y = nnops.group_norm(x, 3, w, b, EPS, "gelu", sums=sums.cuda())
         q, i = R.worst(y.cpu(), ref["y"], R.tolerance("y", ref, mag, slack, fl))
-        assert q <= 1.0, (tuple(sums.shape), _where(i, tuple(y.shape)), q)
+        assert q <= 1.0, (tuple(sums.shape), where(i, tuple(y.shape)), q)

@@ -11,36 +11,9 @@ import pytest
 import torch
 
 from tests import optim_ref as O
+from tests.kernel_harness import Guarded, api, stop_after_a_device_error  # noqa: F401
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]
-
-GUARD = 4096
-_FILL = {torch.float32: (torch.int32, 0x7FC00000), torch.float64: (torch.int64, 0x7FF8000000000000)}
-
-
-class _Buf:
-    def __init__(self, n, dtype=torch.float32, what="", init=None):
-        self.what, self.n = what, n
-        self.buf = torch.full((GUARD + n + GUARD,), float("nan"), device="cuda", dtype=dtype)
-        self.t = self.buf[GUARD:GUARD + n]
-        if init is not None:
-            self.t.copy_(init)
-
-    def guards_intact(self):
-        it, pat = _FILL[self.buf.dtype]
-        bits = self.buf.view(it)
-        assert bool((bits[:GUARD] == pat).all()) and bool((bits[GUARD + self.n:] == pat).all()), f"{self.what}: guard overwritten"
-
-    def owned(self):
-        self.guards_intact()
-        bad = ~torch.isfinite(self.t)
-        assert not bool(bad.any()), f"{self.what}: element {int(bad.nonzero()[0])} of {self.n} not finite"
-
-
-def _api():
-    from remfx_amd import _lib
-    from remfx_amd.ops import _ptr, _stream
-    return _lib.lib(), _ptr, _stream
 
 
 def _grad(n, seed):
@@ -52,16 +25,15 @@ def _grad(n, seed):
 
 
 def _sumsq(gcpu):
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     n = gcpu.numel()
-    g = _Buf(max(n, 1), what="g", init=gcpu if n else None)
-    ws = _Buf(O.SLOTS, torch.float64, what="ws")
-    out = _Buf(1, torch.float64, what="out")
-    before = g.buf.clone()
+    g = Guarded(max(n, 1), what="g", init=gcpu if n else None)
+    ws = Guarded(O.SLOTS, torch.float64, what="ws")
+    out = Guarded(1, torch.float64, what="out")
     assert L.rfx_sumsq(_ptr(g.t), n, _ptr(ws.t), _ptr(out.t), _stream()) == 0
     torch.cuda.synchronize()
     out.owned(); ws.guards_intact()
-    assert torch.equal(g.buf.view(torch.int32), before.view(torch.int32)), "g was written"
+    g.unchanged()
     slots = ws.t.cpu()
     used = O.forms(n)["slots"]
     assert bool(torch.isfinite(slots[:used]).all()) and bool(torch.isnan(slots[used:]).all()), ("slots written", used)
@@ -90,11 +62,11 @@ def test_sumsq(n):
 def test_clip_coef(form):
     """norm above max_norm (coef = max_norm / (norm pre + 1e-6) pre), below it (pre), max_norm == 0 with pre = 0.25 (exactly pre), and
     norm_out == NULL: 16 fp32 half-ulps of the result (sqrt, two products, a sum, a quotient)"""
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     total, max_norm, pre = {"above": (1e4, 10.0, 0.5), "below": (400.0, 10.0, 0.25), "max_norm_0": (1e4, 0.0, 0.25),
                             "no_norm_out": (1e4, 10.0, 1.0)}[form]
     ss = torch.tensor([total], device="cuda", dtype=torch.float64)
-    coef, norm = _Buf(1, what="coef"), _Buf(1, what="norm")
+    coef, norm = Guarded(1, what="coef"), Guarded(1, what="norm")
     assert L.rfx_clip_coef(_ptr(ss), max_norm, pre, _ptr(coef.t), None if form == "no_norm_out" else _ptr(norm.t), _stream()) == 0
     torch.cuda.synchronize()
     coef.owned()
@@ -106,19 +78,17 @@ def test_clip_coef(form):
     if form == "above":
         assert c < pre
     if form == "no_norm_out":
-        it, pat = _FILL[torch.float32]
-        assert bool((norm.buf.view(it) == pat).all()), "norm_out == NULL, yet something was written"
+        norm.untouched()                                         # norm_out == NULL: nothing is written
     else:
         norm.owned()
         assert abs(float(norm.t.cpu()) - rn) <= 8 * O.EPS32 * rn
 
 
 def _adamw(state, n, lr, step, gscale):
-    L, _ptr, _stream = _api()
+    L, _ptr, _stream = api()
     b1, b2 = O.HYPER["betas"]
-    bufs = {k: _Buf(n, what=k, init=state[k]) for k in ("p", "g", "m", "v")}
+    bufs = {k: Guarded(n, what=k, init=state[k]) for k in ("p", "g", "m", "v")}
     gs = torch.tensor([gscale], device="cuda") if gscale is not None else None
-    gbits = bufs["g"].buf.clone()
     out = []
     for s in (step, step + 1):                                   # two consecutive steps on the same buffers: m, v are read back
         assert L.rfx_adamw_step(_ptr(bufs["p"].t), _ptr(bufs["g"].t), _ptr(bufs["m"].t), _ptr(bufs["v"].t), n, lr, b1, b2, O.HYPER["eps"],
@@ -126,7 +96,7 @@ def _adamw(state, n, lr, step, gscale):
         torch.cuda.synchronize()
         for b in bufs.values():
             b.owned()
-        assert torch.equal(bufs["g"].buf.view(torch.int32), gbits.view(torch.int32)), "g was written"
+        bufs["g"].unchanged()
         out.append({k: bufs[k].t.cpu() for k in ("p", "m", "v")})
     return out
 
@@ -166,13 +136,12 @@ def test_adamw_step(n, step, lr, gscale):
 
 def test_adamw_argument_guards():
     """step < 1 is refused; n == 0 returns 0 and touches nothing"""
-    L, _ptr, _stream = _api()
-    bufs = [_Buf(8, what=k) for k in "pgmv"]
+    L, _ptr, _stream = api()
+    bufs = [Guarded(8, what=k) for k in "pgmv"]
     ptrs = [_ptr(b.t) for b in bufs]
     assert L.rfx_adamw_step(*ptrs, 8, 1e-4, 0.95, 0.999, 1e-6, 1e-3, 0, None, _stream()) != 0
     assert L.rfx_adamw_step(*ptrs, 8, 1e-4, 0.95, 0.999, 1e-6, 1e-3, -3, None, _stream()) != 0
     assert L.rfx_adamw_step(*ptrs, 0, 1e-4, 0.95, 0.999, 1e-6, 1e-3, 1, None, _stream()) == 0
     torch.cuda.synchronize()
-    it, pat = _FILL[torch.float32]
     for b in bufs:
-        assert bool((b.buf.view(it) == pat).all()), f"{b.what} was touched"
+        b.untouched()

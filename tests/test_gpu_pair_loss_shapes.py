@@ -25,10 +25,11 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.kernel_harness import GUARD                           # NaN-filled elements on each side of every output buffer
+
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]               # no GEMM inside: one arithmetic mode
 DEV = "cuda:0"
 EPS = 1e-8
-GUARD = 4096                                                    # NaN-filled elements on each side of every output buffer
 
 RES = [(1024, 120, 600), (2048, 240, 1200), (512, 50, 240)]     # auraloss: n_fft, hop, win
 CASES = [(n, h, w, R, T) for (n, h, w) in RES for R in (3, 9) for T in (n + 3 * h, 16 * n + 7)] + [(512, 50, 240, 8, 880000)]
