@@ -484,7 +484,9 @@ int rfx_fx_sox_reverb(const float* x, float* y, float* ws, int32_t B, int32_t Ci
  * (csrc/dconv.hip).  Weights in PyTorch layout: w1 (12, 48, 3), w2 (96, 12[, 1]).  rfx_dconv_layer_ok: shape test.
  * Training: pass all four of h16 (N, 12, T) bf16 = conv1 output, z16 (N, 96, T) bf16 = conv2 output, a_out (N, 12, T) fp32 =
  * GELU(GN(h)), stats (4, N) fp32 = mean1, rstd1, mean2, rstd2 -- exactly what rfx_groupnorm_bwd_x16 / the gather-GEMM input- and
- * weight-gradient kernels of the layer-by-layer path read; inference: all four NULL. */
+ * weight-gradient kernels of the layer-by-layer path read; inference: all four NULL.
+ * Alignment (both entries): every fp32 buffer element-aligned (4 bytes); every bf16 buffer (h16, z16, dz_bf16, dh_bf16) 4-byte
+ * aligned -- dz is written with 4-byte stores of two positions.  Nothing needs more (tests/test_gpu_dconv_kernel.py runs both). */
 int rfx_dconv_layer_ok(int32_t C, int32_t T, int32_t dil);
 int rfx_dconv_layer_fwd(const float* x, float* out, int32_t N, int32_t C, int32_t T, int32_t dil, const float* w1, const float* b1,
                         const float* gn1w, const float* gn1b, const float* w2, const float* b2, const float* gn2w,
