@@ -626,6 +626,27 @@ int rfx_bound_mask_bwd(const float* m, const float* tf, const float* gout, float
 int rfx_phase_mask_fwd(const float* mag, const float* xc, float* out, int64_t n, void* stream);
 int rfx_phase_mask_bwd(const float* xc, const float* gout, float* gmag, int64_t n, void* stream);
 
+/* Open-Unmix Separator, every other mode: the multichannel Wiener filter refined by expectation-maximisation (csrc/wiener.hip; DESIGN.md
+ * 4.27).  The calls it replaces are open-unmix-pytorch `filtering.wiener(targets_spectrograms, mix_stft, iterations, softmask, residual)`
+ * and its `expectation_maximization`, which `Separator.forward` runs once per sample and per window of `wiener_win_len` frames.
+ *   X (B*C, bins, frames, 2) fp32: the mixture STFT; S (J0, B*C, bins, frames) fp32 >= 0: the targets' magnitudes;
+ *   Y (B, J, C, bins, frames, 2) fp32, J = J0 + residual, every element stored once.
+ * Per sample and window of n <= W frames (windows tile the frame axis from 0, the last may be short), eps = 1e-10:
+ *   A. y_j = S_j X/|X| (X = 0: X/|X| = 1), or with softmask y_j = X S_j / (eps + sum_i S_i); residual: y_J0 = X - sum_j y_j.
+ *      niter = 0: stored as they are.
+ *   B. m = max(1, max over the window's channels, bins, frames of |X| / 10); x = X / m, y = y / m.
+ *   C. niter times, per bin: v_j[t] = mean_c |y_j[c][t]|^2; R_j = sum_t y_j[t] y_j[t]^H / (eps + sum_t v_j[t]);
+ *      Cxx[t] = sqrt(eps) I + sum_j v_j[t] R_j; y_j[t] = v_j[t] R_j Cxx[t]^{-1} x[t] (closed-form inverse).
+ *   D. Y = m y.
+ * One workgroup per (sample, window, bin) keeps x and y in LDS between A and D; fixed summation order, no atomics: bit-reproducible.
+ * ws: rfx_wiener_ws_floats(B, C, bins, frames, W) floats, no initialisation needed; read only when niter > 0 (may be NULL otherwise).
+ * Refused (-1, nothing launched): C outside {1, 2}; J outside 1..8; niter > 0 with J == 1 (upstream raises); W < 1 or
+ * W > rfx_wiener_max_window() (what one workgroup's LDS holds at C = 2, J = 8), whatever `frames` is. */
+int rfx_wiener_max_window(void);
+int64_t rfx_wiener_ws_floats(int32_t B, int32_t C, int32_t bins, int32_t frames, int32_t W);
+int rfx_wiener(const float* X, const float* S, float* Y, int32_t B, int32_t C, int32_t J0, int32_t residual, int32_t bins,
+               int32_t frames, int32_t W, int32_t niter, int32_t softmask, float* ws, void* stream);
+
 /* ---- losses -------------------------------------------------------------------
  * auraloss STFTLoss terms on complex spectra [R][n] (n = bins*frames, view_as_real layout):
  * sums[r] = { sum (|Y|-|X|)^2, sum |Y|^2, sum |log|X| - log|Y|| }, |.| = sqrt(max(re^2+im^2, eps)) (written, not accumulated).

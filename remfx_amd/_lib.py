@@ -187,6 +187,9 @@ SIGNATURES = {
     "rfx_bound_mask_bwd": [_P, _P, _P, _P, _I32, _I64, _I64, _I64, _I64, _I64, _P],
     "rfx_phase_mask_fwd": [_P, _P, _P, _I64, _P],
     "rfx_phase_mask_bwd": [_P, _P, _P, _I64, _P],
+    "rfx_wiener_max_window": [],
+    "rfx_wiener_ws_floats": [_I32, _I32, _I32, _I32, _I32],
+    "rfx_wiener": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P],
     "rfx_glu_fwd": [_P, _P, _I64, _I64, _I64, _P],
     "rfx_glu_bwd": [_P, _P, _P, _I64, _I64, _I64, _P],
     "rfx_glu_bwd_bf16": [_P, _P, _P, _I64, _I64, _I64, _P],
@@ -280,7 +283,7 @@ SIGNATURES = {
 }
 
 _RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_stft_scaled_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",
-          "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats", "rfx_fx_normalize_ws_bytes", "rfx_time_sums_ws", "rfx_logcosh_ws"}
+          "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats", "rfx_fx_normalize_ws_bytes", "rfx_time_sums_ws", "rfx_logcosh_ws", "rfx_wiener_ws_floats"}
 _lib = None
 
 

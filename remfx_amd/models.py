@@ -227,7 +227,8 @@ class DemucsModel(_RemovalWrapper):
 
 class OpenUnmixModel(_RemovalWrapper):
     def __init__(self, n_fft: int = 2048, hop_length: int = 512, n_channels: int = 1, alpha: float = 0.3,
-                 sample_rate: int = 22050, mrstft_kwargs=None, time_loss_kwargs=None, perceptual_kwargs=None, sum_diff_kwargs=None):
+                 sample_rate: int = 22050, mrstft_kwargs=None, time_loss_kwargs=None, perceptual_kwargs=None, sum_diff_kwargs=None,
+                 separator_kwargs=None):
         super().__init__()
         from .umx import OpenUnmix, Separator
         from .utils import spectrogram
@@ -238,7 +239,7 @@ class OpenUnmixModel(_RemovalWrapper):
         self.sample_rate = sample_rate
         self.model = OpenUnmix(nb_channels=n_channels, nb_bins=self.num_bins)
         self.separator = Separator(target_models={"other": self.model}, nb_channels=n_channels,
-                                   sample_rate=sample_rate, n_fft=n_fft, n_hop=hop_length)
+                                   sample_rate=sample_rate, n_fft=n_fft, n_hop=hop_length, **(separator_kwargs or {}))
         self.mrstftloss = _mrstft(self.num_bins, sample_rate, mrstft_kwargs)
         self.l1loss = L1Loss()
         self._set_time_loss(time_loss_kwargs)
@@ -248,11 +249,11 @@ class OpenUnmixModel(_RemovalWrapper):
         x, target = batch
         X = self._spectrogram(x, self.window, self.n_fft, self.hop_length, self.alpha)
         Y = self.model(X)  # noqa: F841  dead value kept: it updates BN running stats / draws dropout (Q3)
-        sep_out = self.separator(x).squeeze(1)
+        sep_out = self.separator(x)[:, 0]                    # source 0 = the "other" model; a residual, if asked for, follows it
         return self._loss(sep_out, target), sep_out
 
     def sample(self, x: Tensor) -> Tensor:
-        return self.separator(x).squeeze(1)
+        return self.separator(x)[:, 0]
 
 
 class DCUNetModel(_RemovalWrapper):
