@@ -78,10 +78,7 @@ def spec_augment(x, freq_mask_param, time_mask_param):
     y = x.detach().clone()
     f0, f1 = _iid_span(B * Cc, Fq, freq_mask_param, x.device)
     t0, t1 = _iid_span(B * Cc, T, time_mask_param, x.device)
-    from . import _lib
-    from .ops import _ptr, _stream
-    _lib.check(_lib.lib().rfx_span_mask(_ptr(y), B * Cc, Fq, T, _ptr(f0), _ptr(f1), _ptr(t0), _ptr(t1), _stream()),
-               "rfx_span_mask")
+    ops.launch("rfx_span_mask", y, B * Cc, Fq, T, f0, f1, t0, t1)
     return y
 
 

@@ -12,16 +12,12 @@ import os as _os
 import numpy as np
 import torch
 
-from . import _lib, ops
-from ._lib import ClConvDesc, ClTensor, ClWgradDesc, check
+from ._lib import ClConvDesc, ClTensor, ClWgradDesc
+from .ops import launch, query
 
 TRACE = None                  # tests set this to a list: conv / wgrad append ("conv" | "wgrad", variant code) of every launch they make
 
 EPI = {"store": 0, "gelu": 1, "glu": 2, "dgelu": 3, "dglu": 4, "store_cm": 5}
-
-
-def _stream():
-    return C.c_void_p(ops.raw_stream())
 
 
 def cl_tensor(t, c0=0):
@@ -53,8 +49,8 @@ def from_cm(x, out=None, res=None, aux=None, mode="store"):
     if out is None:
         out = empty(N, A, B, 2 * Cc if mode == "dglu" else Cc, x.device)
     ct, cr, ca = cl_tensor(out), cl_tensor(res), cl_tensor(aux)
-    check(_lib.lib().rfx_cl_from_cm(C.c_void_p(x.data_ptr()), int(x.dtype == torch.bfloat16), x.stride(0), x.stride(1), x.stride(2),
-                                    N, Cc, A, B, C.byref(ct), C.byref(cr), C.byref(ca), FROM_CM_MODE[mode], _stream()), "rfx_cl_from_cm")
+    launch("rfx_cl_from_cm", x, int(x.dtype == torch.bfloat16), x.stride(0), x.stride(1), x.stride(2), N, Cc, A, B,
+           C.byref(ct), C.byref(cr), C.byref(ca), FROM_CM_MODE[mode])
     return out
 
 
@@ -65,9 +61,8 @@ def to_cm(x, dtype=torch.float32, out=None, aux16=None):
     if out is None:
         out = torch.empty((N, Cc, A, B), device=x.device, dtype=dtype)
     ct = cl_tensor(x)
-    check(_lib.lib().rfx_cl_to_cm(C.byref(ct), N, Cc, A, B, C.c_void_p(out.data_ptr()), int(out.dtype == torch.bfloat16),
-                                  out.stride(0), out.stride(1), out.stride(2),
-                                  C.c_void_p(aux16.data_ptr()) if aux16 is not None else None, _stream()), "rfx_cl_to_cm")
+    launch("rfx_cl_to_cm", C.byref(ct), N, Cc, A, B, out, int(out.dtype == torch.bfloat16), out.stride(0), out.stride(1), out.stride(2),
+           aux16)
     return out
 
 
@@ -76,8 +71,7 @@ def dgelu(g, z):
     if g.shape != z.shape or not g.is_contiguous() or not z.is_contiguous():
         raise ValueError("dgelu: dense tensors of one shape")
     out = torch.empty_like(g)
-    check(_lib.lib().rfx_cl_dgelu(C.c_void_p(g.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(out.data_ptr()), g.numel(), _stream()),
-          "rfx_cl_dgelu")
+    launch("rfx_cl_dgelu", g, z, out, g.numel())
     return out
 
 
@@ -87,8 +81,7 @@ def dglu(g, zab):
     if zab.shape[-1] != 2 * Cc or g.numel() * 2 != zab.numel() or not g.is_contiguous() or not zab.is_contiguous():
         raise ValueError("dglu: dense tensors (..., C) and (..., 2C)")
     out = torch.empty_like(zab)
-    check(_lib.lib().rfx_cl_dglu(C.c_void_p(g.data_ptr()), C.c_void_p(zab.data_ptr()), C.c_void_p(out.data_ptr()), g.numel() // Cc, Cc,
-                                 _stream()), "rfx_cl_dglu")
+    launch("rfx_cl_dglu", g, zab, out, g.numel() // Cc, Cc)
     return out
 
 
@@ -166,8 +159,7 @@ def pack(form, w):
     idx = _dev_index(form, w.device)
     wf = w if w.is_contiguous() else w.contiguous()
     out = torch.empty(idx.numel(), device=w.device, dtype=torch.bfloat16)
-    check(_lib.lib().rfx_cl_pack(C.c_void_p(wf.data_ptr()), C.c_void_p(idx.data_ptr()), idx.numel(), C.c_void_p(out.data_ptr()),
-                                 _stream()), "rfx_cl_pack")
+    launch("rfx_cl_pack", wf, idx, idx.numel(), out)
     return out
 
 
@@ -191,8 +183,8 @@ def conv(form, apack, x, N, IA, IB, OA, mode, bias=None, out0=None, out1=None, a
             raise ValueError("store_cm: fp32 (N, C, rows, positions) with contiguous positions")
         d.cm_out, d.cm_ns, d.cm_cs, d.cm_as, d.cm_fold = cm_out.data_ptr(), cm_out.stride(0), cm_out.stride(1), cm_out.stride(2), int(cm_fold)
     if TRACE is not None:
-        TRACE.append(("conv", _lib.lib().rfx_cl_conv_variant(C.byref(d))))
-    check(_lib.lib().rfx_cl_conv(C.byref(d), _stream()), "rfx_cl_conv")
+        TRACE.append(("conv", query("rfx_cl_conv_variant", C.byref(d))))
+    launch("rfx_cl_conv", C.byref(d))
 
 
 # ---- GEMM forms of the Hybrid Demucs layers ---------------------------------------------------------------------------------------
@@ -315,8 +307,7 @@ def im2col_s4(x, OA, OB, along_b):
     if x.dtype != torch.float32 or x.stride(3) != 1:
         x = x.float().contiguous()
     out = empty(N, OA, OB, 16, x.device)
-    check(_lib.lib().rfx_cl_im2col_s4(C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), x.stride(2), N, Cs, IA, IB, OA, OB, int(along_b),
-                                      C.c_void_p(out.data_ptr()), _stream()), "rfx_cl_im2col_s4")
+    launch("rfx_cl_im2col_s4", x, x.stride(0), x.stride(1), x.stride(2), N, Cs, IA, IB, OA, OB, int(along_b), out)
     return out
 
 
@@ -327,8 +318,7 @@ def im2col_fm(spec, a, b):
     if two != 2 or spec.dtype != torch.float32 or not spec.is_contiguous() or bins % 4:
         raise ValueError("im2col_fm: contiguous (N, frames, bins, 2) fp32 with bins % 4 == 0")
     out = empty(N, bins // 4, F, 16, spec.device)
-    check(_lib.lib().rfx_cl_im2col_fm(C.c_void_p(spec.data_ptr()), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), N, F, bins,
-                                      C.c_void_p(out.data_ptr()), _stream()), "rfx_cl_im2col_fm")
+    launch("rfx_cl_im2col_fm", spec, a, b, N, F, bins, out)
     return out
 
 
@@ -484,19 +474,16 @@ def wgrad(form, p, q, N, OA, IA, B, dw, db=None, accumulate=False, p_c0=0, q_c0=
     d.PW = PW
     d.S = form.splits(N * (B // PW) * OA)
     d.ahead, d.bias = min(form.ahead, int(_os.environ.get("RFX_CLW_AHEAD", "99"))), int(form.bias)
-    L = _lib.lib()
-    nws = L.rfx_cl_wgrad_ws_floats(C.byref(d))
+    nws = query("rfx_cl_wgrad_ws_floats", C.byref(d))
     if nws <= 0:
         raise RuntimeError("rfx_cl_wgrad: geometry rejected")
     ws = torch.empty(nws, device=p.device, dtype=torch.float32)
     d.ws = ws.data_ptr()
     if TRACE is not None:
-        TRACE.append(("wgrad", L.rfx_cl_wgrad_variant(C.byref(d))))
-    check(L.rfx_cl_wgrad(C.byref(d), _stream()), "rfx_cl_wgrad")
+        TRACE.append(("wgrad", query("rfx_cl_wgrad_variant", C.byref(d))))
+    launch("rfx_cl_wgrad", C.byref(d))
     mp = _dev_map(form, p.device)
-    check(L.rfx_cl_wgrad_reduce(C.c_void_p(ws.data_ptr()), C.c_void_p(mp.data_ptr()), mp.numel(), d.S, form.DT, form.RW, form.WK,
-                                C.c_void_p(dw.data_ptr()), form.wn, C.c_void_p(db.data_ptr()) if db is not None else None,
-                                int(accumulate), _stream()), "rfx_cl_wgrad_reduce")
+    launch("rfx_cl_wgrad_reduce", ws, mp, mp.numel(), d.S, form.DT, form.RW, form.WK, dw, form.wn, db, int(accumulate))
 
 
 def wform_conv(Cout, Cin, KA, KB):

@@ -18,8 +18,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, clast, ops
-from ._lib import check
+from . import clast, ops
 
 _FORMS = {}
 _BUILD = {
@@ -86,8 +85,7 @@ def rowsum(x, A, Cc, out, scale=1.0, accumulate=False):
         N, ct.ns = N * XA, ct.as_
     G = max(1, min(N, -(-2048 // A)))
     partial = torch.empty((G, A, Cc), device=x.device, dtype=torch.float32)
-    check(_lib.lib().rfx_cl_rowsum(C.byref(ct), N, A, B, Cc, G, float(scale), C.c_void_p(partial.data_ptr()), C.c_void_p(out.data_ptr()),
-                                   int(accumulate), C.c_void_p(ops.raw_stream())), "rfx_cl_rowsum")
+    ops.launch("rfx_cl_rowsum", C.byref(ct), N, A, B, Cc, G, float(scale), partial, out, int(accumulate))
     return out
 
 

@@ -10,8 +10,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, clast, clchain, ops
-from ._lib import ClDconvDesc, check
+from . import clast, clchain, ops
+from ._lib import ClDconvDesc
 
 T = 256
 import os as _os
@@ -73,7 +73,7 @@ def tables(Cc, H):
 
 
 def supported(Cc, H, backward, positions=T):
-    return bool(_lib.lib().rfx_cl_dconv_ok(int(Cc), int(H), int(positions), int(backward)))
+    return bool(ops.query("rfx_cl_dconv_ok", int(Cc), int(H), int(positions), int(backward)))
 
 
 def _dx_form(Cc, H, dil):
@@ -101,14 +101,12 @@ def _wforms(Cc, H, dil):
     return f
 
 
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale):
     d = ClDconvDesc()
     d.S, d.C, d.H, d.dil, d.grid, d.eps = S, Cc, H, dil, GRID, eps
-    d.b1, d.g1w, d.g1b, d.b2, d.g2w, d.g2b, d.scale = _p(b1), _p(g1w), _p(g1b), _p(b2), _p(g2w), _p(g2b), _p(scale)
+    for field, t in (("b1", b1), ("g1w", g1w), ("g1b", g1b), ("b2", b2), ("g2w", g2w), ("g2b", g2b), ("scale", scale)):
+        if t is not None:                           # an absent parameter stays the null pointer
+            setattr(d, field, t.data_ptr())
     return d
 
 
@@ -145,7 +143,7 @@ def layer_forward(x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps, train,
         a = alloc("a", (Bn, A, Tt, HP), torch.bfloat16, dev)
         hpre = alloc("hpre", (Bn, A, Tt, HP), torch.bfloat16, dev)
         d.a, d.hpre = a.data_ptr(), hpre.data_ptr()
-    check(_lib.lib().rfx_cl_dconv_fwd(C.byref(d), C.c_void_p(ops.raw_stream())), "rfx_cl_dconv_fwd")
+    ops.launch("rfx_cl_dconv_fwd", C.byref(d))
     return y, a, hpre, stats
 
 
@@ -186,8 +184,7 @@ def layer_backward(gy, x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, sc
         for q, t in enumerate(sw.grads):
             d.pg_dst[q] = t.data_ptr()
     with sw or ops.NO_SINK:
-        check(_lib.lib().rfx_cl_dconv_bwd(C.byref(d), C.c_void_p(pg.data_ptr() if pg is not None else None),
-                                          C.c_void_p(ops.raw_stream())), "rfx_cl_dconv_bwd")
+        ops.launch("rfx_cl_dconv_bwd", C.byref(d), pg)
     if passes:                                      # dx = gy + the transposed 3-tap convolution of dh (taps cross tile edges)
         fx = _dx_form(Cc, H, dil)
         clast.conv(fx, clchain.packed(fx, w1), dh, Bn, A, Tt, A, "store", out0=dx, res=gy)

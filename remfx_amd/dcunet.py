@@ -16,17 +16,14 @@ MI355X design:
     the pre-allocated concatenation buffer (the apply kernel takes an output stride / offset);
   * the STFT filterbank conv writes into the time-padded (B, 2, 513, 1025) buffer the masker reads.
 """
-import ctypes as C
-
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import check
-from .ops import _ptr, _stream
+from . import ops
+from .ops import launch, query
 
 ENCODERS = ((1, 45, (7, 1), (1, 1)), (45, 45, (1, 7), (1, 1)), (45, 90, (7, 5), (2, 2)), (90, 90, (7, 5), (2, 1)),
             (90, 90, (5, 3), (2, 2)), (90, 90, (5, 3), (2, 1)), (90, 90, (5, 3), (2, 2)), (90, 90, (5, 3), (2, 1)),
@@ -146,7 +143,6 @@ class _CplxNormActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, norm, dst, *params):
-        L = _lib.lib()
         y = y.contiguous()
         N, C2, H, W = y.shape
         Cc, S = C2 // 2, H * W
@@ -156,31 +152,27 @@ class _CplxNormActFn(torch.autograd.Function):
         coefc = torch.empty((6, Cc), device=y.device, dtype=torch.float32)
         if norm.training:
             sums = torch.empty(Cc * 5, device=y.device, dtype=torch.float64)
-            ws = torch.empty(5 * Cc * int(L.rfx_cplx_slots(N, S)), device=y.device, dtype=torch.float64)
-            check(L.rfx_cplx_moments(_ptr(y), N, Cc, S, _ptr(ws), _ptr(sums), _stream()), "rfx_cplx_moments")
+            ws = torch.empty(5 * Cc * query("rfx_cplx_slots", N, S), device=y.device, dtype=torch.float64)
+            launch("rfx_cplx_moments", y, N, Cc, S, ws, sums)
             inv = 1.0 / float(N * S)
-            check(L.rfx_cplx_coef_fwd(_ptr(sums), inv, None, *[_ptr(t) for t in pw], norm.eps, Cc, _ptr(coefc), None,
-                                      _ptr(norm.RMr), _ptr(norm.RMi), _ptr(norm.RVrr), _ptr(norm.RVri), _ptr(norm.RVii),
-                                      norm.momentum, _stream()), "rfx_cplx_coef_fwd")
+            launch("rfx_cplx_coef_fwd", sums, inv, None, *pw, norm.eps, Cc, coefc, None,
+                   norm.RMr, norm.RMi, norm.RVrr, norm.RVri, norm.RVii, norm.momentum)
             with torch.no_grad():
                 norm.num_batches_tracked += 1
             ctx.stat = (sums, inv, None)
         else:
             stats_in = torch.stack([norm.RMr, norm.RMi, norm.RVrr, norm.RVri, norm.RVii]).float().contiguous()
-            check(L.rfx_cplx_coef_fwd(None, 0.0, _ptr(stats_in), *[_ptr(t) for t in pw], norm.eps, Cc, _ptr(coefc), None,
-                                      None, None, None, None, None, 0.0, _stream()), "rfx_cplx_coef_fwd")
+            launch("rfx_cplx_coef_fwd", None, 0.0, stats_in, *pw, norm.eps, Cc, coefc, None, None, None, None, None, None, 0.0)
             ctx.stat = (None, 0.0, stats_in)
         dst = dst.t if dst is not None else torch.empty_like(y)
         assert dst.shape == y.shape and dst.stride(1) == S and dst.stride(3) == 1
-        check(L.rfx_cplx_affine_act_fwd(_ptr(y), _ptr(coefc), N, Cc, S, LEAKY, _ptr(dst), dst.stride(0), Cc, _stream()),
-              "rfx_cplx_affine_act_fwd")
+        launch("rfx_cplx_affine_act_fwd", y, coefc, N, Cc, S, LEAKY, dst, dst.stride(0), Cc)
         ctx.save_for_backward(y, coefc, *pw)
         ctx.norm = norm
         return dst
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         y, coefc, *pw = ctx.saved_tensors
         norm = ctx.norm
         N, C2, H, W = y.shape
@@ -189,17 +181,14 @@ class _CplxNormActFn(torch.autograd.Function):
             g = g.contiguous()
         gx = torch.empty_like(y)
         gcoef = torch.empty((6, Cc), device=y.device, dtype=torch.float32)
-        ws = torch.empty(6 * Cc * int(L.rfx_cplx_slots(N, S)), device=y.device, dtype=torch.float64)
-        check(L.rfx_cplx_affine_act_bwd(_ptr(y), _ptr(coefc), _ptr(g), g.stride(0), Cc, N, Cc, S, LEAKY, _ptr(gx),
-                                        _ptr(ws), _ptr(gcoef), _stream()), "rfx_cplx_affine_act_bwd")
+        ws = torch.empty(6 * Cc * query("rfx_cplx_slots", N, S), device=y.device, dtype=torch.float64)
+        launch("rfx_cplx_affine_act_bwd", y, coefc, g, g.stride(0), Cc, N, Cc, S, LEAKY, gx, ws, gcoef)
         sums, inv, stats_in = ctx.stat
         gw = torch.empty((5, Cc), device=y.device, dtype=torch.float32)
         cm = torch.empty((5, Cc), device=y.device, dtype=torch.float32) if sums is not None else None
-        check(L.rfx_cplx_coef_bwd(_ptr(sums) if sums is not None else None, inv, _ptr(stats_in) if stats_in is not None else None,
-                                  *[_ptr(t) for t in pw], norm.eps, Cc, _ptr(gcoef), _ptr(gw), _ptr(cm) if cm is not None else None,
-                                  _stream()), "rfx_cplx_coef_bwd")
+        launch("rfx_cplx_coef_bwd", sums, inv, stats_in, *pw, norm.eps, Cc, gcoef, gw, cm)
         if cm is not None:
-            check(L.rfx_cplx_moments_bwd(_ptr(y), _ptr(cm), N, Cc, S, _ptr(gx), _stream()), "rfx_cplx_moments_bwd")
+            launch("rfx_cplx_moments_bwd", y, cm, N, Cc, S, gx)
         ctx.stat = None
         return (gx, None, None, gw[0], gw[1], gw[2], gw[3], gw[4])
 
@@ -231,8 +220,7 @@ class _BoundMaskFn(torch.autograd.Function):
         N, _, H, W = m.shape
         P = H * W
         out = torch.empty_like(m)
-        check(_lib.lib().rfx_bound_mask_fwd(_ptr(m), _ptr(tf), _ptr(out), N, P, 2 * P, tf.stride(0), 2 * P, _stream()),
-              "rfx_bound_mask_fwd")
+        launch("rfx_bound_mask_fwd", m, tf, out, N, P, 2 * P, tf.stride(0), 2 * P)
         ctx.save_for_backward(m, tf)
         return out
 
@@ -243,8 +231,7 @@ class _BoundMaskFn(torch.autograd.Function):
         P = H * W
         g = g.contiguous()
         gm = torch.empty_like(m)
-        check(_lib.lib().rfx_bound_mask_bwd(_ptr(m), _ptr(tf), _ptr(g), _ptr(gm), N, P, 2 * P, tf.stride(0), 2 * P,
-                                            2 * P, _stream()), "rfx_bound_mask_bwd")
+        launch("rfx_bound_mask_bwd", m, tf, g, gm, N, P, 2 * P, tf.stride(0), 2 * P, 2 * P)
         return gm, None
 
 

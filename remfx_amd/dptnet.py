@@ -18,9 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, lstm, nnops, ops
-from ._lib import check
-from .ops import _ptr, _stream
+from . import lstm, nnops, ops
+from .ops import launch
 
 EPS = 1e-8
 
@@ -60,7 +59,7 @@ class _MhaFn(torch.autograd.Function):
         ch = E // heads
         out = torch.empty_like(q)
         stat = torch.empty((B * heads * T, 4), device=q.device, dtype=torch.float32)
-        check(_lib.lib().rfx_mha_fwd(_ptr(q), _ptr(k), _ptr(v), B, heads, ch, T, _ptr(stat), _ptr(out), _stream()), "rfx_mha_fwd")
+        launch("rfx_mha_fwd", q, k, v, B, heads, ch, T, stat, out)
         ctx.save_for_backward(q, k, v, stat, out)
         ctx.cfg = (B, heads, ch, T)
         return out
@@ -70,8 +69,7 @@ class _MhaFn(torch.autograd.Function):
         q, k, v, stat, out = ctx.saved_tensors
         B, heads, ch, T = ctx.cfg
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        check(_lib.lib().rfx_mha_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(stat), _ptr(out), _ptr(g.contiguous()), B, heads, ch, T,
-                                     _ptr(dq), _ptr(dk), _ptr(dv), _stream()), "rfx_mha_bwd")
+        launch("rfx_mha_bwd", q, k, v, stat, out, g.contiguous(), B, heads, ch, T, dq, dk, dv)
         return dq, dk, dv, None
 
 
@@ -82,7 +80,7 @@ class _PReLUFn(torch.autograd.Function):
         C = slope.numel()
         N, L = (x.shape[0], x[0].numel()) if C == 1 else (x.shape[0], x[0, 0].numel())
         y = torch.empty_like(x)
-        check(_lib.lib().rfx_prelu_fwd(_ptr(x), _ptr(slope), _ptr(y), N, C, L, _stream()), "rfx_prelu_fwd")
+        launch("rfx_prelu_fwd", x, slope, y, N, C, L)
         ctx.save_for_backward(x, slope)
         ctx.cfg = (N, C, L)
         return y
@@ -93,8 +91,7 @@ class _PReLUFn(torch.autograd.Function):
         N, C, L = ctx.cfg
         gx, gs = torch.empty_like(x), torch.empty_like(slope)
         ws = torch.empty(N * C, device=x.device, dtype=torch.float64)
-        check(_lib.lib().rfx_prelu_bwd(_ptr(x), _ptr(g.contiguous()), _ptr(slope), _ptr(gx), _ptr(ws), _ptr(gs), N, C, L, _stream()),
-              "rfx_prelu_bwd")
+        launch("rfx_prelu_bwd", x, g.contiguous(), slope, gx, ws, gs, N, C, L)
         return gx, gs
 
 

@@ -12,14 +12,12 @@ per-clip parameters.  ``forward(x)`` takes the reference's ``(channels, samples)
 Algorithms are restatements of the published JUCE / pedalboard / pyloudnorm code (oracle/ref_effects.py lists
 them; both packages are absent here, parity unpinned).
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import check
+from .ops import launch, query
 
 
 def loguniform(low=0, high=1):                         # effects.py:25-26
@@ -33,21 +31,6 @@ def rand(low=0, high=1):                               # effects.py:29-30
 
 def randint(low=0, high=1):                            # effects.py:33-34
     return torch.randint(low, high + 1, (1,)).numpy()[0]
-
-
-def _call(name, *args):
-    """Launch the library's entry point `name` on the current stream: a tensor goes as its device pointer, a numpy array as its
-    host pointer, None as a null pointer, any other value as it is.  `args` holds the tensors until the launch is queued: a
-    block freed before that would be handed to the next allocation."""
-    ptrs = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray)
-            else C.c_void_p(0) if a is None else a for a in args]
-    stream = C.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
-    check(getattr(_lib.lib(), name)(*ptrs, stream), name)
-
-
-def _ws_size(name, *dims):
-    """The workspace size the library's `name` query gives for a launch of these dimensions."""
-    return int(getattr(_lib.lib(), name)(*dims))
 
 
 def require_device(x):
@@ -148,7 +131,7 @@ class RandomPedalboardReverb(_RandomEffect):
         wet1 = _col(params, lambda p: 0.5 * (p["wet_dry"] * 3.0) * (1.0 + p["width"]), dev)
         dry = _col(params, lambda p: (1.0 - p["wet_dry"]) * 2.0, dev)
         y = torch.empty_like(clips)
-        _call("rfx_fx_reverb", clips, y, clips.shape[0], clips.shape[1], int(self.sample_rate), damp, fb, wet1, dry)
+        launch("rfx_fx_reverb", clips, y, clips.shape[0], clips.shape[1], int(self.sample_rate), damp, fb, wet1, dry)
         return y
 
 
@@ -213,9 +196,9 @@ class RandomSoxReverb(_RandomEffect):
                     coef.append([q["feedback"], q["damp"], q["gain"], q["wet_dry"]])
         dev = clips.device
         geom, coef = _vec(geom, dev, torch.int32), _vec(coef, dev)
-        ws = torch.empty(_ws_size("rfx_fx_sox_reverb_ws_floats", B, Cin, T), device=dev, dtype=torch.float32)
+        ws = torch.empty(query("rfx_fx_sox_reverb_ws_floats", B, Cin, T), device=dev, dtype=torch.float32)
         y = torch.empty((B, 2, T), device=dev, dtype=torch.float32)
-        _call("rfx_fx_sox_reverb", clips, y, ws, B, Cin, T, geom, coef, lds)
+        launch("rfx_fx_sox_reverb", clips, y, ws, B, Cin, T, geom, coef, lds)
         return y
 
     @staticmethod
@@ -238,7 +221,7 @@ class RandomPedalboardChorus(_RandomEffect):
     def render(self, clips, params):
         cols = [_col(params, k, clips.device) for k in ("rate_hz", "depth", "centre_delay_ms", "feedback", "mix")]
         y = torch.empty_like(clips)
-        _call("rfx_fx_chorus", clips, y, clips.shape[0], clips.shape[1], float(self.sample_rate), *cols)
+        launch("rfx_fx_chorus", clips, y, clips.shape[0], clips.shape[1], float(self.sample_rate), *cols)
         return y
 
 
@@ -255,7 +238,7 @@ class RandomPedalboardDelay(_RandomEffect):
         dev = clips.device
         d = _col(params, lambda p: int(p["delay_seconds"] * self.sample_rate), dev, torch.int32)
         y = torch.empty_like(clips)
-        _call("rfx_fx_delay", clips, y, clips.shape[0], clips.shape[1], d, _col(params, "feedback", dev), _col(params, "mix", dev))
+        launch("rfx_fx_delay", clips, y, clips.shape[0], clips.shape[1], d, _col(params, "feedback", dev), _col(params, "mix", dev))
         return y
 
 
@@ -268,7 +251,7 @@ class RandomPedalboardDistortion(_RandomEffect):
     def render(self, clips, params):
         g = _col(params, lambda p: 10.0 ** (p["drive_db"] / 20.0), clips.device)
         y = torch.empty_like(clips)
-        _call("rfx_fx_distortion", clips, y, clips.shape[0], clips.shape[1], g)
+        launch("rfx_fx_distortion", clips, y, clips.shape[0], clips.shape[1], g)
         return y
 
 
@@ -292,7 +275,7 @@ class RandomPedalboardCompressor(_RandomEffect):
         ca = _col(params, lambda p: _ballistics_cte(p["attack_ms"], self.sample_rate), dev)
         cr = _col(params, lambda p: _ballistics_cte(p["release_ms"], self.sample_rate), dev)
         y, ws = torch.empty_like(clips), torch.empty_like(clips)
-        _call("rfx_fx_compressor", clips, y, ws, clips.shape[0], clips.shape[1], thr, ratio, ca, cr)
+        launch("rfx_fx_compressor", clips, y, ws, clips.shape[0], clips.shape[1], thr, ratio, ca, cr)
         return y
 
 
@@ -364,7 +347,7 @@ class LoudnessNormalize(torch.nn.Module):
         hop_ws = torch.empty((N, nhop), device=clips.device, dtype=torch.float64)
         lufs = torch.empty(N, device=clips.device, dtype=torch.float32)
         gain = torch.empty_like(lufs)
-        _call("rfx_fx_loudness", clips, N, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
+        launch("rfx_fx_loudness", clips, N, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
         return lufs, gain
 
     def measure_joint(self, clips):
@@ -374,7 +357,7 @@ class LoudnessNormalize(torch.nn.Module):
         hop_ws = torch.empty((B * Ch, nhop), device=clips.device, dtype=torch.float64)
         lufs = torch.empty(B, device=clips.device, dtype=torch.float32)
         gain = torch.empty_like(lufs)
-        _call("rfx_fx_loudness_joint", clips, B, Ch, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
+        launch("rfx_fx_loudness_joint", clips, B, Ch, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
         return lufs, gain
 
     def normalize_rows(self, clips, state, rows=None):
@@ -396,15 +379,15 @@ class LoudnessNormalize(torch.nn.Module):
             if clips.untyped_storage().data_ptr() == state.untyped_storage().data_ptr():
                 raise ValueError("normalize_rows: the clips must live outside the state buffer")
         nhop, plan = self._plan(T)
-        ws = torch.empty(_ws_size("rfx_fx_normalize_ws_bytes", n, nhop) // 8 + 1, device=clips.device, dtype=torch.float64)
-        _call("rfx_fx_normalize_rows", clips, state, rows, n, T, *plan, float(self.target_lufs_db), ws)
+        ws = torch.empty(query("rfx_fx_normalize_ws_bytes", n, nhop) // 8 + 1, device=clips.device, dtype=torch.float64)
+        launch("rfx_fx_normalize_rows", clips, state, rows, n, T, *plan, float(self.target_lufs_db), ws)
         return state
 
     @staticmethod
     def _scale(rows, gain):
         """(N, T) rows times their (N,) gains, as a new tensor."""
         y = torch.empty_like(rows)
-        _call("rfx_fx_scale", rows, y, rows.shape[0], rows.shape[1], gain)
+        launch("rfx_fx_scale", rows, y, rows.shape[0], rows.shape[1], gain)
         return y
 
     def normalize_joint(self, clips):
@@ -469,7 +452,7 @@ def _eq_render(clips, params, sample_rate):
         raise ValueError("parametric EQ: every clip of one launch needs the same number of bands")
     coef = torch.from_numpy(np.stack([r for _, r in rows])).to(clips.device)
     y = torch.empty_like(clips)
-    _call("rfx_fx_eq", clips, y, N, T, nsec, chunk, coef)
+    launch("rfx_fx_eq", clips, y, N, T, nsec, chunk, coef)
     return y
 
 
@@ -535,7 +518,7 @@ def _widener_render(rows, widths):
     g = [_widener_gains(w) for w in widths]
     gm, gs = _vec([a for a, _ in g], rows.device), _vec([b for _, b in g], rows.device)
     y = torch.empty_like(rows)
-    _call("rfx_fx_widener", rows, y, rows.shape[0] // 2, rows.shape[1], gm, gs)
+    launch("rfx_fx_widener", rows, y, rows.shape[0] // 2, rows.shape[1], gm, gs)
     return y
 
 
@@ -584,8 +567,8 @@ class RandomVolumeAutomation(_RandomEffect):
             d0 += [0.0] + g[:-1] + [0.0] * pad
             d1 += g + [0.0] * pad
         dev = clips.device
-        # _call holds the three tables until the launch is queued: a freed block would be handed to the next _vec
-        _call("rfx_fx_volume", clips, clips.shape[0], clips.shape[1], S, _vec(ends, dev, torch.int32), _vec(d0, dev), _vec(d1, dev))
+        # launch holds the three tables until the launch is queued: a freed block would be handed to the next _vec
+        launch("rfx_fx_volume", clips, clips.shape[0], clips.shape[1], S, _vec(ends, dev, torch.int32), _vec(d0, dev), _vec(d1, dev))
         return clips
 
 
@@ -602,9 +585,9 @@ class RandomPedalboardPhaser(_RandomEffect):
         dev = clips.device
         N, T = clips.shape
         cols = [_col(params, k, dev) for k in ("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix")]
-        ws = torch.empty(_ws_size("rfx_fx_phaser_ws_floats", N, T), device=dev, dtype=torch.float32)
+        ws = torch.empty(query("rfx_fx_phaser_ws_floats", N, T), device=dev, dtype=torch.float32)
         y = torch.empty_like(clips)
-        _call("rfx_fx_phaser", clips, y, ws, N, T, float(self.sample_rate), *cols)
+        launch("rfx_fx_phaser", clips, y, ws, N, T, float(self.sample_rate), *cols)
         return y
 
 
@@ -634,7 +617,7 @@ class RandomPedalboardLimiter(_RandomEffect):
         prm = _vec(np.asarray(cols).T.copy(), clips.device)
         ws = torch.empty((2, N, T), device=clips.device, dtype=torch.float32)
         y = torch.empty_like(clips)
-        _call("rfx_fx_limiter", clips, y, ws, N, T, prm)
+        launch("rfx_fx_limiter", clips, y, ws, N, T, prm)
         return y
 
 

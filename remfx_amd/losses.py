@@ -52,9 +52,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, stft
-from ._lib import check
-from .ops import _ptr, _req, _stream, zeros
+from . import stft
+from .ops import _req, launch, query, zeros
 
 FFT_SIZES = (1024, 2048, 512)
 HOP_SIZES = (120, 240, 50)
@@ -124,9 +123,8 @@ def _pair_sums(x2, y2, n_fft, hop, win, w, eps, store):
     X = torch.empty((R, frames, bins, 2), device=x2.device, dtype=torch.float32) if store else None
     ym = torch.empty((R, frames, bins), device=x2.device, dtype=torch.float32) if store else None
     d = stft._desc(R, L, n_fft, hop, win, bins, 0, frames, _SPEC_MODE)
-    ws = torch.empty(int(_lib.lib().rfx_stft_pair_loss_ws(C.byref(d))), device=x2.device, dtype=torch.float64)   # one slot per workgroup
-    check(_lib.lib().rfx_stft_pair_loss(C.byref(d), _ptr(x2), _ptr(y2), _ptr(w), eps, _ptr(ws), _ptr(sums), _ptr(X), _ptr(ym),
-                                        _stream()), "rfx_stft_pair_loss")
+    ws = torch.empty(query("rfx_stft_pair_loss_ws", C.byref(d)), device=x2.device, dtype=torch.float64)   # one slot per workgroup
+    launch("rfx_stft_pair_loss", C.byref(d), x2, y2, w, eps, ws, sums, X, ym)
     if _MEMO is not None:
         _MEMO[key] = (sums, X, ym, x2, y2)      # holding the signals keeps their storage from being reused under the key
     return sums, X, ym
@@ -202,13 +200,11 @@ def _scaled_sums(X, Y, bank, eps, weights, store):
     sums = torch.empty((R, 4), device=X.device, dtype=torch.float64)         # written, not accumulated: no zero fill
     mx = torch.empty((R, frames, n_out), device=X.device, dtype=torch.float32) if store else None
     my = torch.empty((R, frames, n_out), device=X.device, dtype=torch.float32) if store else None
-    ws = torch.empty(int(_lib.lib().rfx_stft_scaled_loss_ws(R, frames)), device=X.device, dtype=torch.float64)   # one slot per workgroup
+    ws = torch.empty(query("rfx_stft_scaled_loss_ws", R, frames), device=X.device, dtype=torch.float64)   # one slot per workgroup
     if bank is not None and (bank.bins != bins or bank.w.device != X.device):
         raise ValueError(f"filter bank for {bank.bins} bins on {bank.w.device}, spectrum has {bins} on {X.device}")
-    check(_lib.lib().rfx_stft_scaled_loss(_ptr(X), _ptr(Y), R, frames, bins, _ptr(bank.idx if bank is not None else None),
-                                          _ptr(bank.w if bank is not None else None), n_out,
-                                          bank.w.numel() if bank is not None else 0, eps, _ptr(ws), _ptr(sums), _ptr(mx), _ptr(my),
-                                          _stream()), "rfx_stft_scaled_loss")
+    launch("rfx_stft_scaled_loss", X, Y, R, frames, bins, bank.idx if bank is not None else None,
+           bank.w if bank is not None else None, n_out, bank.w.numel() if bank is not None else 0, eps, ws, sums, mx, my)
     hit = (sums, mx, my)
     if _MEMO is not None and ("spec", X.data_ptr()) in _MEMO and ("spec", Y.data_ptr()) in _MEMO:
         _MEMO[key] = hit                                                     # both spectra are held by the memo: pointers stay valid
@@ -235,10 +231,9 @@ def _scaled_forward(ctx, x, y, fft_sizes, hops, wins, eps, per_example_sc, weigh
         part = saved[c0:c0 + 8]
         m = len(part)
         t = torch.empty((), device=x.device, dtype=torch.float32)
-        sp = (C.c_void_p * m)(*[_ptr(e[3]) for e in part])
+        sp = (C.c_void_p * m)(*[e[3].data_ptr() for e in part])
         nn_ = (C.c_int64 * m)(*[int(e[4]) for e in part])
-        check(_lib.lib().rfx_mrstft_combine_w(sp, nn_, m, R, 1 if per_example_sc else 0, weights[0], weights[1], weights[2], _ptr(t),
-                                              _stream()), "rfx_mrstft_combine_w")
+        launch("rfx_mrstft_combine_w", sp, nn_, m, R, 1 if per_example_sc else 0, weights[0], weights[1], weights[2], t)
         total = t if nres <= 8 else (t * (m / nres) if total is None else total + t * (m / nres))
     ctx.scaled = True
     ctx.saved = saved
@@ -253,14 +248,12 @@ def _scaled_backward(ctx, g):
     for ires, (X, mx, my, sums, n, n_fft, hop, win, bank) in enumerate(ctx.saved):
         frames, bins = X.shape[1], X.shape[2]
         G = torch.empty_like(X)
-        check(_lib.lib().rfx_stft_scaled_loss_grad(
-            _ptr(X), _ptr(mx), _ptr(my), R, frames, bins, _ptr(bank.tidx if bank is not None else None),
-            _ptr(bank.tw if bank is not None else None), n // frames, eps, _ptr(sums), 1 if per_example_sc else 0,
-            w_sc / (nres * R) if per_example_sc else w_sc / nres, w_lm / (nres * R * n), w_lin / (nres * R * n), _ptr(gup), _ptr(G),
-            _stream()), "rfx_stft_scaled_loss_grad")
+        launch("rfx_stft_scaled_loss_grad",
+               X, mx, my, R, frames, bins, bank.tidx if bank is not None else None,
+               bank.tw if bank is not None else None, n // frames, eps, sums, 1 if per_example_sc else 0,
+               w_sc / (nres * R) if per_example_sc else w_sc / nres, w_lm / (nres * R * n), w_lin / (nres * R * n), gup, G)
         d = stft._desc(R, L, n_fft, hop, win, bins, 0, frames, _SPEC_MODE, in_mode=0, herm=0, scale=1.0, accum=1 if ires else 0)
-        check(_lib.lib().rfx_fft_synthesis(C.byref(d), _ptr(G), _ptr(stft.hann(win, g.device)), None, _ptr(stft.syn_ws(d, g.device)),
-                                           _ptr(gx), _stream()), "rfx_fft_synthesis")
+        launch("rfx_fft_synthesis", C.byref(d), G, stft.hann(win, g.device), None, stft.syn_ws(d, g.device), gx)
     ctx.saved = None
     return gx.view(shape)
 
@@ -296,8 +289,7 @@ class _MRSTFTFn(torch.autograd.Function):
                 if sums is None:
                     sums = torch.empty((R, 3), device=x.device, dtype=torch.float32)
                     ws = torch.empty(3 * R * 64, device=x.device, dtype=torch.float64)        # RFX_STFT_REDUCE_SLOTS per row
-                    check(_lib.lib().rfx_stft_loss_reduce(_ptr(X), _ptr(Y), R, n, eps, _ptr(ws), _ptr(sums), _stream()),
-                          "rfx_stft_loss_reduce")
+                    launch("rfx_stft_loss_reduce", X, Y, R, n, eps, ws, sums)
                     if _MEMO is not None and ("spec", X.data_ptr()) in _MEMO and ("spec", Y.data_ptr()) in _MEMO:
                         _MEMO[skey] = sums                               # both spectra are held by the memo: pointers stay valid
             saved.append((paired, X, Y, sums, n, n_fft, hop, win))
@@ -307,10 +299,9 @@ class _MRSTFTFn(torch.autograd.Function):
         for c0 in range(0, nres, 8):               # rfx_mrstft_combine takes up to 8 resolutions per launch (auraloss's default has 3)
             part, m = saved[c0:c0 + 8], len(saved[c0:c0 + 8])
             t = torch.empty((), device=x.device, dtype=torch.float32)
-            sp = (C.c_void_p * m)(*[_ptr(e[3]) for e in part])
+            sp = (C.c_void_p * m)(*[e[3].data_ptr() for e in part])
             nn_ = (C.c_int64 * m)(*[int(e[4]) for e in part])
-            check(_lib.lib().rfx_mrstft_combine(sp, nn_, m, R, 1 if per_example_sc else 0, _ptr(t), _stream()),
-                  "rfx_mrstft_combine")
+            launch("rfx_mrstft_combine", sp, nn_, m, R, 1 if per_example_sc else 0, t)
             total = t if nres <= 8 else (t * (m / nres) if total is None else total + t * (m / nres))
         ctx.saved = saved
         ctx.meta = (x.shape, R, L, eps, per_example_sc, nres)
@@ -337,19 +328,11 @@ class _MRSTFTFn(torch.autograd.Function):
             d = stft._desc(R, L, n_fft, hop, win, X.shape[2], 0, X.shape[1], _SPEC_MODE, in_mode=0, herm=0, scale=1.0,
                            accum=1 if ires else 0)
             if paired and FUSED_GRAD:   # Y = the clamped target magnitudes; the gradient spectrum is formed inside the synthesis
-                check(_lib.lib().rfx_fft_synthesis_lossgrad(C.byref(d), _ptr(X), _ptr(Y), _ptr(sums), w_sc, w_lm, eps, _ptr(gup),
-                                                            _ptr(w), _ptr(stft.syn_ws(d, g.device)), _ptr(gx), _stream()),
-                      "rfx_fft_synthesis_lossgrad")
+                launch("rfx_fft_synthesis_lossgrad", C.byref(d), X, Y, sums, w_sc, w_lm, eps, gup, w, stft.syn_ws(d, g.device), gx)
                 continue
             G = torch.empty_like(X)
-            if paired:
-                check(_lib.lib().rfx_stft_loss_grad_m(_ptr(X), _ptr(Y), R, n, eps, _ptr(sums), w_sc, w_lm, _ptr(gup), _ptr(G),
-                                                      _stream()), "rfx_stft_loss_grad_m")
-            else:
-                check(_lib.lib().rfx_stft_loss_grad(_ptr(X), _ptr(Y), R, n, eps, _ptr(sums), w_sc, w_lm, _ptr(gup), _ptr(G),
-                                                    _stream()), "rfx_stft_loss_grad")
-            check(_lib.lib().rfx_fft_synthesis(C.byref(d), _ptr(G), _ptr(w), None, _ptr(stft.syn_ws(d, g.device)), _ptr(gx), _stream()),
-                  "rfx_fft_synthesis")
+            launch("rfx_stft_loss_grad_m" if paired else "rfx_stft_loss_grad", X, Y, R, n, eps, sums, w_sc, w_lm, gup, G)
+            launch("rfx_fft_synthesis", C.byref(d), G, w, None, stft.syn_ws(d, g.device), gx)
         ctx.saved = None
         return (gx.view(shape),) + (None,) * (6 + ctx.n_extra)
 
@@ -448,7 +431,7 @@ class _L1Fn(torch.autograd.Function):
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty((), device=a.device, dtype=torch.float32)
         ws = torch.empty(512, device=a.device, dtype=torch.float64)                 # RFX_L1_SLOTS per-workgroup partials
-        check(_lib.lib().rfx_l1_sum(_ptr(a), _ptr(b), a.numel(), _ptr(ws), 1.0 / a.numel(), _ptr(out), _stream()), "rfx_l1_sum")
+        launch("rfx_l1_sum", a, b, a.numel(), ws, 1.0 / a.numel(), out)
         ctx.save_for_backward(a, b)
         return out
 
@@ -457,8 +440,7 @@ class _L1Fn(torch.autograd.Function):
         a, b = ctx.saved_tensors
         ga = torch.empty_like(a)
         gup = g.detach().reshape(1).float().contiguous()          # upstream scalar gradient, multiplied in on the device (no host sync)
-        check(_lib.lib().rfx_l1_grad(_ptr(a), _ptr(b), a.numel(), 1.0 / a.numel(), _ptr(gup), _ptr(ga), _stream()),
-              "rfx_l1_grad")
+        launch("rfx_l1_grad", a, b, a.numel(), 1.0 / a.numel(), gup, ga)
         return ga, None
 
 
@@ -514,26 +496,23 @@ class _TimeLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, target, kind, zero_mean, eps, reduction, taps, a):
         x, t, R, L = _rows(input, target)
-        dev, L_ = x.device, _lib.lib()
+        dev = x.device
         k, red = TIME_KINDS[kind], REDUCTIONS[reduction]
         h = taps if taps is not None else (0.0, 1.0, 0.0)
         need = ctx.needs_input_grad[0]
         if kind == "logcosh":
             s = torch.empty((R,), device=dev, dtype=torch.float64)
-            ws = torch.empty(int(L_.rfx_logcosh_ws(R, L)), device=dev, dtype=torch.float64)      # one slot per workgroup
-            check(L_.rfx_logcosh_rows(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), float(a), float(eps), _ptr(ws), _ptr(s),
-                                      _stream()), "rfx_logcosh_rows")
+            ws = torch.empty(query("rfx_logcosh_ws", R, L), device=dev, dtype=torch.float64)      # one slot per workgroup
+            launch("rfx_logcosh_rows", x, t, R, L, x.stride(0), t.stride(0), float(a), float(eps), ws, s)
             coef = None
         else:
             s = torch.empty((R, 5), device=dev, dtype=torch.float64)                            # written, not accumulated: no zero fill
-            ws = torch.empty(int(L_.rfx_time_sums_ws(R, L)), device=dev, dtype=torch.float64)
-            check(L_.rfx_time_sums(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), 1 if taps is not None else 0, h[0], h[1], h[2],
-                                   _ptr(ws), _ptr(s), _stream()), "rfx_time_sums")
+            ws = torch.empty(query("rfx_time_sums_ws", R, L), device=dev, dtype=torch.float64)
+            launch("rfx_time_sums", x, t, R, L, x.stride(0), t.stride(0), 1 if taps is not None else 0, h[0], h[1], h[2], ws, s)
             coef = torch.empty((R, 3), device=dev, dtype=torch.float64) if need else None
         rows = torch.empty((R,), device=dev, dtype=torch.float32)
         out = torch.empty((), device=dev, dtype=torch.float32) if reduction != "none" else None
-        check(L_.rfx_time_loss_rows(_ptr(s), R, L, k, 1 if zero_mean else 0, float(eps), red, _ptr(rows), _ptr(coef), _ptr(out),
-                                    _stream()), "rfx_time_loss_rows")
+        launch("rfx_time_loss_rows", s, R, L, k, 1 if zero_mean else 0, float(eps), red, rows, coef, out)
         if need:
             ctx.save_for_backward(x, t, coef)
             ctx.meta = (input.shape, R, L, kind, red, taps, h, float(a), float(eps))
@@ -546,12 +525,10 @@ class _TimeLossFn(torch.autograd.Function):
         gx = torch.empty((R, L), device=x.device, dtype=torch.float32)
         gup = g.detach().reshape(-1).float().contiguous()                 # 1 value (mean / sum) or R (none); stays on the device
         if kind == "logcosh":
-            check(_lib.lib().rfx_logcosh_grad(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), a, eps, _ptr(gup), red, _ptr(gx),
-                                              _stream()), "rfx_logcosh_grad")
+            launch("rfx_logcosh_grad", x, t, R, L, x.stride(0), t.stride(0), a, eps, gup, red, gx)
         else:
-            check(_lib.lib().rfx_time_loss_grad(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), _ptr(coef),
-                                                1 if taps is not None else 0, h[0], h[1], h[2], _ptr(gup), red, _ptr(gx), _stream()),
-                  "rfx_time_loss_grad")
+            launch("rfx_time_loss_grad", x, t, R, L, x.stride(0), t.stride(0), coef, 1 if taps is not None else 0, h[0], h[1], h[2],
+                   gup, red, gx)
         return (gx.view(shape),) + (None,) * 7
 
 
@@ -595,11 +572,9 @@ class SISDRLoss(_TimeLoss):
         R = x.shape[0]
         s = torch.empty((R, 5), device=x.device, dtype=torch.float64)
         ws = torch.empty(5 * R * 128, device=x.device, dtype=torch.float64)          # RFX_SISDR_SLOTS per-workgroup partials per row
-        check(_lib.lib().rfx_sisdr_sums(_ptr(x), _ptr(t), R, L, x.stride(0), t.stride(0), _ptr(ws), _ptr(s), _stream()),
-              "rfx_sisdr_sums")
+        launch("rfx_sisdr_sums", x, t, R, L, x.stride(0), t.stride(0), ws, s)
         out = torch.empty((), device=x.device, dtype=torch.float32)      # the scalar tail in one launch (fp64 inside)
-        check(_lib.lib().rfx_sisdr_finish(_ptr(s), R, L, 1 if self.zero_mean else 0, float(self.eps), _ptr(out), _stream()),
-              "rfx_sisdr_finish")
+        launch("rfx_sisdr_finish", s, R, L, 1 if self.zero_mean else 0, float(self.eps), out)
         return out
 
 
@@ -717,9 +692,8 @@ def _fir_launch(sigs, h, flip):
     R, L = rows[0].shape
     outs = [torch.empty((R, L), device=r.device, dtype=torch.float32) for r in rows]
     x2, y2 = (rows[1], outs[1]) if len(rows) == 2 else (None, None)
-    check(_lib.lib().rfx_fir_same(_ptr(rows[0]), _ptr(outs[0]), _ptr(x2), _ptr(y2), R, L, rows[0].stride(0), L,
-                                  x2.stride(0) if x2 is not None else 0, L, _ptr(h), h.numel(), 1 if flip else 0, _stream()),
-          "rfx_fir_same")
+    launch("rfx_fir_same", rows[0], outs[0], x2, y2, R, L, rows[0].stride(0), L, x2.stride(0) if x2 is not None else 0, L, h, h.numel(),
+           1 if flip else 0)
     return [o.view(s.shape) for o, s in zip(outs, sigs)]
 
 
@@ -800,8 +774,7 @@ class _SumDiffFn(torch.autograd.Function):
         t = target if target.stride(-1) == 1 else target.contiguous()
         B, _, T = x.shape
         s_in, d_in, s_tg, d_tg = (torch.empty((B, 1, T), device=x.device, dtype=torch.float32) for _ in range(4))
-        check(_lib.lib().rfx_sum_diff(_ptr(x), _ptr(s_in), _ptr(d_in), _ptr(t), _ptr(s_tg), _ptr(d_tg), B, T, x.stride(0), x.stride(1),
-                                      t.stride(0), t.stride(1), _stream()), "rfx_sum_diff")
+        launch("rfx_sum_diff", x, s_in, d_in, t, s_tg, d_tg, B, T, x.stride(0), x.stride(1), t.stride(0), t.stride(1))
         ctx.mark_non_differentiable(s_tg, d_tg)
         return s_in, d_in, s_tg, d_tg
 
@@ -809,7 +782,7 @@ class _SumDiffFn(torch.autograd.Function):
     def backward(ctx, gs, gd, _gs_tg, _gd_tg):
         B, _, T = gs.shape
         gx = torch.empty((B, 2, T), device=gs.device, dtype=torch.float32)
-        check(_lib.lib().rfx_sum_diff_adj(_ptr(gs.contiguous()), _ptr(gd.contiguous()), _ptr(gx), B, T, _stream()), "rfx_sum_diff_adj")
+        launch("rfx_sum_diff_adj", gs.contiguous(), gd.contiguous(), gx, B, T)
         return gx, None
 
 

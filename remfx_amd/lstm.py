@@ -11,32 +11,28 @@ Layout: sequences are channel-major ``(1, C, T*Bn)`` with position ``p = t*Bn + 
   * dX, dW_ih (+ bias row) are the conv dgrad / wgrad plans, and dW_hh is a wgrad whose input operand is
     the layer's own output shifted by one time step (convplan.shift_plan, +-Bn positions).
 """
-import ctypes as C
-
 import torch
 import torch.nn.functional as F
 
-from . import _lib, convplan, ops
-from ._lib import check
-from .ops import _ptr, _stream
+from . import convplan, ops
+from .ops import launch, query
 
 
 def _pack_whh(w_hh, w_hh_r, Bn, train):
     H = w_hh.shape[1]
-    L = _lib.lib()
-    nb = L.rfx_lstm_pack_bytes(H)
+    nb = query("rfx_lstm_pack_bytes", H)
     if nb <= 0:
         raise ValueError(f"LSTM hidden size {H} unsupported (multiple of 32, <= 512)")
     pack = torch.empty(2 * nb, device=w_hh.device, dtype=torch.uint8)
     # the single-workgroup form (csrc/lstm.hip) has its own fragment order: packed only for the shapes that take it
-    fwd_l, bwd_l = L.rfx_lstm_local(H, Bn, ops.GEMM_PREC, 0), (train and L.rfx_lstm_local(H, Bn, ops.GEMM_PREC, 1))
+    fwd_l, bwd_l = query("rfx_lstm_local", H, Bn, ops.GEMM_PREC, 0), (train and query("rfx_lstm_local", H, Bn, ops.GEMM_PREC, 1))
     for d, w in enumerate((w_hh, w_hh_r)):
         wc = w.contiguous()
-        dst = C.c_void_p(pack.data_ptr() + d * nb)
+        dst = pack.data_ptr() + d * nb
         if not (fwd_l and (bwd_l or not train)):           # some sweep still runs the cluster form
-            check(L.rfx_lstm_pack(_ptr(wc), H, dst, _stream()), "rfx_lstm_pack")
+            launch("rfx_lstm_pack", wc, H, dst)
         if fwd_l or bwd_l:
-            check(L.rfx_lstm_pack_local(_ptr(wc), H, dst, _stream()), "rfx_lstm_pack_local")
+            launch("rfx_lstm_pack_local", wc, H, dst)
     return pack
 
 
@@ -50,7 +46,7 @@ def _workspace(device, H):
     key = (device.index, H, ops.raw_stream())
     ws = _WS.get(key)
     if ws is None:
-        nb = _lib.lib().rfx_lstm_ws_bytes(H)
+        nb = query("rfx_lstm_ws_bytes", H)
         if nb <= 0:
             raise ValueError(f"LSTM hidden size {H} unsupported (multiple of 32, <= 512)")
         ws = torch.zeros(nb, device=device, dtype=torch.uint8)
@@ -89,8 +85,7 @@ class _LSTMLayerFn(torch.autograd.Function):
         if x.is_cuda and all(t.is_contiguous() and t.dtype == torch.float32 for t in (w_ih, w_ih_r, b_ih, b_hh, b_ih_r, b_hh_r)):
             wcat = torch.empty((8 * H, Cin, 1, 1), device=x.device, dtype=torch.float32)     # one launch instead of 2 cat + 2 add
             bcat = torch.empty((8 * H,), device=x.device, dtype=torch.float32)
-            check(_lib.lib().rfx_lstm_cat_params(_ptr(w_ih), _ptr(w_ih_r), _ptr(b_ih), _ptr(b_hh), _ptr(b_ih_r), _ptr(b_hh_r), H, Cin,
-                                                 _ptr(wcat), _ptr(bcat), _stream()), "rfx_lstm_cat_params")
+            launch("rfx_lstm_cat_params", w_ih, w_ih_r, b_ih, b_hh, b_ih_r, b_hh_r, H, Cin, wcat, bcat)
         else:
             wcat = torch.cat([w_ih, w_ih_r]).view(8 * H, Cin, 1, 1)
             bcat = torch.cat([b_ih + b_hh, b_ih_r + b_hh_r])
@@ -100,9 +95,7 @@ class _LSTMLayerFn(torch.autograd.Function):
         out = torch.empty((1, 2 * H, P), device=x.device, dtype=torch.float32)
         gates = torch.empty((2, 4 * H, P), device=x.device, dtype=torch.float32) if need else None
         cst = torch.empty((2, H, P), device=x.device, dtype=torch.float32) if need else None
-        check(_lib.lib().rfx_lstm_fwd(_ptr(xp), _ptr(pack), T, Bn, H, _ptr(out), _ptr(gates), _ptr(cst),
-                                      _ptr(_workspace(x.device, H)), ops.GEMM_PREC, _stream()),
-              "rfx_lstm_fwd")
+        launch("rfx_lstm_fwd", xp, pack, T, Bn, H, out, gates, cst, _workspace(x.device, H), ops.GEMM_PREC)
         ctx.prec = ops.GEMM_PREC
         if need:
             ctx.save_for_backward(x, wcat, pack, gates, cst, out)
@@ -117,9 +110,7 @@ class _LSTMLayerFn(torch.autograd.Function):
         P = T * Bn
         g = g.contiguous()
         dG = torch.empty((1, 8 * H, 1, P), device=g.device, dtype=torch.float32)
-        check(_lib.lib().rfx_lstm_bwd(_ptr(g), _ptr(pack), _ptr(gates), _ptr(cst), T, Bn, H, _ptr(dG),
-                                      _ptr(_workspace(g.device, H)), ctx.prec, _stream()),
-              "rfx_lstm_bwd")
+        launch("rfx_lstm_bwd", g, pack, gates, cst, T, Bn, H, dG, _workspace(g.device, H), ctx.prec)
         x4 = x.unsqueeze(2)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -148,8 +139,7 @@ class _LSTMLayerFn(torch.autograd.Function):
             grads = (dwcat[:4 * H], dwhh[0], db0, db0, dwcat[4 * H:], dwhh[1], db1, db1)
             if sunk:                         # one launch instead of six add_ into the flat gradient buffer's views
                 v = sw.grads
-                check(_lib.lib().rfx_lstm_grad_scatter(_ptr(dwcat), _ptr(dbcat), H, Cin, _ptr(v[0]), _ptr(v[4]), _ptr(v[2]), _ptr(v[3]),
-                                                       _ptr(v[6]), _ptr(v[7]), _stream()), "rfx_lstm_grad_scatter")
+                launch("rfx_lstm_grad_scatter", dwcat, dbcat, H, Cin, v[0], v[4], v[2], v[3], v[6], v[7])
         if sunk:
             return (dx,) + (None,) * 10
         return (dx,) + grads + (None, None)

@@ -11,9 +11,8 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import _lib, ops
-from ._lib import check
-from .ops import _ptr, _stream
+from . import ops
+from .ops import launch, query
 
 INTERIM = set()
 
@@ -51,15 +50,13 @@ class _GroupNormFn(torch.autograd.Function):
         given = (sums.shape[1] if sums.dim() == 3 else 1) if sums is not None else 0     # number of partial-sum slots
         if sums is None:
             # the statistics kernel stores one pair per (group, chunk) into its own slot: no zero fill, no atomics
-            chunks = int(_lib.lib().rfx_groupnorm_stat_chunks(Cc, S, groups))
+            chunks = query("rfx_groupnorm_stat_chunks", Cc, S, groups)
             sums = torch.empty(N * groups * 2 * max(chunks, 1), device=x.device, dtype=torch.float64)
             given = -1
         if res is not None:
             res = res.contiguous()
-        fwd = _lib.lib().rfx_groupnorm_fwd_x16 if x16 else _lib.lib().rfx_groupnorm_fwd
-        check(fwd(_ptr(x), _ptr(gamma), _ptr(beta), N, Cc, S, groups, eps, mode,
-                  _ptr(res), _ptr(scale), _ptr(sums), given, _ptr(mean), _ptr(rstd), _ptr(y), _stream()),
-              "rfx_groupnorm_fwd")
+        launch("rfx_groupnorm_fwd_x16" if x16 else "rfx_groupnorm_fwd", x, gamma, beta, N, Cc, S, groups, eps, mode,
+               res, scale, sums, given, mean, rstd, y)
         ctx.save_for_backward(x, gamma, beta, mean, rstd, scale)
         ctx.cfg = (N, Cc, S, groups, mode)
         return y
@@ -78,13 +75,10 @@ class _GroupNormFn(torch.autograd.Function):
         else:
             dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
             dscale = torch.empty_like(scale) if mode == 3 else None
-        gsum = torch.empty(int(_lib.lib().rfx_norm_bwd_work_floats(N, Cc, S, groups)), device=x.device, dtype=torch.float32)
-        bwd = _lib.lib().rfx_groupnorm_bwd_x16 if x.dtype == torch.bfloat16 else _lib.lib().rfx_groupnorm_bwd
+        gsum = torch.empty(query("rfx_norm_bwd_work_floats", N, Cc, S, groups), device=x.device, dtype=torch.float32)
         with sw or ops.NO_SINK:
-            check(bwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(gy),
-                      N, Cc, S, groups, mode, _ptr(scale), _ptr(gsum), _ptr(dx),
-                      _ptr(dgamma), _ptr(dbeta), _ptr(dscale), _stream()),
-                  "rfx_groupnorm_bwd")
+            launch("rfx_groupnorm_bwd_x16" if x.dtype == torch.bfloat16 else "rfx_groupnorm_bwd", x, gamma, beta, mean, rstd, gy,
+                   N, Cc, S, groups, mode, scale, gsum, dx, dgamma, dbeta, dscale)
         if sw is not None:
             return dx, None, None, None, None, None, (gy if mode == 3 else None), None, None
         return dx, dgamma, dbeta, None, None, None, (gy if mode == 3 else None), dscale, None
@@ -111,15 +105,13 @@ class _BatchNormFn(torch.autograd.Function):
         if training:
             mean = torch.empty(Cc, device=x.device, dtype=torch.float32)
             rstd = torch.empty_like(mean)
-            sums = torch.empty(Cc * 2 * int(_lib.lib().rfx_batchnorm_stat_slots(N, S)), device=x.device, dtype=torch.float64)
+            sums = torch.empty(Cc * 2 * query("rfx_batchnorm_stat_slots", N, S), device=x.device, dtype=torch.float64)
             given = 0
         else:
             mean = running_mean.contiguous()
             rstd = torch.rsqrt(running_var + eps)
             sums, given = None, 1
-        check(_lib.lib().rfx_batchnorm_fwd(_ptr(x), _ptr(gamma), _ptr(beta), N, Cc, S, eps, mode, given,
-                                           _ptr(sums), _ptr(mean), _ptr(rstd), _ptr(y), _stream()),
-              "rfx_batchnorm_fwd")
+        launch("rfx_batchnorm_fwd", x, gamma, beta, N, Cc, S, eps, mode, given, sums, mean, rstd, y)
         if training and running_mean is not None:
             with torch.no_grad():              # C-length vectors: bookkeeping, nn.BatchNorm2d semantics
                 n = N * S
@@ -139,10 +131,8 @@ class _BatchNormFn(torch.autograd.Function):
         gy = gy.contiguous()
         dx = torch.empty_like(x)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        work = torch.empty(int(_lib.lib().rfx_norm_bwd_work_floats(N, Cc, S, 0)), device=x.device, dtype=torch.float32)
-        check(_lib.lib().rfx_batchnorm_bwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(gy),
-                                           N, Cc, S, mode, _ptr(work), _ptr(dx), _ptr(dgamma), _ptr(dbeta),
-                                           _stream()), "rfx_batchnorm_bwd")
+        work = torch.empty(query("rfx_norm_bwd_work_floats", N, Cc, S, 0), device=x.device, dtype=torch.float32)
+        launch("rfx_batchnorm_bwd", x, gamma, beta, mean, rstd, gy, N, Cc, S, mode, work, dx, dgamma, dbeta)
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -161,7 +151,7 @@ class _AvgPoolFn(torch.autograd.Function):
         x = x.contiguous()
         N, Cc, H, W = x.shape
         y = torch.empty((N, Cc, H // kh, W // kw), device=x.device, dtype=torch.float32)
-        check(_lib.lib().rfx_avgpool2d_fwd(_ptr(x), _ptr(y), N * Cc, H, W, kh, kw, _stream()), "rfx_avgpool2d_fwd")
+        launch("rfx_avgpool2d_fwd", x, y, N * Cc, H, W, kh, kw)
         ctx.cfg = (N, Cc, H, W, kh, kw)
         return y
 
@@ -169,8 +159,7 @@ class _AvgPoolFn(torch.autograd.Function):
     def backward(ctx, gy):
         N, Cc, H, W, kh, kw = ctx.cfg
         gx = torch.empty((N, Cc, H, W), device=gy.device, dtype=torch.float32)
-        check(_lib.lib().rfx_avgpool2d_bwd(_ptr(gy.contiguous()), _ptr(gx), N * Cc, H, W, kh, kw, _stream()),
-              "rfx_avgpool2d_bwd")
+        launch("rfx_avgpool2d_bwd", gy.contiguous(), gx, N * Cc, H, W, kh, kw)
         return gx, None, None
 
 
@@ -191,7 +180,7 @@ class _GluFn(torch.autograd.Function):
         shp = list(x.shape)
         shp[1] = Cc // 2
         y = torch.empty(shp, device=x.device, dtype=torch.float32)
-        check(_lib.lib().rfx_glu_fwd(_ptr(x), _ptr(y), N, Cc, S, _stream()), "rfx_glu_fwd")
+        launch("rfx_glu_fwd", x, y, N, Cc, S)
         ctx.save_for_backward(x)
         return y
 
@@ -201,7 +190,7 @@ class _GluFn(torch.autograd.Function):
         N, Cc = x.shape[0], x.shape[1]
         S = x.numel() // (N * Cc)
         gx = torch.empty_like(x)
-        check(_lib.lib().rfx_glu_bwd(_ptr(x), _ptr(gy.contiguous()), _ptr(gx), N, Cc, S, _stream()), "rfx_glu_bwd")
+        launch("rfx_glu_bwd", x, gy.contiguous(), gx, N, Cc, S)
         return gx
 
 
@@ -224,8 +213,7 @@ class _AddFn(torch.autograd.Function):
         out = torch.empty_like(x4)
         N, Cc, A, B = x4.shape
         ys = ye.stride()
-        check(_lib.lib().rfx_add_bcast(_ptr(x4), _ptr(ye), _ptr(out), N, Cc, A, B, ys[0], ys[1], ys[2], ys[3],
-                                       float(alpha), _stream()), "rfx_add_bcast")
+        launch("rfx_add_bcast", x4, ye, out, N, Cc, A, B, ys[0], ys[1], ys[2], ys[3], float(alpha))
         ctx.cfg = (tuple(y4.shape), tuple(x4.shape), alpha, y.dim())
         return out if x.dim() == 4 else out.squeeze(2)
 
@@ -275,9 +263,8 @@ class _DConvLayerFn(torch.autograd.Function):
             z16 = torch.empty((N, 2 * Cc, T), device=x.device, dtype=torch.bfloat16)
             a_out = torch.empty((N, H, T), device=x.device, dtype=torch.float32)
             stats = torch.empty((4, N), device=x.device, dtype=torch.float32)
-        check(_lib.lib().rfx_dconv_layer_fwd(_ptr(x), _ptr(out), N, Cc, T, dil, _ptr(w1), _ptr(b1), _ptr(g1w), _ptr(g1b),
-                                             _ptr(w2), _ptr(b2), _ptr(g2w), _ptr(g2b), _ptr(scale), float(eps), _ptr(h16),
-                                             _ptr(z16), _ptr(a_out), _ptr(stats), _stream()), "rfx_dconv_layer_fwd")
+        launch("rfx_dconv_layer_fwd", x, out, N, Cc, T, dil, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, float(eps), h16, z16, a_out,
+               stats)
         if fused_bwd:
             ctx.save_for_backward(x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale)
             ctx.cfg = (dil, float(eps), True)
@@ -294,15 +281,12 @@ class _DConvLayerFn(torch.autograd.Function):
         x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, h16, z16, a_out, stats = ctx.saved_tensors
         N, Cc, T = x.shape
         H = Cc // 4
-        L = _lib.lib()
         gy = gy.contiguous()
         # GroupNorm(1, 2C) + GLU + LayerScale backward (mode 3): dz (bf16), dgamma2 / dbeta2 / dscale; the residual passes gy on
         dz = torch.empty_like(z16)
         dg2w, dg2b, dscale = torch.empty_like(g2w), torch.empty_like(g2b), torch.empty_like(scale)
-        work = torch.empty(int(L.rfx_norm_bwd_work_floats(N, 2 * Cc, T, 1)), device=x.device, dtype=torch.float32)
-        check(L.rfx_groupnorm_bwd_x16(_ptr(z16), _ptr(g2w), _ptr(g2b), _ptr(stats[2]), _ptr(stats[3]), _ptr(gy), N, 2 * Cc, T, 1, 3,
-                                      _ptr(scale), _ptr(work), _ptr(dz), _ptr(dg2w), _ptr(dg2b), _ptr(dscale), _stream()),
-              "rfx_groupnorm_bwd")
+        work = torch.empty(query("rfx_norm_bwd_work_floats", N, 2 * Cc, T, 1), device=x.device, dtype=torch.float32)
+        launch("rfx_groupnorm_bwd_x16", z16, g2w, g2b, stats[2], stats[3], gy, N, 2 * Cc, T, 1, 3, scale, work, dz, dg2w, dg2b, dscale)
         # 1x1 convolution: da = W2^T dz;  dW2, db2
         w24 = w2.reshape(2 * Cc, H, 1, 1)
         a4, dz4 = a_out.unsqueeze(2), dz.unsqueeze(2)
@@ -311,9 +295,8 @@ class _DConvLayerFn(torch.autograd.Function):
         # GroupNorm(1, H) + GELU backward (mode 1): dh (bf16), dgamma1 / dbeta1
         dh = torch.empty_like(h16)
         dg1w, dg1b = torch.empty_like(g1w), torch.empty_like(g1b)
-        work1 = torch.empty(int(L.rfx_norm_bwd_work_floats(N, H, T, 1)), device=x.device, dtype=torch.float32)
-        check(L.rfx_groupnorm_bwd_x16(_ptr(h16), _ptr(g1w), _ptr(g1b), _ptr(stats[0]), _ptr(stats[1]), _ptr(da), N, H, T, 1, 1,
-                                      None, _ptr(work1), _ptr(dh), _ptr(dg1w), _ptr(dg1b), None, _stream()), "rfx_groupnorm_bwd")
+        work1 = torch.empty(query("rfx_norm_bwd_work_floats", N, H, T, 1), device=x.device, dtype=torch.float32)
+        launch("rfx_groupnorm_bwd_x16", h16, g1w, g1b, stats[0], stats[1], da, N, H, T, 1, 1, None, work1, dh, dg1w, dg1b, None)
         # dilated convolution: dx = W1^T * dh + gy (the residual rides in the GEMM's store);  dW1, db1
         w14 = w1.reshape(H, Cc, 1, 3)
         x4, dh4 = x.unsqueeze(2), dh.unsqueeze(2)
@@ -328,16 +311,13 @@ class _DConvLayerFn(torch.autograd.Function):
         x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale = ctx.saved_tensors
         N, Cc, T = x.shape
         H = Cc // 4
-        L = _lib.lib()
         gy = gy.contiguous()
         dx = torch.empty_like(x)
         dz = torch.empty((N, 2 * Cc, T), device=x.device, dtype=torch.bfloat16)
         a_out = torch.empty((N, H, T), device=x.device, dtype=torch.float32)
         dh = torch.empty((N, H, T), device=x.device, dtype=torch.bfloat16)
-        partial = torch.empty((L.rfx_dconv_layer_bwd_rows(N), 5 * Cc + 2 * H), device=x.device, dtype=torch.float32)
-        check(L.rfx_dconv_layer_bwd(_ptr(x), _ptr(gy), _ptr(dx), N, Cc, T, dil, _ptr(w1), _ptr(b1), _ptr(g1w), _ptr(g1b), _ptr(w2),
-                                    _ptr(b2), _ptr(g2w), _ptr(g2b), _ptr(scale), eps, _ptr(dz), _ptr(a_out), _ptr(dh), _ptr(partial),
-                                    _stream()), "rfx_dconv_layer_bwd")
+        partial = torch.empty((query("rfx_dconv_layer_bwd_rows", N), 5 * Cc + 2 * H), device=x.device, dtype=torch.float32)
+        launch("rfx_dconv_layer_bwd", x, gy, dx, N, Cc, T, dil, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, eps, dz, a_out, dh, partial)
         ps = partial.sum(0)
         dscale, dg2w, dg2b = ps[:Cc], ps[Cc:3 * Cc], ps[3 * Cc:5 * Cc]
         dg1w, dg1b = ps[5 * Cc:5 * Cc + H], ps[5 * Cc + H:]
@@ -363,7 +343,7 @@ def dconv_layer_fused_ok(x, hidden, kernel_size, dil, need_grad):
     if not DCONV_FUSED or ops.GEMM_PREC != 2 or x.dim() != 3 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
         return False
     Cc, T = x.shape[1], x.shape[2]
-    return hidden * 4 == Cc and kernel_size == 3 and bool(_lib.lib().rfx_dconv_layer_ok(Cc, T, dil))
+    return hidden * 4 == Cc and kernel_size == 3 and bool(query("rfx_dconv_layer_ok", Cc, T, dil))
 
 
 def dconv_layer(x, conv1, gn1, conv2, gn2, scale, dil):
@@ -380,7 +360,7 @@ class _MulFn(torch.autograd.Function):
         if a.shape != b.shape:
             raise ValueError("mul: equal shapes")
         y = torch.empty_like(a)
-        check(_lib.lib().rfx_mul(_ptr(a), _ptr(b), _ptr(y), a.numel(), _stream()), "rfx_mul")
+        launch("rfx_mul", a, b, y, a.numel())
         ctx.save_for_backward(a, b)
         return y
 
@@ -389,8 +369,8 @@ class _MulFn(torch.autograd.Function):
         a, b = ctx.saved_tensors
         g = g.contiguous()
         ga, gb = torch.empty_like(a), torch.empty_like(b)
-        check(_lib.lib().rfx_mul(_ptr(g), _ptr(b), _ptr(ga), a.numel(), _stream()), "rfx_mul")
-        check(_lib.lib().rfx_mul(_ptr(g), _ptr(a), _ptr(gb), a.numel(), _stream()), "rfx_mul")
+        launch("rfx_mul", g, b, ga, a.numel())
+        launch("rfx_mul", g, a, gb, a.numel())
         return ga, gb
 
 
@@ -402,18 +382,11 @@ def mul(a, b):
 def row_standardize(x, eps):
     """(x - mean) / (eps + std) over all dims but the first, unbiased std (HDemucs forward); x carries no
     gradient (it is the input waveform / its STFT).  Returns y, mean (R,), std (R,)."""
-    ops._req(x, "x")
     x = x.contiguous()
+    mean, std, a, b = row_moments(x, eps)
     R = x.shape[0]
-    L = x.numel() // R
-    lib = _lib.lib()
-    sums = torch.empty(2 * R * lib.rfx_row_moments_slots(L), device=x.device, dtype=torch.float64)    # one slot per workgroup
-    mean = torch.empty(R, device=x.device, dtype=torch.float32)
-    std, a, b = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-    check(lib.rfx_row_moments(_ptr(x), R, L, _ptr(sums), _ptr(mean), _ptr(std), float(eps), _ptr(a), _ptr(b), _stream()),
-          "rfx_row_moments")                                   # a = 1 / (eps + std), b = -mean a come out of the finalize kernel
     y = torch.empty_like(x)
-    check(_lib.lib().rfx_row_affine(_ptr(x), _ptr(a), _ptr(b), _ptr(y), R, L, _stream()), "rfx_row_affine")
+    launch("rfx_row_affine", x, a, b, y, R, x.numel() // R)
     return y, mean, std
 
 
@@ -423,7 +396,7 @@ class _RowAffineFn(torch.autograd.Function):
         x = x.contiguous()
         R = x.shape[0]
         y = torch.empty_like(x)
-        check(_lib.lib().rfx_row_affine(_ptr(x), _ptr(a), _ptr(b), _ptr(y), R, x.numel() // R, _stream()), "rfx_row_affine")
+        launch("rfx_row_affine", x, a, b, y, R, x.numel() // R)
         ctx.save_for_backward(a)
         return y
 
@@ -433,7 +406,7 @@ class _RowAffineFn(torch.autograd.Function):
         g = g.contiguous()
         R = g.shape[0]
         gx = torch.empty_like(g)
-        check(_lib.lib().rfx_row_affine(_ptr(g), _ptr(a), None, _ptr(gx), R, g.numel() // R, _stream()), "rfx_row_affine")
+        launch("rfx_row_affine", g, a, None, gx, R, g.numel() // R)
         return gx, None, None
 
 
@@ -444,53 +417,35 @@ def row_moments(x, eps):
     x = x.contiguous()
     R = x.shape[0]
     L = x.numel() // R
-    lib = _lib.lib()
-    sums = torch.empty(2 * R * lib.rfx_row_moments_slots(L), device=x.device, dtype=torch.float64)
+    sums = torch.empty(2 * R * query("rfx_row_moments_slots", L), device=x.device, dtype=torch.float64)    # one slot per workgroup
     mean = torch.empty(R, device=x.device, dtype=torch.float32)
     std, a, b = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-    check(lib.rfx_row_moments(_ptr(x), R, L, _ptr(sums), _ptr(mean), _ptr(std), float(eps), _ptr(a), _ptr(b), _stream()), "rfx_row_moments")
+    launch("rfx_row_moments", x, R, L, sums, mean, std, float(eps), a, b)     # a = 1 / (eps + std), b = -mean a: the finalize kernel
     return mean, std, a, b
 
 
+def _fm_cm_affine(x, y, a, b, N, group, bins, F, fwd):
+    """rfx_fm_cm_affine (one coefficient pair per row) or, for group > 1, rfx_fm_cm_affine_g."""
+    if group == 1:
+        launch("rfx_fm_cm_affine", x, y, a, b, N, bins, F, fwd)
+    else:
+        launch("rfx_fm_cm_affine_g", x, y, a, b, N, group, bins, F, fwd)
+
+
 class _CmToFmAffineFn(torch.autograd.Function):
-    """y[n][frame][bin][c] = x[n][c][bin][frame] a[n] + b[n]: HDemucs' de-standardisation fused with the layout change in front of the
-    frame-major inverse STFT (rfx_fm_cm_affine); the gradient reaches x only (a, b are detached statistics of the input)."""
-
-    @staticmethod
-    def forward(ctx, x, a, b):
-        ops._req(x, "x")
-        x = x.contiguous()
-        N, Cc, bins, F = x.shape
-        if Cc != 2 or x.dtype != torch.float32:
-            raise ValueError("cm_to_fm_affine: (N, 2, bins, frames) fp32")
-        y = torch.empty((N, F, bins, 2), device=x.device, dtype=torch.float32)
-        check(_lib.lib().rfx_fm_cm_affine(_ptr(x), _ptr(y), _ptr(a), _ptr(b), N, bins, F, 1, _stream()), "rfx_fm_cm_affine")
-        ctx.save_for_backward(a)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        (a,) = ctx.saved_tensors
-        g = g.contiguous()
-        N, F, bins, _ = g.shape
-        gx = torch.empty((N, 2, bins, F), device=g.device, dtype=torch.float32)
-        check(_lib.lib().rfx_fm_cm_affine(_ptr(g), _ptr(gx), _ptr(a), None, N, bins, F, 0, _stream()), "rfx_fm_cm_affine")
-        return gx, None, None
-
-
-class _CmToFmAffineGroupFn(torch.autograd.Function):
-    """_CmToFmAffineFn with one (a, b) pair per `group` consecutive rows (rfx_fm_cm_affine_g): the S * Cin rows of a multi-source
-    HDemucs clip share the clip's statistics."""
+    """y[n][frame][bin][c] = x[n][c][bin][frame] a[n / group] + b[n / group]: HDemucs' de-standardisation fused with the layout change
+    in front of the frame-major inverse STFT; the gradient reaches x only (a, b are detached statistics of the input).  `group`
+    consecutive rows share one (a, b) pair: the S * Cin rows of a multi-source HDemucs clip share the clip's statistics."""
 
     @staticmethod
     def forward(ctx, x, a, b, group):
         ops._req(x, "x")
         x = x.contiguous()
         N, Cc, bins, F = x.shape
-        if Cc != 2 or x.dtype != torch.float32 or N % group or a.numel() != N // group or b.numel() != N // group:
+        if Cc != 2 or x.dtype != torch.float32 or N % group or (group > 1 and (a.numel() != N // group or b.numel() != N // group)):
             raise ValueError(f"cm_to_fm_affine: (N, 2, bins, frames) fp32 with N / group = {N} / {group} coefficient pairs")
         y = torch.empty((N, F, bins, 2), device=x.device, dtype=torch.float32)
-        check(_lib.lib().rfx_fm_cm_affine_g(_ptr(x), _ptr(y), _ptr(a), _ptr(b), N, group, bins, F, 1, _stream()), "rfx_fm_cm_affine_g")
+        _fm_cm_affine(x, y, a, b, N, group, bins, F, 1)
         ctx.save_for_backward(a)
         ctx.group = group
         return y
@@ -501,15 +456,13 @@ class _CmToFmAffineGroupFn(torch.autograd.Function):
         g = g.contiguous()
         N, F, bins, _ = g.shape
         gx = torch.empty((N, 2, bins, F), device=g.device, dtype=torch.float32)
-        check(_lib.lib().rfx_fm_cm_affine_g(_ptr(g), _ptr(gx), _ptr(a), None, N, ctx.group, bins, F, 0, _stream()), "rfx_fm_cm_affine_g")
+        _fm_cm_affine(g, gx, a, None, N, ctx.group, bins, F, 0)
         return gx, None, None, None
 
 
 def cm_to_fm_affine(x, a, b, group=1):
     """(N, 2, bins, frames) -> (N, frames, bins, 2) times a plus b; `group` consecutive rows share one coefficient pair."""
-    if group == 1:
-        return _CmToFmAffineFn.apply(x, a.contiguous(), b.contiguous())
-    return _CmToFmAffineGroupFn.apply(x, a.contiguous(), b.contiguous(), int(group))
+    return _CmToFmAffineFn.apply(x, a.contiguous(), b.contiguous(), int(group))
 
 
 def row_affine(x, a, b):
@@ -531,8 +484,7 @@ class _RowAffineAddFn(torch.autograd.Function):
         if x.numel() != y.numel() or x.numel() % R or b.numel() != Q:
             raise ValueError(f"row_affine_add: x {tuple(x.shape)}, y {tuple(y.shape)} against {Q} coefficient pairs for groups of {group} rows")
         out = torch.empty_like(y)
-        check(_lib.lib().rfx_row_affine_add(_ptr(x), _ptr(a), _ptr(b), _ptr(y), _ptr(out), R, group, x.numel() // R, _stream()),
-              "rfx_row_affine_add")
+        launch("rfx_row_affine_add", x, a, b, y, out, R, group, x.numel() // R)
         ctx.save_for_backward(a)
         ctx.xshape = x.shape
         return out
@@ -546,7 +498,7 @@ class _RowAffineAddFn(torch.autograd.Function):
             Q = a.numel()
             gx = torch.empty(ctx.xshape, device=g.device, dtype=torch.float32)
             # the rows of a group are contiguous: one row of group * L samples per coefficient
-            check(_lib.lib().rfx_row_affine(_ptr(gc), _ptr(a), None, _ptr(gx), Q, gc.numel() // Q, _stream()), "rfx_row_affine")
+            launch("rfx_row_affine", gc, a, None, gx, Q, gc.numel() // Q)
         return gx, None, None, g, None
 
 
@@ -569,14 +521,12 @@ class _LocalStateFn(torch.autograd.Function):
         ch = Ctot // heads
         out = torch.empty_like(q)
         need_w = any(ctx.needs_input_grad[:4])
-        L = _lib.lib()
         # bf16 mode: MFMA kernels (attention_mfma.hip), weights recomputed in the backward pass instead of stored
-        mfma = ops.GEMM_PREC == 2 and bool(L.rfx_localstate_mfma_ok(B, heads, ch, T, ndecay))
+        mfma = ops.GEMM_PREC == 2 and bool(query("rfx_localstate_mfma_ok", B, heads, ch, T, ndecay))
         # more than 256 frames (whole files) or ch * T beyond the LDS-resident kernel: the streaming any-T kernels
         gen = not mfma and (T > 256 or ch * T > 12288 or ndecay > 8)
         if mfma:
-            check(L.rfx_localstate_mfma_fwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), B, heads, ch, T, ndecay, _ptr(out),
-                                            _stream()), "rfx_localstate_mfma_fwd")
+            launch("rfx_localstate_mfma_fwd", q, k, cont, qd, B, heads, ch, T, ndecay, out)
             if need_w:
                 ctx.save_for_backward(q, k, cont, qd)
         elif gen:
@@ -584,14 +534,12 @@ class _LocalStateFn(torch.autograd.Function):
                 raise ValueError(f"LocalState attention: {ch} channels per head / {ndecay} decay terms exceed the HIP kernels' "
                                  "limits (ch <= 104, ndecay <= 64)")
             stat = torch.empty((B * heads * T, 4), device=q.device, dtype=torch.float32)
-            check(L.rfx_localstate_gen_fwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), B, heads, ch, T, ndecay, _ptr(stat),
-                                           _ptr(out), _stream()), "rfx_localstate_gen_fwd")
+            launch("rfx_localstate_gen_fwd", q, k, cont, qd, B, heads, ch, T, ndecay, stat, out)
             if need_w:
                 ctx.save_for_backward(q, k, cont, qd, stat, out)
         else:
             w = torch.empty((B, heads, T, T), device=q.device, dtype=torch.float32) if need_w else None
-            check(L.rfx_localstate_fwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), B, heads, ch, T, ndecay, _ptr(w),
-                                       _ptr(out), _stream()), "rfx_localstate_fwd")
+            launch("rfx_localstate_fwd", q, k, cont, qd, B, heads, ch, T, ndecay, w, out)
             if need_w:
                 ctx.save_for_backward(q, k, cont, qd, w)
         ctx.cfg = (B, heads, ch, T, ndecay, mfma, gen)
@@ -605,19 +553,13 @@ class _LocalStateFn(torch.autograd.Function):
         dq, dk, dc, dqd = torch.empty_like(q), torch.empty_like(k), torch.empty_like(cont), torch.empty_like(qd)
         if mfma:
             stat = torch.empty((B * heads * T, 4), device=q.device, dtype=torch.float32)
-            check(_lib.lib().rfx_localstate_mfma_bwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), _ptr(g), B, heads, ch, T, ndecay,
-                                                     _ptr(dq), _ptr(dk), _ptr(dc), _ptr(dqd), _ptr(stat), _stream()),
-                  "rfx_localstate_mfma_bwd")
+            launch("rfx_localstate_mfma_bwd", q, k, cont, qd, g, B, heads, ch, T, ndecay, dq, dk, dc, dqd, stat)
         elif gen:
             stat, out = ctx.saved_tensors[4:6]
-            check(_lib.lib().rfx_localstate_gen_bwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), _ptr(stat), _ptr(out), _ptr(g), B,
-                                                    heads, ch, T, ndecay, _ptr(dq), _ptr(dk), _ptr(dc), _ptr(dqd), _stream()),
-                  "rfx_localstate_gen_bwd")
+            launch("rfx_localstate_gen_bwd", q, k, cont, qd, stat, out, g, B, heads, ch, T, ndecay, dq, dk, dc, dqd)
         else:
             w = ctx.saved_tensors[4]
-            check(_lib.lib().rfx_localstate_bwd(_ptr(q), _ptr(k), _ptr(cont), _ptr(qd), _ptr(w), _ptr(g), B, heads, ch, T,
-                                                ndecay, _ptr(dq), _ptr(dk), _ptr(dc), _ptr(dqd), _stream()),
-                  "rfx_localstate_bwd")
+            launch("rfx_localstate_bwd", q, k, cont, qd, w, g, B, heads, ch, T, ndecay, dq, dk, dc, dqd)
         return dq, dk, dc, dqd, None, None
 
 
@@ -635,7 +577,7 @@ class _BlstmFrameFn(torch.autograd.Function):
         x = x.contiguous()
         B, Cc, T = x.shape
         h = torch.empty((1, Cc, width * B * nfr), device=x.device, dtype=torch.float32)
-        check(_lib.lib().rfx_blstm_frames(_ptr(x), None, _ptr(h), B, Cc, T, nfr, width, stride, 0, _stream()), "rfx_blstm_frames")
+        launch("rfx_blstm_frames", x, None, h, B, Cc, T, nfr, width, stride, 0)
         ctx.cfg = (B, Cc, T, nfr, width, stride)
         return h
 
@@ -643,8 +585,7 @@ class _BlstmFrameFn(torch.autograd.Function):
     def backward(ctx, g):
         B, Cc, T, nfr, width, stride = ctx.cfg
         dx = torch.empty((B, Cc, T), device=g.device, dtype=torch.float32)
-        check(_lib.lib().rfx_blstm_frames(_ptr(g.contiguous()), None, _ptr(dx), B, Cc, T, nfr, width, stride, 1, _stream()),
-              "rfx_blstm_frames")
+        launch("rfx_blstm_frames", g.contiguous(), None, dx, B, Cc, T, nfr, width, stride, 1)
         return dx, None, None, None
 
 
@@ -658,8 +599,7 @@ class _BlstmUnframeFn(torch.autograd.Function):
         Cc = h.shape[1]
         out = torch.empty((B, Cc, T), device=h.device, dtype=torch.float32)
         sk = skip.contiguous() if skip is not None else None
-        check(_lib.lib().rfx_blstm_frames(_ptr(h), _ptr(sk), _ptr(out), B, Cc, T, nfr, width, stride, 2, _stream()),
-              "rfx_blstm_frames")
+        launch("rfx_blstm_frames", h, sk, out, B, Cc, T, nfr, width, stride, 2)
         ctx.cfg = (B, Cc, T, nfr, width, stride, skip is not None)
         return out
 
@@ -668,7 +608,7 @@ class _BlstmUnframeFn(torch.autograd.Function):
         B, Cc, T, nfr, width, stride, has_skip = ctx.cfg
         g = g.contiguous()
         dh = torch.empty((1, Cc, width * B * nfr), device=g.device, dtype=torch.float32)
-        check(_lib.lib().rfx_blstm_frames(_ptr(g), None, _ptr(dh), B, Cc, T, nfr, width, stride, 3, _stream()), "rfx_blstm_frames")
+        launch("rfx_blstm_frames", g, None, dh, B, Cc, T, nfr, width, stride, 3)
         return dh, (g if has_skip else None), None, None, None, None, None
 
 
@@ -688,7 +628,7 @@ class _DropoutFn(torch.autograd.Function):
         ops._req(x, "x")
         xc = x.contiguous()
         out = torch.empty_like(xc)
-        check(_lib.lib().rfx_dropout(_ptr(xc), _ptr(out), xc.numel(), float(p), int(seed), _stream()), "rfx_dropout")
+        launch("rfx_dropout", xc, out, xc.numel(), float(p), int(seed))
         ctx.cfg = (float(p), int(seed))
         return out
 
@@ -697,7 +637,7 @@ class _DropoutFn(torch.autograd.Function):
         p, seed = ctx.cfg
         gc = g.contiguous()
         dx = torch.empty_like(gc)
-        check(_lib.lib().rfx_dropout(_ptr(gc), _ptr(dx), gc.numel(), p, seed, _stream()), "rfx_dropout")
+        launch("rfx_dropout", gc, dx, gc.numel(), p, seed)
         return dx, None, None
 
 

@@ -262,27 +262,60 @@ def raw_stream():
     return _raw_stream(_cur_device())
 
 
-def _stream():
-    return C.c_void_p(_raw_stream(_cur_device()))
+_Tensor, _ndarray = torch.Tensor, np.ndarray
+_PLAIN = frozenset((int, float, type(None)))       # most arguments of a launch: one hash lookup, then the isinstance chain
 
 
+def _native(args):
+    """The one argument rule of every native call: a tensor goes as its device address, a numpy array as its host address (plain
+    ints: a `void *` parameter takes them), everything else -- None (the null pointer), numbers, C.byref(desc), ctypes values --
+    as it is.  One pass, no ctypes object per argument: ~920 launches per Demucs step go through here."""
+    return [a if type(a) in _PLAIN else a.data_ptr() if isinstance(a, _Tensor) else a.ctypes.data if isinstance(a, _ndarray) else a
+            for a in args]
+
+
+def launch_rc(name, *args):
+    """Call the library's entry point `name` with `args` (see _native) and the current stream as the last argument; the code it
+    returns.  `args` holds every tensor until the call has returned: the pointer of a temporary (`g.contiguous()`) stays valid, and
+    its block is not handed to the next allocation before the launch is queued behind it.  The library (`_lib.lib`) and the
+    stream (`ops.raw_stream`) are looked up at call time: these are the two seams tests and tracing tools replace."""
+    return getattr(_lib.lib(), name)(*_native(args), raw_stream())
+
+
+def launch(name, *args):
+    """launch_rc that raises on a nonzero code, naming the symbol: how every kernel of the package is launched."""
+    rc = getattr(_lib.lib(), name)(*_native(args), raw_stream())
+    if rc:
+        check(rc, name)
+
+
+def query(name, *args):
+    """The host-only entry point `name` (no stream: workspace sizes, slot counts, `*_ok`, `*_variant`) -> int."""
+    return int(getattr(_lib.lib(), name)(*_native(args)))
+
+
+# Spelling an ABI call by hand -- `lib.rfx_x(_ptr(a), n, _stream())`, no helper in between -- is what the per-element kernel tests
+# and the probes under scripts/ do on purpose: they call the entry point under test directly and judge its return code
+# themselves.  These two spell its pointer and stream arguments; nothing in the package calls them (launch is the way in), and
+# `_stream` reads the one stream seam, `raw_stream`.
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def zeros(shape, device, dtype=torch.float32):
-    """torch.zeros on the GPU through rfx_zero (one launch at HBM rate on the current stream)."""
-    t = torch.empty(shape, device=device, dtype=dtype)
-    if t.numel():
-        check(_lib.lib().rfx_zero(_ptr(t), t.numel() * t.element_size(), _stream()), "rfx_zero")
-    return t
+def _stream():
+    return C.c_void_p(raw_stream())
 
 
 def zero_(t):
-    """t.zero_() for a contiguous GPU tensor of a 4- or 8-byte type."""
+    """t.zero_() for a contiguous GPU tensor of a 4- or 8-byte type (one launch at HBM rate on the current stream)."""
     if t.numel():
-        check(_lib.lib().rfx_zero(_ptr(t), t.numel() * t.element_size(), _stream()), "rfx_zero")
+        launch("rfx_zero", t, t.numel() * t.element_size())
     return t
+
+
+def zeros(shape, device, dtype=torch.float32):
+    """torch.zeros on the GPU through rfx_zero."""
+    return zero_(torch.empty(shape, device=device, dtype=dtype))
 
 
 def _req(t, name="tensor"):
@@ -351,12 +384,10 @@ def pack_a(dp, w, out=None):
     prec = dp.fwd_prec()
     if prec == 0:
         apack = out if out is not None else torch.empty((p.Kpad + 64, p.Mpad), device=w.device, dtype=torch.float32)
-        check(_lib.lib().rfx_pack_a(_ptr(w), _ptr(dp.woff), p.w_ms, p.M, p.extra["n_weight_rows"], p.Mpad, p.Kpad, 0,
-                                    _ptr(apack), _stream()), "rfx_pack_a")
+        launch("rfx_pack_a", w, dp.woff, p.w_ms, p.M, p.extra["n_weight_rows"], p.Mpad, p.Kpad, 0, apack)
     else:                                       # tap-major order, bf16 hi / lo cells: 2 x [Kpad_t / 8 + 8][Mpad] x 16 bytes
         apack = out if out is not None else torch.empty((p.Kpad_t + 64, p.Mpad), device=w.device, dtype=torch.float32)
-        check(_lib.lib().rfx_pack_a(_ptr(w), _ptr(dp.woff_t), p.w_ms, p.M, p.Kpad_t, p.Mpad, p.Kpad_t, prec,
-                                    _ptr(apack), _stream()), "rfx_pack_a")
+        launch("rfx_pack_a", w, dp.woff_t, p.w_ms, p.M, p.Kpad_t, p.Mpad, p.Kpad_t, prec, apack)
     return apack
 
 
@@ -473,9 +504,9 @@ def gemm_fwd(dp, apack, x, out, bias=None, act=None, act_param=None, res=None, a
         raise ValueError("two-phase gather-GEMM: both phases must use the same table form")
     tab = dp.tap_tab if prec else dp.ktab
     if dp2 is not None and prec:
-        a2, k2, K2, Kpad2 = _ptr(apack2), _ptr(dp2.tap_tab), dp2.p.ntaps, dp2.p.Kpad_t
+        a2, k2, K2, Kpad2 = apack2, dp2.tap_tab, dp2.p.ntaps, dp2.p.Kpad_t
     elif dp2 is not None:
-        a2, k2, K2, Kpad2 = _ptr(apack2), _ptr(dp2.ktab), dp2.p.K, dp2.p.Kpad
+        a2, k2, K2, Kpad2 = apack2, dp2.ktab, dp2.p.K, dp2.p.Kpad
     else:
         a2, k2, K2, Kpad2 = None, None, 0, 0
     if x.dtype == torch.bfloat16 and not (prec == 2 and dp.p.R > 0):
@@ -484,10 +515,8 @@ def gemm_fwd(dp, apack, x, out, bias=None, act=None, act_param=None, res=None, a
     if dp2 is not None and prec:
         desc.gpt2 = int(dp2.p.gpt)              # the second table's own channel blocking
     if TRACE_VARIANT is not None:               # measurement hook (bench.py): which kernel instantiation this launch is
-        TRACE_VARIANT.append(_lib.lib().rfx_gemm_fwd_variant(C.byref(desc), C.byref(e), int(dp2 is not None), prec))
-    check(_lib.lib().rfx_gemm_fwd(C.byref(desc), _ptr(apack), _ptr(tab), _ptr(x), _ptr(out),
-                                  C.byref(e), a2, k2, K2, Kpad2, _ptr(in2), prec, _stream()),
-          "rfx_gemm_fwd")
+        TRACE_VARIANT.append(query("rfx_gemm_fwd_variant", C.byref(desc), C.byref(e), int(dp2 is not None), prec))
+    launch("rfx_gemm_fwd", C.byref(desc), apack, tab, x, out, C.byref(e), a2, k2, K2, Kpad2, in2, prec)
     return out
 
 
@@ -514,42 +543,38 @@ def gemm_wgrad(dp, x, g):
     if x.dtype == torch.bfloat16:                            # bf16 storage is implemented for the gradient operand only
         x = x.float()
     if g.dtype == torch.bfloat16:
-        rc = _lib.lib().rfx_gemm_wgrad(C.byref(dp.desc_for(x, g)), _ptr(dp.ktab), _ptr(x), _ptr(g), _ptr(ws), cap, C.byref(ns),
-                                       GEMM_PREC, _stream())
+        rc = launch_rc("rfx_gemm_wgrad", C.byref(dp.desc_for(x, g)), dp.ktab, x, g, ws, cap, C.byref(ns), GEMM_PREC)
         if rc == 0:
             if TRACE_WGRAD is not None:
-                TRACE_WGRAD.append(_lib.lib().rfx_gemm_wgrad_variant(C.byref(dp.desc_for(x, g)), cap, GEMM_PREC))
+                TRACE_WGRAD.append(query("rfx_gemm_wgrad_variant", C.byref(dp.desc_for(x, g)), cap, GEMM_PREC))
             return WgradOut(ws, ns.value)
         if rc != -1:                                         # -1 = "plan not supported by the 16-bit path"; anything else is a real failure
-            check(rc, "rfx_gemm_wgrad")
+            raise RuntimeError(f"rfx_gemm_wgrad failed with code {rc}")
         if TRACE_WGRAD is not None:
             TRACE_WGRAD.append(-1)                           # refused: the retry below is the launch
         g = g.float()                                        # a plan the wide-load kernel does not take: widen once
-    check(_lib.lib().rfx_gemm_wgrad(C.byref(dp.desc), _ptr(dp.ktab), _ptr(x), _ptr(g), _ptr(ws), cap, C.byref(ns),
-                                    GEMM_PREC, _stream()), "rfx_gemm_wgrad")
+    launch("rfx_gemm_wgrad", C.byref(dp.desc), dp.ktab, x, g, ws, cap, C.byref(ns), GEMM_PREC)
     if TRACE_WGRAD is not None:
-        TRACE_WGRAD.append(_lib.lib().rfx_gemm_wgrad_variant(C.byref(dp.desc), cap, GEMM_PREC))
+        TRACE_WGRAD.append(query("rfx_gemm_wgrad_variant", C.byref(dp.desc), cap, GEMM_PREC))
     return WgradOut(ws, ns.value)
 
 
 def unpack_set(dp, wg, dw):
     """dw = sum of the split matrices, unpacked; only for plans whose rows cover every element of dw exactly once (dense conv plans)."""
     p = dp.p
-    check(_lib.lib().rfx_unpack_set(_ptr(wg.ws), _ptr(dp.woff), p.w_ms, p.M, p.extra["n_weight_rows"],
-                                    p.Kpad, _ptr(dw), wg.splits, _stream()), "rfx_unpack_set")
+    launch("rfx_unpack_set", wg.ws, dp.woff, p.w_ms, p.M, p.extra["n_weight_rows"], p.Kpad, dw, wg.splits)
 
 
 def unpack_add(dp, wg, dw):
     p = dp.p
-    check(_lib.lib().rfx_unpack_add(_ptr(wg.ws), _ptr(dp.woff), p.w_ms, p.M, p.extra["n_weight_rows"],
-                                    p.Kpad, _ptr(dw), wg.splits, _stream()), "rfx_unpack_add")
+    launch("rfx_unpack_add", wg.ws, dp.woff, p.w_ms, p.M, p.extra["n_weight_rows"], p.Kpad, dw, wg.splits)
 
 
 def unpack_col(dp, wg, col):
     """(M,) = column `col` of the summed split matrices (the bias-gradient column)."""
     p = dp.p
     out = torch.empty(p.M, device=wg.ws.device, dtype=torch.float32)
-    check(_lib.lib().rfx_unpack_col(_ptr(wg.ws), p.M, p.Kpad, col, wg.splits, _ptr(out), _stream()), "rfx_unpack_col")
+    launch("rfx_unpack_col", wg.ws, p.M, p.Kpad, col, wg.splits, out)
     return out
 
 
@@ -648,8 +673,8 @@ def conv2d_wgrad(x, g, wshape, stride, padding, dilation, need_bias, w=None, b=N
             dw, db = sw.grads
             wg = gemm_wgrad(dp, x, g)
             if need_bias:       # weight + bias gradient out of the same matrices in one launch
-                check(_lib.lib().rfx_unpack_add_bias(_ptr(wg.ws), _ptr(dp.woff), p.w_ms, p.M, p.extra["n_weight_rows"], p.Kpad,
-                                                     _ptr(dw), p.K - 1, _ptr(db), wg.splits, _stream()), "rfx_unpack_add_bias")
+                launch("rfx_unpack_add_bias", wg.ws, dp.woff, p.w_ms, p.M, p.extra["n_weight_rows"], p.Kpad, dw, p.K - 1, db,
+                       wg.splits)
             else:
                 unpack_add(dp, wg, dw)                     # conv_fwd_plan rows = every live (ci, ka, kb) of every output channel, once
         return None, None
@@ -675,15 +700,20 @@ def _conv2d_backward(ctx, g, res=None):
     return dx, dw, db
 
 
+def _conv2d_node_forward(ctx, x, w, bias, stride, padding, dilation, stat_sums, out_bf16):
+    """conv2d_forward as an autograd node's forward: saves what _conv2d_backward reads."""
+    ctx.save_for_backward(x, w)
+    ctx.bias = bias                                       # identity only (GradSink lookup); never read
+    ctx.cfg = (stride, padding, dilation, bias is not None)
+    return conv2d_forward(x, w, bias, stride, padding, dilation, stat_sums=stat_sums, out_bf16=out_bf16)
+
+
 class Conv2dFn(torch.autograd.Function):
     """nn.Conv2d / nn.Conv1d (A == 1) forward + backward on the gather-GEMM kernels."""
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, padding, dilation, stat_sums=None, out_bf16=False):
-        ctx.save_for_backward(x, w)
-        ctx.bias = bias                                   # identity only (GradSink lookup); never read
-        ctx.cfg = (stride, padding, dilation, bias is not None)
-        return conv2d_forward(x, w, bias, stride, padding, dilation, stat_sums=stat_sums, out_bf16=out_bf16)
+        return _conv2d_node_forward(ctx, x, w, bias, stride, padding, dilation, stat_sums, out_bf16)
 
     @staticmethod
     def backward(ctx, g):
@@ -698,10 +728,7 @@ class ConvFork2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, padding, dilation, stat_sums=None, out_bf16=False):
-        ctx.save_for_backward(x, w)
-        ctx.bias = bias
-        ctx.cfg = (stride, padding, dilation, bias is not None)
-        return conv2d_forward(x, w, bias, stride, padding, dilation, stat_sums=stat_sums, out_bf16=out_bf16), x.view_as(x)
+        return _conv2d_node_forward(ctx, x, w, bias, stride, padding, dilation, stat_sums, out_bf16), x.view_as(x)
 
     @staticmethod
     def backward(ctx, g, gres):
@@ -744,10 +771,7 @@ class ConvGlu2dFn(torch.autograd.Function):
         N, C2 = y2.shape[0], y2.shape[1]
         S = y2.numel() // (N * C2)
         g2 = torch.empty_like(y2)
-        if y2.dtype == torch.bfloat16:
-            check(_lib.lib().rfx_glu_bwd_bf16(_ptr(y2), _ptr(g.contiguous()), _ptr(g2), N, C2, S, _stream()), "rfx_glu_bwd_bf16")
-        else:
-            check(_lib.lib().rfx_glu_bwd(_ptr(y2), _ptr(g.contiguous()), _ptr(g2), N, C2, S, _stream()), "rfx_glu_bwd")
+        launch("rfx_glu_bwd_bf16" if y2.dtype == torch.bfloat16 else "rfx_glu_bwd", y2, g.contiguous(), g2, N, C2, S)
         return _conv2d_backward(ctx, g2) + (None,) * 3
 
 
@@ -870,9 +894,8 @@ def channel_sum(g):
     out = torch.empty(g4.shape[1], device=g.device, dtype=torch.float32)
     N, Cc, A, B = g4.shape
     s = g4.stride()
-    L = _lib.lib()
-    ws = torch.empty(int(L.rfx_channel_sum_ws(_ptr(g4), N, Cc, A, B, s[0], s[1], s[2], s[3])), device=g.device, dtype=torch.float64)
-    check(L.rfx_channel_sum(_ptr(g4), N, Cc, A, B, s[0], s[1], s[2], s[3], _ptr(ws), _ptr(out), _stream()), "rfx_channel_sum")
+    ws = torch.empty(query("rfx_channel_sum_ws", g4, N, Cc, A, B, s[0], s[1], s[2], s[3]), device=g.device, dtype=torch.float64)
+    launch("rfx_channel_sum", g4, N, Cc, A, B, s[0], s[1], s[2], s[3], ws, out)
     return out
 
 
@@ -880,8 +903,16 @@ def _rows16(x, gy, out, act):
     """rfx_act_rows16 on a contiguous tensor whose storage is bf16 (ops.bf16_storage): (rows, T) view, T = last axis."""
     T = x.shape[-1]
     R = x.numel() // T
-    check(_lib.lib().rfx_act_rows16(_ptr(x), 0, 0, T, _ptr(gy) if gy is not None else None, 0, 0, T, _ptr(out), 0, 0, T,
-                                    1, 1, R, T, ACT[act], _stream()), "rfx_act_rows16")
+    launch("rfx_act_rows16", x, 0, 0, T, gy, 0, 0, T, out, 0, 0, T, 1, 1, R, T, ACT[act])
+
+
+def _act_bwd(ctx, gy):
+    """(gx, contiguous gy) of a node that saved its contiguous fp32 x and set ctx.act."""
+    (x,) = ctx.saved_tensors
+    gy = gy.contiguous()
+    gx = torch.empty_like(x)
+    launch("rfx_act_bwd", x, gy, gx, x.numel(), ACT[ctx.act])
+    return gx, gy
 
 
 class ActFn(torch.autograd.Function):
@@ -895,7 +926,7 @@ class ActFn(torch.autograd.Function):
             _req(x)
             x = x.contiguous()
             y = torch.empty_like(x)
-            check(_lib.lib().rfx_act_fwd(_ptr(x), _ptr(y), x.numel(), ACT[act], _stream()), "rfx_act_fwd")
+            launch("rfx_act_fwd", x, y, x.numel(), ACT[act])
         ctx.save_for_backward(x)
         ctx.act = act
         return y
@@ -903,14 +934,12 @@ class ActFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = torch.empty_like(x)
         if x.dtype == torch.bfloat16:
+            gy = gy.contiguous()
+            gx = torch.empty_like(x)
             _rows16(x, gy, gx, ctx.act)
             return gx, None
-        check(_lib.lib().rfx_act_bwd(_ptr(x), _ptr(gy), _ptr(gx), x.numel(), ACT[ctx.act], _stream()),
-              "rfx_act_bwd")
-        return gx, None
+        return _act_bwd(ctx, gy)[0], None
 
 
 def activation(x, act):
@@ -925,19 +954,14 @@ class ActAddFn(torch.autograd.Function):
         _req(x); _req(res, "res")
         x, res = x.contiguous(), res.contiguous()
         y = torch.empty_like(x)
-        check(_lib.lib().rfx_act_add_fwd(_ptr(x), _ptr(res), _ptr(y), x.numel(), ACT[act], _stream()), "rfx_act_add_fwd")
+        launch("rfx_act_add_fwd", x, res, y, x.numel(), ACT[act])
         ctx.save_for_backward(x)
         ctx.act = act
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = torch.empty_like(x)
-        check(_lib.lib().rfx_act_bwd(_ptr(x), _ptr(gy), _ptr(gx), x.numel(), ACT[ctx.act], _stream()),
-              "rfx_act_bwd")
-        return gx, gy, None
+        return _act_bwd(ctx, gy) + (None,)
 
 
 def activation_add(x, res, act):
@@ -961,15 +985,14 @@ class ActToFn(torch.autograd.Function):
         x16 = x.dtype == torch.bfloat16         # a conv output stored in 16 bits (bf16 mode): fp32 result, 16-bit gradient
         if not x16:
             _req(x)
-        rows = _lib.lib().rfx_act_rows16 if x16 else _lib.lib().rfx_act_rows
         xs = _row_strides(x)
         D = x.shape
         y = torch.empty([D[p] for p in perm] + [D[3]], device=x.device, dtype=torch.float32)
         inv = [perm.index(i) for i in range(3)]
         y = y.permute(*inv, 3)                                  # x-shaped view of the permuted buffer
         ys = _row_strides(y)
-        check(rows(_ptr(x), xs[0], xs[1], xs[2], None, 0, 0, 0, _ptr(y), ys[0], ys[1], ys[2],
-                   D[0], D[1], D[2], D[3], ACT[act], _stream()), "rfx_act_rows")
+        launch("rfx_act_rows16" if x16 else "rfx_act_rows", x, xs[0], xs[1], xs[2], None, 0, 0, 0, y, ys[0], ys[1], ys[2],
+               D[0], D[1], D[2], D[3], ACT[act])
         ctx.save_for_backward(x)
         ctx.act = act
         return y
@@ -981,9 +1004,8 @@ class ActToFn(torch.autograd.Function):
             gy = gy.contiguous()
         xs, gs, D = _row_strides(x), _row_strides(gy), x.shape
         gx = torch.empty_strided(x.shape, x.stride(), device=x.device, dtype=x.dtype)
-        rows = _lib.lib().rfx_act_rows16 if x.dtype == torch.bfloat16 else _lib.lib().rfx_act_rows
-        check(rows(_ptr(x), xs[0], xs[1], xs[2], _ptr(gy), gs[0], gs[1], gs[2], _ptr(gx), xs[0], xs[1],
-                   xs[2], D[0], D[1], D[2], D[3], ACT[ctx.act], _stream()), "rfx_act_rows")
+        launch("rfx_act_rows16" if x.dtype == torch.bfloat16 else "rfx_act_rows", x, xs[0], xs[1], xs[2], gy, gs[0], gs[1], gs[2],
+               gx, xs[0], xs[1], xs[2], D[0], D[1], D[2], D[3], ACT[ctx.act])
         return gx, None, None
 
 

@@ -7,13 +7,10 @@ their .grad tensors as views into ONE contiguous gradient buffer.  That makes
   * the data-parallel gradient exchange a handful of large RCCL all-reduces over xGMI
     on slices of the same buffer (remfx_amd/ddp.py) -- no per-tensor collectives.
 """
-import ctypes as C
-
 import torch
 
-from . import _lib, ops
-from ._lib import check
-from .ops import _ptr, _stream
+from . import ops
+from .ops import launch
 
 
 class FlatParams:
@@ -101,19 +98,17 @@ class FlatAdamW:
     def step(self, clip_norm=None, grad_prescale=1.0):
         """One update.  clip_norm: global L2 norm clip (Lightning gradient_clip_val);
         grad_prescale: factor already owed to the gradients (1/world_size after a SUM all-reduce)."""
-        L, f = _lib.lib(), self.flat
+        f = self.flat
         f.join()                                         # side-stream weight gradients land before the buffer is read
         self.step_count += 1
         gscale = None
         if clip_norm or grad_prescale != 1.0:
-            check(L.rfx_sumsq(_ptr(f.grad), f.numel, _ptr(self._sumsq_ws), _ptr(self._sumsq), _stream()), "rfx_sumsq")
-            check(L.rfx_clip_coef(_ptr(self._sumsq), float(clip_norm or 0.0), float(grad_prescale),
-                                  _ptr(self._coef), _ptr(self.last_grad_norm), _stream()), "rfx_clip_coef")
+            launch("rfx_sumsq", f.grad, f.numel, self._sumsq_ws, self._sumsq)
+            launch("rfx_clip_coef", self._sumsq, float(clip_norm or 0.0), float(grad_prescale), self._coef, self.last_grad_norm)
             gscale = self._coef
         lr = self.param_groups[0]["lr"]
-        check(L.rfx_adamw_step(_ptr(f.data), _ptr(f.grad), _ptr(self.m), _ptr(self.v), f.numel, lr,
-                               self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
-                               _ptr(gscale), _stream()), "rfx_adamw_step")
+        launch("rfx_adamw_step", f.data, f.grad, self.m, self.v, f.numel, lr, self.betas[0], self.betas[1], self.eps,
+               self.weight_decay, self.step_count, gscale)
         ops.weights_changed()                            # the kernel wrote the parameters through a raw pointer: cached packs are stale
 
     def zero_grad(self):

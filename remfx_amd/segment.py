@@ -20,7 +20,7 @@ w[j] = min(j + 1, L' - j) over the valid window.
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import ops
 
 
 class SegmentPlan:
@@ -78,8 +78,7 @@ def split(x, plan):
     x = x.contiguous()
     rows = x.shape[0] * x.shape[1]
     out = torch.empty(rows * plan.n_segments, 1, plan.segment, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().rfx_segment_split(ops._ptr(x), ops._ptr(out), rows, plan.T, plan.segment, plan.hop, plan.n_segments,
-                                            ops._stream()), "rfx_segment_split")
+    ops.launch("rfx_segment_split", x, out, rows, plan.T, plan.segment, plan.hop, plan.n_segments)
     return out
 
 
@@ -99,8 +98,7 @@ def merge(y, plan, channels=1, out=None):
         ops._req(out, "segment.merge out")
         if out.numel() != rows * plan.out_len or not out.is_contiguous():
             raise ValueError(f"segment.merge: out must be contiguous with {rows} x {plan.out_len} samples")
-    _lib.check(_lib.lib().rfx_segment_merge(ops._ptr(y), ops._ptr(out), rows, plan.T, plan.segment, plan.hop, plan.lead,
-                                            plan.trail, S, ops._stream()), "rfx_segment_merge")
+    ops.launch("rfx_segment_merge", y, out, rows, plan.T, plan.segment, plan.hop, plan.lead, plan.trail, S)
     return out
 
 
@@ -112,8 +110,7 @@ def split_c(x, plan):
     x = x.contiguous()
     B, Cn = x.shape[0], x.shape[1]
     out = torch.empty(B * plan.n_segments, Cn, plan.segment, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().rfx_segment_split_c(ops._ptr(x), ops._ptr(out), B, Cn, plan.T, plan.segment, plan.hop, plan.n_segments,
-                                              ops._stream()), "rfx_segment_split_c")
+    ops.launch("rfx_segment_split_c", x, out, B, Cn, plan.T, plan.segment, plan.hop, plan.n_segments)
     return out
 
 
@@ -126,8 +123,7 @@ def merge_c(y, plan):
     y = y.contiguous()
     B, Co = y.shape[0] // S, y.shape[1]
     out = torch.empty(B, Co, plan.out_len, device=y.device, dtype=torch.float32)
-    _lib.check(_lib.lib().rfx_segment_merge_c(ops._ptr(y), ops._ptr(out), B, Co, plan.T, plan.segment, plan.hop, plan.lead,
-                                              plan.trail, S, ops._stream()), "rfx_segment_merge_c")
+    ops.launch("rfx_segment_merge_c", y, out, B, Co, plan.T, plan.segment, plan.hop, plan.lead, plan.trail, S)
     return out
 
 

@@ -11,9 +11,8 @@ import math
 
 import torch
 
-from . import _lib
-from ._lib import StftDesc, check
-from .ops import _ptr, _req, _stream, zeros
+from ._lib import StftDesc
+from .ops import _req, launch, query, zeros
 
 MODES = {"complex": 0, "cac": 1, "mag": 2, "pow": 3, "magpow": 4, "complex_fm": 5}
 N_FFT_MIN, N_FFT_MAX = 16, 32768
@@ -46,7 +45,7 @@ def _desc(R, T, n_fft, hop, win, bins, frame0, frames_out, mode, extra_pad=(0, 0
 def syn_ws(d, device):
     """Scratch of one rfx_fft_synthesis launch (uninitialised): carried sums + padded edge zones, or the windowed frames of the
     generic sizes (include/remfx_hip.h)."""
-    return torch.empty(int(_lib.lib().rfx_fft_synthesis_ws(C.byref(d))), device=device, dtype=torch.float32)
+    return torch.empty(query("rfx_fft_synthesis_ws", C.byref(d)), device=device, dtype=torch.float32)
 
 
 def _out_shape(R, bins, frames, mode):
@@ -73,8 +72,7 @@ def stft_raw(x, n_fft, hop, win, window, mode, normalized=False, eps=0.0, alpha=
     out = torch.empty(_out_shape(R, bins, frames_out, mode), device=x.device, dtype=torch.float32)
     d = _desc(R, T, n_fft, hop, win, bins, frame0, frames_out, mode, extra_pad,
               scale=(1.0 / math.sqrt(n_fft)) if normalized else 1.0, eps=eps, alpha=alpha)
-    check(_lib.lib().rfx_fft_analysis(C.byref(d), _ptr(x), _ptr(window), None, _ptr(out), _stream()),
-          "rfx_fft_analysis")
+    launch("rfx_fft_analysis", C.byref(d), x, window, None, out)
     return out
 
 
@@ -99,8 +97,7 @@ class STFTFn(torch.autograd.Function):
         gx = torch.empty((R, T), device=g.device, dtype=torch.float32)      # rfx_fft_synthesis writes every element (accum = 0)
         d = _desc(R, T, n_fft, hop, win, nb, frame0, fo, mode, extra_pad, in_mode=0, herm=0,
                   scale=(1.0 / math.sqrt(n_fft)) if normalized else 1.0)
-        check(_lib.lib().rfx_fft_synthesis(C.byref(d), _ptr(g), _ptr(window), None, _ptr(syn_ws(d, g.device)), _ptr(gx), _stream()),
-              "rfx_fft_synthesis")
+        launch("rfx_fft_synthesis", C.byref(d), g, window, None, syn_ws(d, g.device), gx)
         return (gx,) + (None,) * 10
 
 
@@ -154,8 +151,7 @@ class ISTFTFn(torch.autograd.Function):
         out = torch.empty((R, length), device=spec.device, dtype=torch.float32)   # every sample is stored exactly once (overlap-add by ownership)
         d = _desc(R, length, n_fft, hop, win, nb, frame0, fi, mode, in_mode=1, in_offset=n_fft // 2 + crop,
                   herm=1, scale=scale)
-        check(_lib.lib().rfx_fft_synthesis(C.byref(d), _ptr(spec), _ptr(window), _ptr(inv_env), _ptr(syn_ws(d, spec.device)), _ptr(out),
-                                           _stream()), "rfx_fft_synthesis")
+        launch("rfx_fft_synthesis", C.byref(d), spec, window, inv_env, syn_ws(d, spec.device), out)
         ctx.save_for_backward(window, inv_env)
         ctx.cfg = (spec.shape, n_fft, hop, win, mode, frames, frame0, crop, length, scale, nb, fi)
         return out
@@ -169,8 +165,7 @@ class ISTFTFn(torch.autograd.Function):
         gs = torch.empty(shape, device=g.device, dtype=torch.float32)
         d = _desc(R, length, n_fft, hop, win, nb, frame0, fi, mode, in_mode=1, in_offset=n_fft // 2 + crop,
                   herm=1, scale=scale)
-        check(_lib.lib().rfx_fft_analysis(C.byref(d), _ptr(g), _ptr(window), _ptr(inv_env), _ptr(gs),
-                                          _stream()), "rfx_fft_analysis")
+        launch("rfx_fft_analysis", C.byref(d), g, window, inv_env, gs)
         return (gs,) + (None,) * 10
 
 

@@ -18,9 +18,8 @@ channels, windows longer than rfx_wiener_max_window() frames.
 import torch
 import torch.nn as nn
 
-from . import _lib, lstm, nnops, ops, stft
-from ._lib import check
-from .ops import _ptr, _stream
+from . import lstm, nnops, ops, stft
+from .ops import launch, query
 
 
 class OpenUnmix(nn.Module):
@@ -73,7 +72,7 @@ class _PhaseMaskFn(torch.autograd.Function):
     def forward(ctx, mag, xc):
         mag = mag.contiguous()
         out = torch.empty_like(xc)
-        check(_lib.lib().rfx_phase_mask_fwd(_ptr(mag), _ptr(xc), _ptr(out), mag.numel(), _stream()), "rfx_phase_mask_fwd")
+        launch("rfx_phase_mask_fwd", mag, xc, out, mag.numel())
         ctx.save_for_backward(xc)
         return out
 
@@ -81,8 +80,7 @@ class _PhaseMaskFn(torch.autograd.Function):
     def backward(ctx, g):
         (xc,) = ctx.saved_tensors
         gm = torch.empty(xc.shape[:-1], device=xc.device, dtype=torch.float32)
-        check(_lib.lib().rfx_phase_mask_bwd(_ptr(xc), _ptr(g.contiguous()), _ptr(gm), gm.numel(), _stream()),
-              "rfx_phase_mask_bwd")
+        launch("rfx_phase_mask_bwd", xc, g.contiguous(), gm, gm.numel())
         return gm, None
 
 
@@ -114,9 +112,9 @@ class Separator(nn.Module):
             wiener_win_len = int(wiener_win_len)
             if wiener_win_len < 1:
                 raise ValueError("wiener_win_len must be positive or None")
-            if not self.plain and wiener_win_len > _lib.lib().rfx_wiener_max_window():
+            if not self.plain and wiener_win_len > query("rfx_wiener_max_window"):
                 raise NotImplementedError("wiener_win_len %d is above the %d frames one workgroup keeps on chip "
-                                          "(rfx_wiener_max_window)" % (wiener_win_len, _lib.lib().rfx_wiener_max_window()))
+                                          "(rfx_wiener_max_window)" % (wiener_win_len, query("rfx_wiener_max_window")))
         self.target_models = nn.ModuleDict(target_models)
         self.nb_targets = len(self.target_models)
         self.niter, self.softmask, self.residual, self.wiener_win_len = niter, softmask, residual, wiener_win_len
@@ -143,12 +141,11 @@ class Separator(nn.Module):
             return ys[0].view(B, 1, Cc, T) if len(ys) == 1 else torch.stack(ys, 1)
         if Cc > 2:
             raise NotImplementedError("the Wiener filter takes at most 2 channels (got %d)" % Cc)
-        L = _lib.lib()
         bins, frames = X.shape[-2:]
         W = frames if self.wiener_win_len is None else self.wiener_win_len
-        if W > L.rfx_wiener_max_window():
+        if W > query("rfx_wiener_max_window"):
             raise NotImplementedError("wiener_win_len=None on %d frames: one window above the %d frames one workgroup keeps on chip "
-                                      "(rfx_wiener_max_window)" % (frames, L.rfx_wiener_max_window()))
+                                      "(rfx_wiener_max_window)" % (frames, query("rfx_wiener_max_window")))
         J0, J = self.nb_targets, self.nb_targets + self.residual
         S = torch.empty((J0, B * Cc, bins, frames), device=audio.device, dtype=torch.float32)     # the models' magnitudes, written once
         for j, model in enumerate(self.target_models.values()):
@@ -157,10 +154,9 @@ class Separator(nn.Module):
                 raise RuntimeError("Separator with niter > 0, softmask or residual is forward only: there is no gradient through the "
                                    "Wiener filter.  Call it under torch.no_grad() or freeze() it")
             S[j].copy_(mag.detach().reshape(B * Cc, bins, frames))
-        ws = torch.empty((max(1, L.rfx_wiener_ws_floats(B, Cc, bins, frames, W)),), device=audio.device, dtype=torch.float32)
+        ws = torch.empty((max(1, query("rfx_wiener_ws_floats", B, Cc, bins, frames, W)),), device=audio.device, dtype=torch.float32)
         Y = torch.empty((B, J, Cc, bins, frames, 2), device=audio.device, dtype=torch.float32)
-        check(L.rfx_wiener(_ptr(xc), _ptr(S), _ptr(Y), B, Cc, J0, int(self.residual), bins, frames, W, self.niter, int(self.softmask),
-                           _ptr(ws), _stream()), "rfx_wiener")
+        launch("rfx_wiener", xc, S, Y, B, Cc, J0, int(self.residual), bins, frames, W, self.niter, int(self.softmask), ws)
         y = stft.istft(Y.view(B * J * Cc, bins, frames, 2), self.n_fft, self.n_hop, mode="complex", length=T)
         return y.view(B, J, Cc, T)
 

@@ -9,8 +9,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from remfx_amd import _lib, stft
-from remfx_amd.ops import _ptr, _stream
+from remfx_amd import ops, stft
 
 dev = torch.device("cuda:0")
 R, L = 64, 262144
@@ -41,11 +40,10 @@ def main():
         w = stft.hann(n, dev)
         X = torch.empty((R, frames, bins, 2), device=dev)
         d = stft._desc(R, L, n, hop, n, bins, 0, frames, 5)
-        lib = _lib.lib()
-        ana = lambda: _lib.check(lib.rfx_fft_analysis(C.byref(d), _ptr(x), _ptr(w), None, _ptr(X), _stream()), "analysis")
+        ana = lambda: ops.launch("rfx_fft_analysis", C.byref(d), x, w, None, X)
         t_a = median_us(ana)
         ws, gx = stft.syn_ws(d, dev), torch.empty_like(x)
-        syn = lambda: _lib.check(lib.rfx_fft_synthesis(C.byref(d), _ptr(X), _ptr(w), None, _ptr(ws), _ptr(gx), _stream()), "synthesis")
+        syn = lambda: ops.launch("rfx_fft_synthesis", C.byref(d), X, w, None, ws, gx)
         t_s = median_us(syn)
         nbytes = x.numel() * 4 + X.numel() * 4
         print(f"{n:>6} {frames:>7} {nbytes / 1e9:>7.3f} {t_a:>12.1f} {nbytes / (t_a * 1e-6) / HBM:>7.3f} {t_s:>13.1f} "

@@ -24,8 +24,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
-from remfx_amd import _lib, losses  # noqa: E402
-from remfx_amd.ops import _ptr, _stream  # noqa: E402
+from remfx_amd import losses, ops  # noqa: E402
 
 HBM = 8.0e12
 FMA_RATE = 157.3e12 / 2            # fp32 vector peak in fused multiply-adds per second (packed: 2 per lane and instruction)
@@ -62,12 +61,9 @@ def main():
     nbytes = 2 * 2 * R * L * 4
     print(f"{R} x {L}, K = {K}, two signals, {S} buffer sets of {nbytes / 1e6:.1f} MB: HBM floor {nbytes / HBM * 1e6:.1f} us, "
           f"packed fp32 FMA floor {2 * R * L * K / FMA_RATE * 1e6:.1f} us", flush=True)
-    lib = _lib.lib()
-
     def fir(flip, i):
         j = i % S
-        _lib.check(lib.rfx_fir_same(_ptr(xs[j]), _ptr(yxs[j]), _ptr(ts[j]), _ptr(yts[j]), R, L, L, L, L, L, _ptr(h), K, flip, _stream()),
-                   "rfx_fir_same")
+        ops.launch("rfx_fir_same", xs[j], yxs[j], ts[j], yts[j], R, L, L, L, L, L, h, K, flip)
 
     w = {0: h.view(1, 1, K), 1: h.flip(0).contiguous().view(1, 1, K)}
 

@@ -89,20 +89,17 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("perf_wiener.py measures on the GPU; none found")
-    from remfx_amd import _lib
-    from remfx_amd.ops import _ptr, _stream
-    L = _lib.lib()
+    from remfx_amd import ops
     B, C, J0, residual, W, n_fft, hop = a.clips, 2, 4, 1, 300, 4096, 1024
     bins, frames, J = n_fft // 2 + 1, 1 + a.samples // hop, J0 + residual
     g = torch.Generator(device="cuda").manual_seed(0)
     X = torch.randn((B * C, bins, frames, 2), device="cuda", generator=g)
     S = torch.view_as_complex(X).abs()[None] * torch.rand((J0, B * C, bins, frames), device="cuda", generator=g)
     Y = torch.empty((B, J, C, bins, frames, 2), device="cuda")
-    ws = torch.empty((L.rfx_wiener_ws_floats(B, C, bins, frames, W),), device="cuda")
+    ws = torch.empty((ops.query("rfx_wiener_ws_floats", B, C, bins, frames, W),), device="cuda")
 
     def kernel():
-        rc = L.rfx_wiener(_ptr(X), _ptr(S), _ptr(Y), B, C, J0, residual, bins, frames, W, a.niter, 0, _ptr(ws), _stream())
-        assert rc == 0, rc
+        ops.launch("rfx_wiener", X, S, Y, B, C, J0, residual, bins, frames, W, a.niter, 0, ws)
 
     Xc = torch.view_as_complex(X)
     k_ms = timed(kernel, 3, a.repeats)

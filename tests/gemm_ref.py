@@ -778,15 +778,15 @@ def recorder(dry_run):
     launchers' selection are the real ones"""
     from remfx_amd import _lib, ops
     real = _lib.lib()
-    saved = (_lib.lib, ops._stream, ops.raw_stream, ops._req)
+    saved = (_lib.lib, ops.raw_stream, ops._req)
     proxy = _Proxy(real, dry_run)
     _lib.lib = lambda: proxy
     if dry_run:
-        ops._stream, ops.raw_stream, ops._req = (lambda: None), (lambda: 0), (lambda *a: None)
+        ops.raw_stream, ops._req = (lambda: 0), (lambda *a: None)
     try:
         yield proxy
     finally:
-        _lib.lib, ops._stream, ops.raw_stream, ops._req = saved
+        _lib.lib, ops.raw_stream, ops._req = saved
 
 
 @contextlib.contextmanager
@@ -818,7 +818,7 @@ def _cpu_alloc(shape, dtype, fill=None):
 def launch(case, inp, dev="cpu", alloc=_cpu_alloc):
     """One case through remfx_amd.ops (call inside case_env and recorder(); recorder(True) without a GPU).  alloc(shape, dtype[, fill]) hands out the output
     buffers (the GPU test: NaN-filled between guards).  -> {output name: tensor}"""
-    from remfx_amd import _lib, convplan, ops
+    from remfx_amd import convplan, ops
     d = lambda t: t.to(dev)
     N, Cin, Cout = case.N, case.cin, case.cout
     (IA, IB), (KA, KB) = case.ishape, case.ksize
@@ -889,13 +889,12 @@ def launch(case, inp, dev="cpu", alloc=_cpu_alloc):
     dp = ops._plans(key, x.device, lambda: convplan.conv_fwd_plan(tuple(x.shape), x.stride(), tuple(w.shape), st, pd, dl, g.stride(), bias_row=case.bias))
     p = dp.p
     wg = ops.gemm_wgrad(dp, x, g)
-    L = _lib.lib()
     if case.unpack == "set":
         dw = alloc(tuple(w.shape), torch.float32, None if p.extra.get("dense", True) else 0.0)
         ops.unpack_set(dp, wg, dw)
         if case.bias:
             db = alloc((Cout,), torch.float32)
-            ops.check(L.rfx_unpack_col(ops._ptr(wg.ws), p.M, p.Kpad, p.K - 1, wg.splits, ops._ptr(db), ops._stream()), "rfx_unpack_col")
+            ops.launch("rfx_unpack_col", wg.ws, p.M, p.Kpad, p.K - 1, wg.splits, db)
     else:
         dw = alloc(tuple(w.shape), torch.float32, 0.0)
         dw.copy_(d(inp["dw0"]))
@@ -903,8 +902,7 @@ def launch(case, inp, dev="cpu", alloc=_cpu_alloc):
             db = alloc((Cout,), torch.float32, 0.0)
             db.copy_(d(inp["db0"]))
         if case.unpack == "add_bias":
-            ops.check(L.rfx_unpack_add_bias(ops._ptr(wg.ws), ops._ptr(dp.woff), p.w_ms, p.M, p.extra["n_weight_rows"], p.Kpad, ops._ptr(dw),
-                                            p.K - 1, ops._ptr(db), wg.splits, ops._stream()), "rfx_unpack_add_bias")
+            ops.launch("rfx_unpack_add_bias", wg.ws, dp.woff, p.w_ms, p.M, p.extra["n_weight_rows"], p.Kpad, dw, p.K - 1, db, wg.splits)
         else:
             ops.unpack_add(dp, wg, dw)
             if case.bias:
