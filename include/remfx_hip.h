@@ -578,11 +578,14 @@ int rfx_avgpool2d_fwd(const float* x, float* y, int64_t NC, int32_t H, int32_t W
                       void* stream);
 int rfx_avgpool2d_bwd(const float* gy, float* gx, int64_t NC, int32_t H, int32_t W, int32_t kh, int32_t kw,
                       void* stream);
-/* GLU over the channel axis of (N, C, S): y = x[:, :C/2] * sigmoid(x[:, C/2:]) */
+/* GLU over the channel axis of (N, C, S): y = x[:, :C/2] * sigmoid(x[:, C/2:]).  Alignment rule: the 16-byte row kernels run when
+ * (C/2)*S is a multiple of 4 AND x, y (backward: x, gy, gx) are 16-byte aligned; any other length or base takes the flat
+ * one-element-per-thread kernels, which need fp32 alignment only.  Both forms compute the same values. */
 int rfx_glu_fwd(const float* x, float* y, int64_t N, int64_t C, int64_t S, void* stream);
 int rfx_glu_bwd(const float* x, const float* gy, float* gx, int64_t N, int64_t C, int64_t S, void* stream);
 /* same with x (the conv output) and gx (its gradient) STORED as bf16 (bf16 arithmetic mode: both are only GEMM operands / GLU
- * inputs); gy fp32; (C/2)*S a multiple of 4. */
+ * inputs); gy fp32; (C/2)*S a multiple of 4, x and gx 8-byte aligned, gy 16-byte aligned -- there is no flat 16-bit form: anything
+ * else returns -1 and writes nothing. */
 int rfx_glu_bwd_bf16(const void* x, const float* gy, void* gx, int64_t N, int64_t C, int64_t S, void* stream);
 
 /* ---- complex-valued pieces of DCUNet (asteroid DCUNet via models.py:347-367) -------

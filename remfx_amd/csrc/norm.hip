@@ -1157,6 +1157,8 @@ __global__ __launch_bounds__(256) void glu_bwd_rows_kernel(const XT* __restrict_
   rfx_st4(gx + ia, da);
   rfx_st4(gx + ia + L, db);
 }
+// the row kernels move 16 bytes of fp32 (8 of bf16) per lane: every base has to be aligned to that, as in segment.hip / fir.hip
+static bool glu_aligned(const void* p, uintptr_t bytes) { return !(reinterpret_cast<uintptr_t>(p) & (bytes - 1)); }
 static bool glu_row_items(int64_t N, int64_t L, uint32_t* nitems, uint32_t* ipr) {
   const int64_t per = (L + 255) / 256;
   if ((L & 3) || N * per > 0x7fffffffLL) return false;
@@ -1166,7 +1168,7 @@ static bool glu_row_items(int64_t N, int64_t L, uint32_t* nitems, uint32_t* ipr)
 extern "C" int rfx_glu_fwd(const float* x, float* y, int64_t N, int64_t C, int64_t S, void* stream) {
   if (!x || !y || N <= 0 || C <= 0 || (C & 1) || S <= 0) return -1;
   uint32_t nitems = 0, ipr = 0;
-  if (glu_row_items(N, (C / 2) * S, &nitems, &ipr))
+  if (glu_aligned(x, 16) && glu_aligned(y, 16) && glu_row_items(N, (C / 2) * S, &nitems, &ipr))
     hipLaunchKernelGGL(glu_fwd_rows_kernel, dim3((nitems + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, y, nitems, ipr,
                        (C / 2) * S);
   else
@@ -1177,7 +1179,7 @@ extern "C" int rfx_glu_fwd(const float* x, float* y, int64_t N, int64_t C, int64
 extern "C" int rfx_glu_bwd(const float* x, const float* gy, float* gx, int64_t N, int64_t C, int64_t S, void* stream) {
   if (!x || !gy || !gx || N <= 0 || C <= 0 || (C & 1) || S <= 0) return -1;
   uint32_t nitems = 0, ipr = 0;
-  if (glu_row_items(N, (C / 2) * S, &nitems, &ipr))
+  if (glu_aligned(x, 16) && glu_aligned(gy, 16) && glu_aligned(gx, 16) && glu_row_items(N, (C / 2) * S, &nitems, &ipr))
     hipLaunchKernelGGL(glu_bwd_rows_kernel<float>, dim3((nitems + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, gy, gx, nitems,
                        ipr, (C / 2) * S);
   else
@@ -1186,9 +1188,10 @@ extern "C" int rfx_glu_bwd(const float* x, const float* gy, float* gx, int64_t N
   return 0;
 }
 // x (conv output) and gx (its gradient) stored as bf16 (bf16 mode: both are only ever GEMM operands / GLU inputs); gy fp32.
-// (C / 2) * S must be a multiple of 4.
+// (C / 2) * S must be a multiple of 4, x and gx 8-byte and gy 16-byte aligned: there is no flat 16-bit form to fall back to.
 extern "C" int rfx_glu_bwd_bf16(const void* x, const float* gy, void* gx, int64_t N, int64_t C, int64_t S, void* stream) {
   if (!x || !gy || !gx || N <= 0 || C <= 0 || (C & 1) || S <= 0) return -1;
+  if (!glu_aligned(x, 8) || !glu_aligned(gx, 8) || !glu_aligned(gy, 16)) return -1;
   uint32_t nitems = 0, ipr = 0;
   if (!glu_row_items(N, (C / 2) * S, &nitems, &ipr)) return -1;
   hipLaunchKernelGGL(glu_bwd_rows_kernel<rfx_bf16s>, dim3((nitems + 3) / 4), dim3(256), 0, (hipStream_t)stream,

@@ -925,3 +925,37 @@ def walk_all_cases():
         for p in DROPOUT_P:
             out |= forms_dropout(n, p)
     return out
+
+
+# ---- rfx_zero (csrc/optim.hip: zero_kernel) ----------------------------------------------------------------------------------------------
+# nbytes a multiple of 4 at a 4-byte aligned base; anything else is refused and nothing is written.  The kernel stores up to 3 head words
+# to reach a 16-byte boundary, 16-byte vectors in a grid-stride loop, and up to 3 tail words; the grid is capped at 16384 workgroups
+# of 256 threads, one workgroup per 4096 words.
+ZERO_GRID_CAP_WORDS = 16384 * 4096
+ZERO_BYTES = (0, 1, 3, 4, 15, 16, 17, 20, 64, 4099, 4100, 16 * 4096 + 28)     # the issue's counts, and word counts with a body and a tail
+ZERO_BYTES_CAP = 4 * (ZERO_GRID_CAP_WORDS + 9)                  # one workgroup more than the cap holds; from a base one word on: head 3, tail 2
+ZERO_WORD_OFFSETS = (0, 1, 2, 3)                                 # base past a 16-byte boundary, in words: head of 0, 3, 2, 1 words
+
+
+def forms_zero(nbytes, byte_off=0):
+    """branches of one rfx_zero call at a base `byte_off` bytes past a 16-byte boundary; None: refused; empty: accepted, nothing launched"""
+    if nbytes < 0 or nbytes % 4 or byte_off % 4:
+        return None
+    n = nbytes // 4
+    if n == 0:
+        return set()
+    head = min(((16 - byte_off % 16) % 16) // 4, n)
+    n4 = (n - head) // 4
+    out = set()
+    if head:
+        out.add("head")
+    if n4:
+        out.add("vec")
+    if n - head - 4 * n4:
+        out.add("tail")
+    grid = min(max(-(-n // 4096), 1), 16384)
+    if n4 > grid * 256:
+        out.add("second_iteration")
+    if -(-n // 4096) > 16384:
+        out.add("grid_capped")
+    return out

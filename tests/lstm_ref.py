@@ -289,3 +289,60 @@ def make_inputs(H, T, Bn, seed=0):
     xp = torch.randn(2, 4 * H, T * Bn, generator=g)
     gout = torch.randn(2 * H, T * Bn, generator=g)
     return xp, w[0], w[1], gout
+
+
+# ---- the parameter glue of one bidirectional layer (rfx_lstm_cat_params, rfx_lstm_grad_scatter) ----------------------------------------
+# Written as the operation: a concatenation, a sum of two biases and six additions -- each fp32 result is ONE rounding of the fp64 value
+# (a copy: none), so the GPU test judges every element with bound 0.
+GLUE_CASES = ((1, 1), (3, 5), (64, 48), (192, 192))             # (H, Cin)
+GLUE_GRID = 1024 * 256                                          # threads of the capped grid
+GLUE_PARAMS = ("w_ih", "w_ih_r", "b_ih", "b_hh", "b_ih_r", "b_hh_r")
+GLUE_MUTATIONS = ("bcat_second_half_from_bh0", "gbh1_not_updated", "assign_for_add")
+
+
+def forms_glue(H, Cin):
+    """what one call of either entry reaches (both size their grid by the 2 * 4 H Cin weight elements); None: refused"""
+    if H <= 0 or Cin <= 0:
+        return None
+    n = 2 * 4 * H * Cin
+    out = {"weights", "biases"}
+    if n > GLUE_GRID:
+        out.add("stride_loop")
+    if n % 256:
+        out.add("ragged_last_block")
+    return out                                                  # the 8 H biases take one pass of the same grid at every H below 32768
+
+
+def glue_data(H, Cin):
+    """every buffer with its own seed and scale, so that two exchanged pointers or halves show: the six parameters, the projection
+    GEMM's gradients dwcat [8H][Cin] / dbcat [8H], and what the six gradient buffers hold before the call (nowhere zero)"""
+    def rnd(n, seed, scale, shift=0.0):
+        return (torch.randn(n, generator=torch.Generator().manual_seed(seed + 131 * H + Cin), dtype=torch.float64) * scale + shift).float()
+    nw, nb = 4 * H * Cin, 4 * H
+    p = {"w_ih": rnd(nw, 1, 1.0), "w_ih_r": rnd(nw, 2, 10.0), "b_ih": rnd(nb, 3, 0.1), "b_hh": rnd(nb, 4, 3.0),
+         "b_ih_r": rnd(nb, 5, 30.0), "b_hh_r": rnd(nb, 6, 0.01)}
+    d = {"dwcat": rnd(2 * nw, 7, 0.5), "dbcat": rnd(2 * nb, 8, 2.0)}
+    g0 = {k: rnd(p[k].numel(), 11 + i, 1.0 + i, shift=5.0 * (i + 1)) for i, k in enumerate(GLUE_PARAMS)}
+    return p, d, g0
+
+
+def cat_params(p, mutate=None):
+    """fp64 {wcat [8H Cin], bcat [8H]}"""
+    second = p["b_ih_r"].double() + (p["b_hh"] if mutate == "bcat_second_half_from_bh0" else p["b_hh_r"]).double()
+    return {"wcat": torch.cat([p["w_ih"], p["w_ih_r"]]).double(), "bcat": torch.cat([p["b_ih"].double() + p["b_hh"].double(), second])}
+
+
+def grad_scatter(g, d, mutate=None):
+    """fp64 {the six gradients after ONE call}: g + the half of dwcat / dbcat that belongs to it, both biases of a direction the same"""
+    nw, nb = g["w_ih"].numel(), g["b_ih"].numel()
+    add = {"w_ih": d["dwcat"][:nw], "w_ih_r": d["dwcat"][nw:], "b_ih": d["dbcat"][:nb], "b_hh": d["dbcat"][:nb], "b_ih_r": d["dbcat"][nb:],
+           "b_hh_r": d["dbcat"][nb:]}
+    out = {}
+    for k in GLUE_PARAMS:
+        if mutate == "gbh1_not_updated" and k == "b_hh_r":
+            out[k] = g[k].double()
+        elif mutate == "assign_for_add":
+            out[k] = add[k].double()
+        else:
+            out[k] = g[k].double() + add[k].double()
+    return out

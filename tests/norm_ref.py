@@ -604,3 +604,208 @@ def large_mean_row(m, eps=GEN_EPS):
     fl, mag = stat_floors(x, "gn", 1, eps), stat_magnitudes(x, "gn", 1, eps)
     return (float((mt.abs() * rt).max()), float(rt[0]), float(((r32 - rt) / rt).abs().max()), float(((rtorch - rt) / rt).abs().max()),
             float((k_of(fl["rstd"]) * EPS32 * mag["rstd"]).max()))
+
+
+# ---- plain GLU and average pooling: the tail of norm.hip (rfx_glu_fwd / _bwd / _bwd_bf16, rfx_avgpool2d_fwd / _bwd) -----------------------
+# Written as the operation.  Bounds, none measured on a kernel:
+#   GLU   the K rule of DESIGN.md 4.21 with elem_ref's sigmoid floors: y = a s(b) and da = g s(b) carry one product more than the
+#         sigmoid (one eps32 = a half-ulp pair more), db = g a s(b) (1 - s(b)) two more than the sigmoid's derivative; each keeps the
+#         smallest normal per unit of what multiplies the sigmoid (1 / (1 + exp(-v)) is 0 where exp overflows and sigmoid is still a
+#         subnormal).  The stored bf16 gx: half a bf16 ulp of the value the kernel rounded on top.
+#   pool  forward: kh kw - 1 rounded adds, the product and the rounding of 1 / (kh kw), in half-ulps of sum |x| / (kh kw), plus one
+#         subnormal spacing; backward: gy * inv, exact where kh kw is a power of two (inv and the product are), else two half-ulps.
+from tests import elem_ref as _E                                # noqa: E402
+
+GLU_GRID_CAP = 4096 * 1024                                      # gn_grid: 4096 workgroups of 256 threads ... 1024 elements each
+GLU_ROW_CASES = ((3, 2, 4), (2, 4, 130), (5, 6, 256), (1, 2, 512))
+GLU_FLAT_CASES = ((1, 2, 1), (3, 2, 5), (2, 6, 43))
+GLU_CAP_CASES = ((1, 2, 4194307), (2, 2, 2097156))             # flat and row, more than GLU_GRID_CAP outputs
+GLU_ENTRIES = ("fwd", "bwd", "bwd_bf16")
+# floors of glu_restate32 over the case tables in units of eps32 x magnitude, rounded up to the next half.  Measured: 1.48, 1.45, 2.24 --
+# above elem_ref's sigmoid floors (1.0 / 2.0) by the extra products, so they are kept here.  The bound keeps K = k_of(sigmoid) + 1 = 17
+# and k_of(sigmoid_grad) + 2 = 26, which is tighter than 8 floor + 8 = 20 / 28 and still 8 floor + 4 at least (test_norm_ref_cpu.py)
+GLU_FLOOR = {"y": 1.5, "da": 1.5, "db": 2.5}
+GLU_SPECIALS = (0.0, -0.0, 2.0 ** -149, -(2.0 ** -149), 2.0 ** -127, -(2.0 ** -127), 88.0, -88.0, 104.0, -104.0, 1e4, -1e4)
+
+
+def forms_glu(entry, N, C, S, offs=(0, 0, 0)):
+    """the kernel and the branches one call reaches, from the conditions of rfx_glu_fwd / _bwd / _bwd_bf16; None: refused.  offs: how many
+    ELEMENTS the bases of (x, y or gx, gy) sit past a 16-byte boundary"""
+    if N <= 0 or C <= 0 or C % 2 or S <= 0:
+        return None
+    L = (C // 2) * S
+    per = -(-L // 256)
+    x16 = entry == "bwd_bf16"
+    esz = (2 if x16 else 4, 2 if x16 else 4, 4)
+    need = (8 if x16 else 16, 8 if x16 else 16, 16)
+    used = (0, 1) if entry == "fwd" else (0, 1, 2)
+    aligned = all((offs[i] * esz[i]) % need[i] == 0 for i in used)
+    rows = L % 4 == 0 and N * per <= 0x7FFFFFFF and aligned
+    if not rows:
+        if x16:
+            return None
+        out = {f"glu_{entry}_kernel:flat"}
+        if N * L > GLU_GRID_CAP:
+            out.add("flat:grid_capped")
+        return out
+    out = {f"glu_{entry[:3]}_rows_kernel<{'bf16' if x16 else 'f32'}>:rows"}
+    if L % 256:
+        out.add("rows:ragged_chunk")                            # lanes of the last chunk leave at o >= L
+    if per > 1:
+        out.add("rows:several_chunks")
+    if (N * per) % 4:
+        out.add("rows:idle_wave")
+    return out
+
+
+def _mixed(n, g):
+    """magnitudes 1e-4 ... 1e3, log-uniform, random sign"""
+    m = 10.0 ** (torch.rand(n, generator=g, dtype=torch.float64) * 7.0 - 4.0)
+    return (m * torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0)).float()
+
+
+def glu_data(N, C, S, seed=0, x16=False):
+    """(x (N, C, S), gy (N, C / 2, S)) fp32.  The value half a: mixed scales with zeros; the gate half b: uniform in [-12, 12] with
+    GLU_SPECIALS at its head when there is room -- two visibly different distributions; gy: mixed scales with zeros"""
+    g = torch.Generator().manual_seed(1000 * seed + 7 * N + 3 * C + S)
+    Co = C // 2
+    n = N * Co * S
+    a, gy = _mixed(n, g), _mixed(n, g)
+    b = (torch.rand(n, generator=g, dtype=torch.float64) * 24.0 - 12.0).float()
+    if n >= 2 * len(GLU_SPECIALS):
+        b[:len(GLU_SPECIALS)] = torch.tensor(GLU_SPECIALS, dtype=torch.float64).float()
+    if n >= 3:
+        a[1::11] = 0.0
+        gy[2::13] = 0.0
+    x = torch.cat([a.view(N, Co, S), b.view(N, Co, S)], 1).contiguous()
+    if x16:
+        x = bf16_rne(x)
+    return x, gy.view(N, Co, S)
+
+
+def glu(x, gy=None):
+    """fp64 {y} or, with gy, {gx}: y = a s(b); da = g s(b), db = g a s(b) (1 - s(b))"""
+    x = x.double()
+    Co = x.shape[1] // 2
+    a, b = x[:, :Co], x[:, Co:]
+    s = _E.act(b, _E.SIGMOID)
+    if gy is None:
+        return {"y": a * s}
+    g = gy.double()
+    return {"gx": torch.cat([g * s, g * a * _E.act_grad(b, _E.SIGMOID)], 1)}
+
+
+def glu_bounds(x, gy=None):
+    """fp32 bound per element of the same outputs"""
+    x = x.double()
+    Co = x.shape[1] // 2
+    a, b = x[:, :Co], x[:, Co:]
+    s = _E.act(b, _E.SIGMOID)
+    k = _E.k_of("sigmoid") + 1.0
+    if gy is None:
+        return {"y": k * EPS32 * (a * s).abs() + a.abs() * _E.MINNORM}
+    g = gy.double()
+    da = k * EPS32 * (g * s).abs() + g.abs() * _E.MINNORM
+    db = (_E.k_of("sigmoid_grad") + 2.0) * EPS32 * a.abs() * _E.act_grad_magnitude(b, g, _E.SIGMOID) + _E.MINNORM * (1.0 + (g * a).abs())
+    return {"gx": torch.cat([da, db], 1)}
+
+
+def bf16_store_bound(ref, b32):
+    """a bf16 RNE store of a value inside b32 of ref: half a bf16 ulp of |ref| + b32 on top"""
+    return 0.5 * ulp(ref.abs() + b32, 7) + b32
+
+
+def glu_restate32(x, gy=None):
+    """the same formulas in float32 with 1 / (1 + exp(-v)) (CPU libm, never a kernel)"""
+    x = x.float()
+    Co = x.shape[1] // 2
+    a, b = x[:, :Co], x[:, Co:]
+    s = 1.0 / (1.0 + torch.exp(-b))
+    if gy is None:
+        return {"y": a * s}
+    g = gy.float()
+    return {"gx": torch.cat([g * s, g * a * s * (1.0 - s)], 1)}
+
+
+def glu_floors(x, gy):
+    """{y, da, db}: the restatement's error, less the smallest-normal term, in units of eps32 x the magnitude the bound multiplies"""
+    x64 = x.double()
+    Co = x.shape[1] // 2
+    a, b, g = x64[:, :Co], x64[:, Co:], gy.double()
+    s = _E.act(b, _E.SIGMOID)
+    ref, r32 = {**glu(x), **glu(x, gy)}, {**glu_restate32(x), **glu_restate32(x, gy)}
+    mags = {"y": ((a * s).abs(), a.abs() * _E.MINNORM, ref["y"], r32["y"]),
+            "da": ((g * s).abs(), g.abs() * _E.MINNORM, ref["gx"][:, :Co], r32["gx"][:, :Co]),
+            "db": (a.abs() * _E.act_grad_magnitude(b, g, _E.SIGMOID), _E.MINNORM * (1.0 + (g * a).abs()), ref["gx"][:, Co:], r32["gx"][:, Co:])}
+    out = {}
+    for k, (mag, tiny, r, f) in mags.items():
+        e = ((f.double() - r).abs() - tiny).clamp_min(0.0)
+        out[k] = float((e / (EPS32 * mag).clamp_min(1e-300)).max())
+    return out
+
+
+# ---- average pooling ------------------------------------------------------------------------------------------------------------------
+POOL_CASES = ((3, 4, 6, 2, 2), (2, 5, 7, 2, 2), (1, 2, 2, 2, 2), (2, 7, 9, 3, 2), (2, 4, 6, 4, 6), (2, 3, 9, 1, 3), (4, 8, 513, 2, 2))
+POOL_CAP_FWD = (4, 2051, 2051, 2, 2)                            # 4 * 1025 * 1025 outputs > GLU_GRID_CAP, both remainders
+POOL_CAP_BWD = (1, 2049, 2051, 2, 3)                            # 2049 * 2051 inputs > GLU_GRID_CAP, both remainders, kh kw = 6
+POOL_REFUSED = ((2, 3, 6, 4, 2), (2, 4, 5, 2, 6), (2, 4, 6, 0, 2), (2, 4, 6, 2, 0), (0, 4, 6, 2, 2))   # H < kh, W < kw, kh = 0, kw = 0, NC = 0
+
+
+def forms_pool(bwd, NC, H, W, kh, kw):
+    if NC <= 0 or kh <= 0 or kw <= 0 or H < kh or W < kw:
+        return None
+    total = NC * H * W if bwd else NC * (H // kh) * (W // kw)
+    out = {"avgpool2_bwd_kernel" if bwd else "avgpool2_fwd_kernel"}
+    if total > GLU_GRID_CAP:
+        out.add("grid_capped")
+    if H % kh:
+        out.add("row_remainder")
+    if W % kw:
+        out.add("column_remainder")
+    if (kh * kw) & (kh * kw - 1):
+        out.add("inv_rounded")
+    return out
+
+
+def pool_data(NC, H, W, kh, kw, seed=0):
+    """(x (NC, H, W), gy (NC, H / kh, W / kw)) fp32, mixed scales and signs: the windows cancel"""
+    g = torch.Generator().manual_seed(100 * seed + NC + 3 * H + 5 * W + 7 * kh + kw)
+    return _mixed(NC * H * W, g).view(NC, H, W), _mixed(NC * (H // kh) * (W // kw), g).view(NC, H // kh, W // kw)
+
+
+def _windows(x, kh, kw):
+    NC, H, W = x.shape
+    OH, OW = H // kh, W // kw
+    return x[:, :OH * kh, :OW * kw].reshape(NC, OH, kh, OW, kw)
+
+
+def pool_fwd(x, kh, kw):
+    """(fp64 means over the kh x kw windows, remainder rows and columns ignored; bound)"""
+    w = _windows(x.double(), kh, kw)
+    n = kh * kw
+    return w.sum((2, 4)) / n, (n + 1) * _E.HALF * w.abs().sum((2, 4)) / n + _E.TINY
+
+
+def pool_bwd(gy, H, W, kh, kw):
+    """(gy / (kh kw) spread over its window, +0 in the remainder; bound: 0 where kh kw is a power of two)"""
+    NC, OH, OW = gy.shape
+    n = kh * kw
+    gx = torch.zeros(NC, H, W, dtype=torch.float64)
+    spread = (gy.double() / n).repeat_interleave(kh, 1).repeat_interleave(kw, 2)
+    gx[:, :OH * kh, :OW * kw] = spread
+    if n & (n - 1) == 0:
+        return gx, torch.zeros_like(gx)
+    bound = torch.zeros_like(gx)
+    bound[:, :OH * kh, :OW * kw] = 2 * _E.HALF * spread.abs() + _E.TINY
+    return gx, bound
+
+
+def pool_restate32(x, gy, kh, kw):
+    """float32: the window summed row by row from 0, times fl(1 / (kh kw)); gy times the same"""
+    w = _windows(x.float(), kh, kw)
+    acc = torch.zeros(w.shape[0], w.shape[1], w.shape[3])
+    for a in range(kh):
+        for b in range(kw):
+            acc = acc + w[:, :, a, :, b]
+    inv = torch.tensor(1.0) / torch.tensor(float(kh * kw))
+    return acc * inv, gy.float() * inv

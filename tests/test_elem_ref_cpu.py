@@ -331,3 +331,18 @@ def test_dropout_draw():
     assert bool(keep.all()) and torch.equal(out, x)
     out, keep = E.dropout(x, 0.5, 5)
     assert torch.equal(out[keep], x[keep] * 2) and bool((out[~keep] == 0).all())
+
+
+def test_zero_case_table_reaches_every_branch():
+    """rfx_zero (tests/test_gpu_elem_kernel.py::test_zero): head, vector body, tail, a second grid-stride iteration and the capped grid are
+    all reached, the byte counts that are no multiple of 4 and the odd byte bases are the refused ones"""
+    reached = set()
+    for nb in E.ZERO_BYTES + (E.ZERO_BYTES_CAP,):
+        for w in E.ZERO_WORD_OFFSETS:
+            f = E.forms_zero(nb, 4 * w)
+            assert (f is None) == (nb % 4 != 0), (nb, w)
+            reached |= f or set()
+        assert E.forms_zero(nb, 1) is None and E.forms_zero(nb, 6) is None
+    assert reached == {"head", "vec", "tail", "second_iteration", "grid_capped"}
+    assert E.forms_zero(0) == set() and E.forms_zero(4, 4) == {"head"} and E.forms_zero(16, 0) == {"vec"} and E.forms_zero(20, 8) == {"head", "tail"}
+    assert {0, 1, 3, 4, 15, 16, 17, 4099} <= set(E.ZERO_BYTES) and "grid_capped" in E.forms_zero(E.ZERO_BYTES_CAP, 4)

@@ -5,6 +5,8 @@ their constants come from are in elem_ref's docstring and DESIGN.md 4.21; none i
 Buffers: every input and output sits between NaN guards of 4096 elements, outputs are NaN-filled, workspaces are exactly the size the
 _ws / _slots call returns; inputs have to come back bit for bit; every case runs twice into fresh buffers: the same bits.  A failure
 names the entry point, the output and the element."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -540,3 +542,54 @@ def test_refusals_write_nothing():
     torch.cuda.synchronize()
     for b in bufs + [wsd] + ints:
         b.untouched()
+
+
+# ---- rfx_zero ------------------------------------------------------------------------------------------------------------------------
+def _zero(nbytes, byte_off, words):
+    """rfx_zero on `nbytes` at `byte_off` bytes into a NaN-filled guarded payload of `words` fp32 -> (return code, the buffer)"""
+    L, _, stream = api()
+    Z = Guarded(words, what="p")
+    rc = L.rfx_zero(ctypes.c_void_p(Z.t.data_ptr() + byte_off), nbytes, stream())
+    torch.cuda.synchronize()
+    return rc, Z
+
+
+def _zero_check(nbytes, byte_off):
+    forms = E.forms_zero(nbytes, byte_off)
+    pad = 8                                                    # payload words that stay NaN on either side of the zeroed run
+    lo = byte_off // 4
+    words = lo + -(-nbytes // 4) + pad
+    rc, Z = _zero(nbytes, byte_off, words)
+    if forms is None:
+        assert rc != 0, ("rfx_zero accepted", nbytes, "bytes at byte offset", byte_off)
+        Z.untouched()
+        return
+    assert rc == 0, ("rfx_zero", rc, nbytes, byte_off, sorted(forms))
+    Z.guards_intact()
+    b = bits(Z.t)
+    n = nbytes // 4
+    assert bool((b[lo:lo + n] == 0).all()), ("rfx_zero", nbytes, byte_off, sorted(forms), "a word of the run is not zero")
+    keep = torch.cat([b[:lo], b[lo + n:]])
+    assert bool((keep == Z.fill).all()), ("rfx_zero", nbytes, byte_off, sorted(forms), "wrote outside its run")
+
+
+@pytest.mark.parametrize("nbytes", E.ZERO_BYTES)
+def test_zero(nbytes):
+    """every byte count at bases 0 - 3 words past a 16-byte boundary (head of 0, 3, 2, 1 words) and at two odd byte offsets: a multiple of 4
+    at a 4-byte base becomes all-zero bits and nothing around it changes; anything else is refused and nothing is written"""
+    for off in [4 * w for w in E.ZERO_WORD_OFFSETS] + [1, 6]:
+        _zero_check(nbytes, off)
+    report("ELEM", f"rfx_zero nbytes={nbytes}", [] if nbytes % 4 else [0.0])
+
+
+def test_zero_past_the_grid_cap():
+    """one workgroup more than the 16384 of the cap would hold, from a base one word past a 16-byte boundary: head, body, tail"""
+    assert E.forms_zero(E.ZERO_BYTES_CAP, 4) == {"head", "vec", "tail", "second_iteration", "grid_capped"}
+    _zero_check(E.ZERO_BYTES_CAP, 4)
+    L, _, stream = api()
+    assert L.rfx_zero(None, 16, stream()) != 0 and L.rfx_zero(None, 0, stream()) == 0
+    Z = Guarded(8, what="p")
+    assert L.rfx_zero(Z.ptr(), -4, stream()) != 0
+    torch.cuda.synchronize()
+    Z.untouched()
+    report("ELEM", "rfx_zero cap", [0.0])

@@ -279,3 +279,92 @@ def test_ring_wrap_form_over_several_launches(prec):
     got = launch(H, T, Bn, prec, inputs)
     ref, fl, _ = references(H, T, Bn, prec, inputs, got, loose=False)
     tight(H, prec, Bn, None, ("out", "gates", "cstate", "dG"), got, ref, fl)
+
+
+# ---- the parameter glue: rfx_lstm_cat_params, rfx_lstm_grad_scatter ---------------------------------------------------
+from tests.kernel_harness import api, judge, report, twice  # noqa: E402
+
+
+def _glue_inputs(p):
+    return {k: Guarded(v.numel(), what=k, init=v) for k, v in p.items()}
+
+
+@pytest.mark.one_mode
+@pytest.mark.parametrize("H,Cin", R.GLUE_CASES)
+def test_cat_params(H, Cin):
+    """wcat = the two weight blocks bit for bit, bcat = [b_ih + b_hh ; b_ih_r + b_hh_r] rounded once; the six inputs come back unchanged"""
+    L, _, stream = api()
+    p, _, _ = R.glue_data(H, Cin)
+    ref = R.cat_params(p)
+    info = ("rfx_lstm_cat_params", (H, Cin), sorted(R.forms_glue(H, Cin)))
+
+    def run():
+        I = _glue_inputs(p)
+        W, B = Guarded(8 * H * Cin, what="wcat"), Guarded(8 * H, what="bcat")
+        rc = L.rfx_lstm_cat_params(*(I[k].ptr() for k in R.GLUE_PARAMS), H, Cin, W.ptr(), B.ptr(), stream())
+        torch.cuda.synchronize()
+        assert rc == 0, (rc, *info)
+        for b in I.values():
+            b.unchanged()
+        W.owned()
+        B.owned()
+        return {"wcat": W.cpu(), "bcat": B.cpu()}
+    got = twice(run)[0]
+    report("LSTM", f"rfx_lstm_cat_params H={H} Cin={Cin}", {k: judge(got[k], ref[k], 0, ctx=(*info, k)) for k in ("wcat", "bcat")})
+
+
+@pytest.mark.one_mode
+@pytest.mark.parametrize("H,Cin", R.GLUE_CASES)
+def test_grad_scatter(H, Cin):
+    """six gradient buffers that start from distinct non-zero contents end at g + d rounded once, both biases of a direction with the same
+    addend; dwcat / dbcat unchanged; a second call accumulates again"""
+    L, _, stream = api()
+    _, d, g0 = R.glue_data(H, Cin)
+    once = R.grad_scatter(g0, d)
+    second = R.grad_scatter({k: v.float() for k, v in once.items()}, d)
+    info = ("rfx_lstm_grad_scatter", (H, Cin), sorted(R.forms_glue(H, Cin)))
+
+    def run():
+        D = _glue_inputs(d)
+        G = {k: Guarded(g0[k].numel(), what="g_" + k, init=g0[k]) for k in R.GLUE_PARAMS}
+        out = {}
+        for call in ("first", "second"):
+            rc = L.rfx_lstm_grad_scatter(D["dwcat"].ptr(), D["dbcat"].ptr(), H, Cin, *(G[k].ptr() for k in R.GLUE_PARAMS), stream())
+            torch.cuda.synchronize()
+            assert rc == 0, (rc, call, *info)
+            for b in D.values():
+                b.unchanged()
+            for k in R.GLUE_PARAMS:
+                G[k].owned()
+                out[f"{call} {k}"] = G[k].cpu().clone()
+        return out
+    got = twice(run)[0]
+    ratios = [(call, judge(got[f"{call} {k}"], ref[k], 0, ctx=(*info, call, k))) for call, ref in (("first", once), ("second", second))
+              for k in R.GLUE_PARAMS]
+    report("LSTM", f"rfx_lstm_grad_scatter H={H} Cin={Cin}", ratios)
+
+
+@pytest.mark.one_mode
+def test_glue_refusals_write_nothing():
+    """each NULL pointer, H = 0 and Cin = 0: nonzero, and neither an output nor a gradient is touched"""
+    L, _, stream = api()
+    H, Cin = 3, 5
+    p, d, g0 = R.glue_data(H, Cin)
+    I, D = _glue_inputs(p), _glue_inputs(d)
+    W, B = Guarded(8 * H * Cin, what="wcat"), Guarded(8 * H, what="bcat")
+    G = {k: Guarded(g0[k].numel(), what="g_" + k, init=g0[k]) for k in R.GLUE_PARAMS}
+    cat = [I[k].ptr() for k in R.GLUE_PARAMS] + [H, Cin, W.ptr(), B.ptr()]
+    sc = [D["dwcat"].ptr(), D["dbcat"].ptr(), H, Cin] + [G[k].ptr() for k in R.GLUE_PARAMS]
+    bad_cat = [cat[:i] + [None] + cat[i + 1:] for i in (0, 1, 2, 3, 4, 5, 8, 9)] + [cat[:6] + [0, Cin] + cat[8:], cat[:6] + [H, 0] + cat[8:]]
+    bad_sc = [sc[:i] + [None] + sc[i + 1:] for i in (0, 1, 4, 5, 6, 7, 8, 9)] + [sc[:2] + [0, Cin] + sc[4:], sc[:2] + [H, 0] + sc[4:]]
+    assert R.forms_glue(0, Cin) is None and R.forms_glue(H, 0) is None
+    for a in bad_cat:
+        assert L.rfx_lstm_cat_params(*a, stream()) != 0, a
+    for a in bad_sc:
+        assert L.rfx_lstm_grad_scatter(*a, stream()) != 0, a
+    torch.cuda.synchronize()
+    W.untouched()
+    B.untouched()
+    for b in list(I.values()) + list(D.values()) + list(G.values()):
+        b.unchanged()
+    report("LSTM", "glue refusals", [])

@@ -15,12 +15,17 @@ After the call no output element is NaN and every guard holds its fill bit for b
 twice into fresh buffers: all outputs are the same bits.
 
 Cases above norm_ref.CAP elements draw their samples from a small pool (Case.pool): the device sees the full batch, the fp64
-reference is evaluated per pool entry, and the kernel has to return the same statistics bits for equal samples."""
+reference is evaluated per pool entry, and the kernel has to return the same statistics bits for equal samples.
+
+The tail of norm.hip -- rfx_glu_fwd / _bwd / _bwd_bf16 and rfx_avgpool2d_fwd / _bwd -- is at the end of this module: the same buffers
+through tests/kernel_harness.py (Guarded, judge per element, twice, report), the references and derived bounds of norm_ref (DESIGN.md
+4.28)."""
 import pytest
 import torch
 
 from tests import norm_ref as R
-from tests.kernel_harness import Guarded, stop_after_a_device_error, where  # noqa: F401
+from tests.kernel_harness import Guarded, api, report, stop_after_a_device_error, twice, where  # noqa: F401
+from tests.kernel_harness import judge as judge_elements
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_mode]          # no GEMM inside: the arithmetic modes agree
 
@@ -295,3 +300,183 @@ def test_handed_over_sums_through_the_wrapper():
         y = nnops.group_norm(x, 3, w, b, EPS, "gelu", sums=sums.cuda())
         q, i = R.worst(y.cpu(), ref["y"], R.tolerance("y", ref, mag, slack, fl))
         assert q <= 1.0, (tuple(sums.shape), where(i, tuple(y.shape)), q)
+
+
+# ---- plain GLU ------------------------------------------------------------------------------------------------------------------------
+def _glu_call(entry, N, C, S, x, gy, offs=(0, 0, 0)):
+    """one call into fresh guarded buffers -> (return code, the output buffer); the inputs have to come back bit for bit"""
+    L, _, stream = api()
+    xdt = torch.bfloat16 if entry == "bwd_bf16" else torch.float32
+    Co = C // 2
+    X = Guarded(max(N, 0) * C * S, xdt, "x", x, offs[0])
+    if entry == "fwd":
+        O = Guarded(max(N, 0) * Co * S, what="y", off=offs[1])
+        rc = L.rfx_glu_fwd(X.ptr(), O.ptr(), N, C, S, stream())
+        ins = (X,)
+    else:
+        G = Guarded(max(N, 0) * Co * S, what="gy", init=gy, off=offs[2])
+        O = Guarded(max(N, 0) * C * S, xdt, "gx", off=offs[1])
+        fn = L.rfx_glu_bwd_bf16 if entry == "bwd_bf16" else L.rfx_glu_bwd
+        rc = fn(X.ptr(), G.ptr(), O.ptr(), N, C, S, stream())
+        ins = (X, G)
+    torch.cuda.synchronize()
+    for b in ins:
+        b.unchanged()
+    return rc, O
+
+
+def _glu_case(entry, N, C, S, offs=(0, 0, 0)):
+    """-> (the output, largest error / bound)"""
+    x16 = entry == "bwd_bf16"
+    x, gy = R.glu_data(N, C, S, x16=x16)
+    forms = R.forms_glu(entry, N, C, S, offs)
+    name = "y" if entry == "fwd" else "gx"
+    info = ("rfx_glu_" + entry, (N, C, S), "offsets", offs, sorted(forms))
+
+    def run():
+        rc, O = _glu_call(entry, N, C, S, x, gy, offs)
+        assert rc == 0, (rc, *info)
+        O.owned()
+        return {name: O.cpu()}
+    got = twice(run)[0][name]
+    ref = R.glu(x, None if entry == "fwd" else gy)[name]
+    bound = R.glu_bounds(x, None if entry == "fwd" else gy)[name]
+    if x16:
+        bound = R.bf16_store_bound(ref, bound)
+    return got, judge_elements(got, ref, bound, exact="value", ctx=info)
+
+
+@pytest.mark.parametrize("entry", R.GLU_ENTRIES)
+@pytest.mark.parametrize("shape", R.GLU_ROW_CASES, ids=str)
+def test_glu_row_kernels(shape, entry):
+    """(C / 2) S a multiple of 4 and every base aligned: one vector, a second chunk of one vector (the o >= L exit), a last workgroup
+    with an idle wave, two full chunks"""
+    assert any(f.endswith(":rows") for f in R.forms_glu(entry, *shape))
+    report("NORM", f"rfx_glu_{entry} rows {shape}", [_glu_case(entry, *shape)[1]])
+
+
+@pytest.mark.parametrize("entry", ("fwd", "bwd"))
+@pytest.mark.parametrize("shape", R.GLU_FLAT_CASES, ids=str)
+def test_glu_flat_kernels(shape, entry):
+    assert f"glu_{entry}_kernel:flat" in R.forms_glu(entry, *shape)
+    report("NORM", f"rfx_glu_{entry} flat {shape}", [_glu_case(entry, *shape)[1]])
+
+
+@pytest.mark.parametrize("entry", ("fwd", "bwd"))
+@pytest.mark.parametrize("shape", R.GLU_ROW_CASES, ids=str)
+def test_glu_misaligned_base_takes_the_flat_kernel(shape, entry):
+    """each base in turn one element past a 16-byte boundary: the flat kernel, the same bound; and, the flat and the row kernel being
+    the same arithmetic, the aligned run's bits"""
+    aligned = _glu_case(entry, *shape)[0]
+    ratios = []
+    for i in range(2 if entry == "fwd" else 3):
+        offs = tuple(int(j == i) for j in range(3))
+        assert R.forms_glu(entry, *shape, offs) == {f"glu_{entry}_kernel:flat"}
+        got, q = _glu_case(entry, *shape, offs)
+        ratios.append(q)
+        assert torch.equal(got.view(torch.int32), aligned.view(torch.int32)), (entry, shape, offs, "differs from the aligned run")
+    report("NORM", f"rfx_glu_{entry} misaligned {shape}", ratios)
+
+
+@pytest.mark.parametrize("shape", R.GLU_CAP_CASES, ids=str)
+def test_glu_past_the_grid_cap(shape):
+    """more than 4096 x 1024 outputs: the flat kernels' grid-stride loop runs again, the row kernels' grid grows"""
+    ratios = []
+    for entry in R.GLU_ENTRIES:
+        forms = R.forms_glu(entry, *shape)
+        if forms is None:
+            continue
+        assert shape[0] * (shape[1] // 2) * shape[2] > R.GLU_GRID_CAP
+        ratios.append((entry, _glu_case(entry, *shape)[1]))
+    assert ratios
+    report("NORM", f"rfx_glu cap {shape}", ratios)
+
+
+def test_glu_refusals_write_nothing():
+    """the 16-bit form has no flat kernel: every flat shape and every misaligned base is refused; so are an odd C, N = 0 and NULL"""
+    L, _, stream = api()
+    for shape in R.GLU_FLAT_CASES:
+        assert R.forms_glu("bwd_bf16", *shape) is None
+        x, gy = R.glu_data(*shape, x16=True)
+        rc, O = _glu_call("bwd_bf16", *shape, x, gy)
+        assert rc != 0, shape
+        O.untouched()
+    shape = R.GLU_ROW_CASES[1]
+    x, gy = R.glu_data(*shape, x16=True)
+    for offs in ((1, 0, 0), (2, 0, 0), (0, 1, 0), (0, 2, 0), (0, 0, 1), (0, 0, 2)):
+        assert R.forms_glu("bwd_bf16", *shape, offs) is None
+        rc, O = _glu_call("bwd_bf16", *shape, x, gy, offs)
+        assert rc != 0, offs
+        O.untouched()
+    for entry in R.GLU_ENTRIES:
+        for (N, C, S) in ((2, 3, 4), (0, 2, 4), (2, 0, 4), (2, 2, 0)):
+            assert R.forms_glu(entry, N, C, S) is None
+            rc, O = _glu_call(entry, N, C, S, torch.ones(N * C * S), torch.ones(N * (C // 2) * S))
+            assert rc != 0, (entry, N, C, S)
+            O.untouched()
+    O = Guarded(16, what="y")
+    X = Guarded(32, what="x", init=torch.ones(32))
+    assert L.rfx_glu_fwd(None, O.ptr(), 2, 4, 4, stream()) != 0 and L.rfx_glu_fwd(X.ptr(), None, 2, 4, 4, stream()) != 0
+    G = Guarded(32, what="gx")
+    assert L.rfx_glu_bwd(X.ptr(), None, G.ptr(), 2, 4, 4, stream()) != 0 and L.rfx_glu_bwd(None, X.ptr(), G.ptr(), 2, 4, 4, stream()) != 0
+    assert L.rfx_glu_bwd_bf16(X.ptr(), None, G.ptr(), 2, 4, 4, stream()) != 0
+    torch.cuda.synchronize()
+    O.untouched()
+    G.untouched()
+    X.unchanged()
+    report("NORM", "rfx_glu refusals", [])
+
+
+# ---- average pooling ------------------------------------------------------------------------------------------------------------------
+def _pool_call(bwd, NC, H, W, kh, kw, src, n_out):
+    L, _, stream = api()
+    I = Guarded(src.numel(), what="gy" if bwd else "x", init=src)
+    O = Guarded(n_out, what="gx" if bwd else "y")
+    rc = (L.rfx_avgpool2d_bwd if bwd else L.rfx_avgpool2d_fwd)(I.ptr(), O.ptr(), NC, H, W, kh, kw, stream())
+    torch.cuda.synchronize()
+    I.unchanged()
+    return rc, O
+
+
+def _pool_case(bwd, NC, H, W, kh, kw):
+    x, gy = R.pool_data(NC, H, W, kh, kw)
+    info = ("rfx_avgpool2d_" + ("bwd" if bwd else "fwd"), (NC, H, W, kh, kw), sorted(R.forms_pool(bwd, NC, H, W, kh, kw)))
+    ref, bound = R.pool_bwd(gy, H, W, kh, kw) if bwd else R.pool_fwd(x, kh, kw)
+
+    def run():
+        rc, O = _pool_call(bwd, NC, H, W, kh, kw, gy if bwd else x, ref.numel())
+        assert rc == 0, (rc, *info)
+        O.owned()
+        return {"out": O.cpu()}
+    return judge_elements(twice(run)[0]["out"], ref, bound, ctx=info)
+
+
+@pytest.mark.parametrize("shape", R.POOL_CASES, ids=str)
+def test_avgpool(shape):
+    """forward: the window mean inside its counted half-ulps; backward: bit for bit where kh kw is a power of two (+0 in the remainder
+    rows and columns everywhere), two half-ulps otherwise"""
+    report("NORM", f"rfx_avgpool2d {shape}", [("fwd", _pool_case(False, *shape)), ("bwd", _pool_case(True, *shape))])
+
+
+def test_avgpool_past_the_grid_cap():
+    assert "grid_capped" in R.forms_pool(False, *R.POOL_CAP_FWD) and "grid_capped" in R.forms_pool(True, *R.POOL_CAP_BWD)
+    report("NORM", "rfx_avgpool2d cap", [("fwd", _pool_case(False, *R.POOL_CAP_FWD)), ("bwd", _pool_case(True, *R.POOL_CAP_BWD))])
+
+
+def test_avgpool_refusals_write_nothing():
+    L, _, stream = api()
+    for shape in R.POOL_REFUSED:
+        NC, H, W, kh, kw = shape
+        assert R.forms_pool(False, *shape) is None and R.forms_pool(True, *shape) is None
+        for bwd in (False, True):
+            rc, O = _pool_call(bwd, NC, H, W, kh, kw, torch.ones(64), 64)
+            assert rc != 0, (shape, bwd)
+            O.untouched()
+    O = Guarded(64, what="out")
+    I = Guarded(64, what="in", init=torch.ones(64))
+    for fn in (L.rfx_avgpool2d_fwd, L.rfx_avgpool2d_bwd):
+        assert fn(None, O.ptr(), 1, 4, 4, 2, 2, stream()) != 0 and fn(I.ptr(), None, 1, 4, 4, 2, 2, stream()) != 0
+    torch.cuda.synchronize()
+    O.untouched()
+    I.unchanged()
+    report("NORM", "rfx_avgpool2d refusals", [])

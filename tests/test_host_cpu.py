@@ -567,3 +567,41 @@ def test_flat_layout_follows_forward_use_order_and_buckets_complete_in_backward_
     assert names[id(order[0])].startswith("time_encoder.0") and names[id(order[-1])].startswith("time_decoder.4")
     with pytest.raises(ValueError):
         FlatParams(plist, allow_cpu=True, layout=order[:-1])
+
+
+def test_every_entry_point_is_pinned():
+    """tests/abi_census.py: its keys are the ABI, every value is an existing tests/test_gpu_*.py (this module for host-only queries), and
+    the entry's name stands in that module, in a tests/*_ref.py it imports or in the remfx_amd wrapper it imports -- for the entries
+    no test names, in the wrapper VIA records"""
+    from remfx_amd import _lib
+    from tests import abi_census as A
+    assert set(A.PINNED_BY) == set(_lib.SIGNATURES), set(A.PINNED_BY) ^ set(_lib.SIGNATURES)
+    here = os.path.join(ROOT, "tests")
+    for entry, module in A.PINNED_BY.items():
+        assert re.fullmatch(r"test_gpu_\w+\.py", module) or module == A.HOST_ONLY, (entry, module)
+        assert os.path.exists(os.path.join(here, module)), (entry, module)
+        found = A.names(entry, module)
+        assert found, (entry, "is not named by", module, "or by anything it imports")
+        if entry in A.VIA:
+            assert A.VIA[entry][0] in found, (entry, found)
+        else:
+            assert any(not f.startswith("remfx_amd/") for f in found), (entry, "only named by a wrapper: record it in VIA", found)
+    assert set(A.VIA) <= set(A.PINNED_BY)
+    # the host-only queries are called here, without a device
+    for entry, module in A.PINNED_BY.items():
+        if module == A.HOST_ONLY:
+            assert entry in ("rfx_abi_version", "rfx_gemm_pick_r", "rfx_lstm_ws_bytes"), entry
+
+
+def test_lstm_workspace_bytes():
+    """rfx_lstm_ws_bytes, a host-only query: 256 bytes of flags, 64 bytes of counters for each of the 768 / (H / 32) clusters the
+    workspace is laid out for, and per cluster two exchange buffers of (H / 32)^2 tiles of 4096 bytes; H has to be a multiple of 32 up
+    to 512"""
+    from remfx_amd import _lib
+    L = _lib.lib()
+    for H in range(32, 513, 32):
+        nwc = H // 32
+        clusters = 768 // nwc
+        assert L.rfx_lstm_ws_bytes(H) == 256 + clusters * 64 + clusters * 2 * nwc * nwc * 4096, H
+    for H in (0, -32, 16, 33, 544, 1024):
+        assert L.rfx_lstm_ws_bytes(H) == -1, H

@@ -128,3 +128,43 @@ def test_mutation_clears_the_bound(H, T, Bn, mutation, mode, sweep):
     assert ratio > 1.0, (mutation, got, fl[sweep])
     if mutation == "reverse_starts_late":                                       # ... and only where the fault is
         assert all(got[k] == (0.0, 0.0) for k in got if k.endswith(".d0"))
+
+
+# ---- the parameter glue (rfx_lstm_cat_params, rfx_lstm_grad_scatter) ----------------------------------------------------------------
+def _once(t64):
+    return t64.float()
+
+
+@pytest.mark.parametrize("H,Cin", R.GLUE_CASES)
+def test_glue_reference_is_cat_and_add(H, Cin):
+    p, d, g0 = R.glue_data(H, Cin)
+    ref = R.cat_params(p)
+    assert torch.equal(_once(ref["wcat"]).view(8 * H, Cin), torch.cat([p["w_ih"].view(4 * H, Cin), p["w_ih_r"].view(4 * H, Cin)], 0))
+    assert torch.equal(_once(ref["bcat"]), torch.cat([p["b_ih"] + p["b_hh"], p["b_ih_r"] + p["b_hh_r"]]))
+    after = R.grad_scatter(g0, d)
+    dw, db = d["dwcat"].view(2, 4 * H * Cin), d["dbcat"].view(2, 4 * H)
+    for k, add in (("w_ih", dw[0]), ("w_ih_r", dw[1]), ("b_ih", db[0]), ("b_hh", db[0]), ("b_ih_r", db[1]), ("b_hh_r", db[1])):
+        assert torch.equal(_once(after[k]), g0[k] + add), k
+    # every buffer differs from every other of its size and nothing the gradients start from is zero
+    for group in (("w_ih", "w_ih_r"), ("b_ih", "b_hh", "b_ih_r", "b_hh_r")):
+        for i, a in enumerate(group):
+            assert bool((g0[a] != 0).all())
+            for b in group[i + 1:]:
+                assert not torch.equal(p[a], p[b]) and not torch.equal(g0[a], g0[b])
+
+
+@pytest.mark.parametrize("mutation", R.GLUE_MUTATIONS)
+def test_glue_mutation_is_not_one_rounding_of_the_reference(mutation):
+    """bound 0 = the fp32 rounding of the fp64 value, bit for bit: each planted fault differs from it"""
+    H, Cin = 3, 5
+    p, d, g0 = R.glue_data(H, Cin)
+    same = lambda a, b: all(torch.equal(_once(a[k]), _once(b[k])) for k in a)            # noqa: E731
+    assert not (same(R.cat_params(p, mutation), R.cat_params(p)) and same(R.grad_scatter(g0, d, mutation), R.grad_scatter(g0, d)))
+
+
+def test_glue_case_table_reaches_the_stride_loop():
+    forms = {c: R.forms_glue(*c) for c in R.GLUE_CASES}
+    assert "stride_loop" in forms[(192, 192)] and 2 * 4 * 192 * 192 == 294912 > R.GLUE_GRID
+    assert all("stride_loop" not in forms[c] for c in R.GLUE_CASES[:3])
+    assert "ragged_last_block" in forms[(1, 1)] and "ragged_last_block" in forms[(3, 5)] and "ragged_last_block" not in forms[(64, 48)]
+    assert R.forms_glue(0, 4) is None and R.forms_glue(4, 0) is None

@@ -262,3 +262,170 @@ def test_workspace_sizes_by_hand():
     assert (R.stat_chunks(6, 4100, 3), R.stat_chunks(4, 4096, 2), R.stat_chunks(8, 12, 8), R.stat_chunks(3, 1367, 1)) == (3, 2, 1, 2)
     # BatchNorm: one slot per (sample, chunk)
     assert (R.bn_stat_slots(70, 231), R.bn_stat_slots(3, 4099), R.bn_stat_slots(65540, 4)) == (70, 6, 65540)
+
+
+# ---- plain GLU and average pooling (the tail of norm.hip) -----------------------------------------------------------------------------
+GLU_TABLE = R.GLU_ROW_CASES + R.GLU_FLAT_CASES + R.GLU_CAP_CASES
+
+
+def test_glu_reference_against_float64_autograd():
+    x, gy = R.glu_data(3, 6, 43)
+    xr = x.double().clone().requires_grad_(True)
+    y = F.glu(xr, 1)
+    y.backward(gy.double())
+    sane = x.abs() < 50                                        # autograd's sigmoid' underflows differently at the planted +-88 ... 1e4
+    assert _rel(R.glu(x)["y"], y.detach()) <= 1e-12
+    assert _rel(torch.where(sane, R.glu(x, gy)["gx"], 0.0), torch.where(sane, xr.grad, 0.0)) <= 1e-12
+
+
+def test_glu_floors_are_below_the_table():
+    """the fp32 restatement 1 / (1 + exp(-v)) (CPU libm) over every case and both storage types: its error in units of eps32 x magnitude is no
+    larger than GLU_FLOOR, the bound's K is 8 floor + 4 at least, and the restatement itself passes the bound"""
+    from tests import elem_ref as E
+    worst = {}
+    for (N, C, S) in GLU_TABLE:
+        for x16 in (False, True):
+            x, gy = R.glu_data(N, C, S, x16=x16)
+            for k, v in R.glu_floors(x, gy).items():
+                worst[k] = max(worst.get(k, 0.0), v)
+            if N * C * S <= 100000:
+                for ref, b, r32 in ((R.glu(x), R.glu_bounds(x), R.glu_restate32(x)), (R.glu(x, gy), R.glu_bounds(x, gy), R.glu_restate32(x, gy))):
+                    for name in ref:
+                        assert R.worst(r32[name], ref[name], b[name])[0] <= 1.0, (N, C, S, x16, name)
+    print("\nGLU floors (eps32 x magnitude), measured on the CPU restatement:", {k: round(v, 2) for k, v in worst.items()})
+    for k, v in worst.items():
+        assert v <= R.GLU_FLOOR[k], (k, v)
+    assert E.k_of("sigmoid") + 1 >= 8 * R.GLU_FLOOR["y"] + 4 and E.k_of("sigmoid") + 1 >= 8 * R.GLU_FLOOR["da"] + 4
+    assert E.k_of("sigmoid_grad") + 2 >= 8 * R.GLU_FLOOR["db"] + 4
+
+
+def test_glu_inputs_hold_what_the_cases_need():
+    x, gy = R.glu_data(2, 4, 130)
+    a, b = x[:, :2].reshape(-1), x[:, 2:].reshape(-1)
+    for v in R.GLU_SPECIALS:
+        assert bool((b == torch.tensor(v).float()).any()), v
+    assert bool((b.view(torch.int32) == torch.tensor(-0.0).view(torch.int32)).any())
+    assert float(a.abs().max()) > 100 and 0 < float(a[a != 0].abs().min()) < 1e-3 and bool((a == 0).any()) and bool((gy == 0).any())
+    assert float(b.abs()[len(R.GLU_SPECIALS):].max()) <= 12
+    xb, _ = R.glu_data(2, 4, 130, x16=True)
+    assert torch.equal(R.bf16_rne(xb), xb)
+
+
+@pytest.mark.parametrize("fault", ["halves_swapped", "gate_stride_S", "one_minus_sigmoid_dropped"])
+def test_glu_bound_rejects_planted_fault(fault):
+    """what the per-element bound sees, on the fp32 restatement as the stand-in for a kernel"""
+    N, C, S = 2, 6, 43
+    x, gy = R.glu_data(N, C, S)
+    Co = C // 2
+    if fault == "halves_swapped":
+        bad = R.glu_restate32(torch.cat([x[:, Co:], x[:, :Co]], 1))["y"]
+        ref, b = R.glu(x)["y"], R.glu_bounds(x)["y"]
+    elif fault == "gate_stride_S":                             # the gate read one channel after the value instead of Co channels
+        xs = x.clone()
+        xs[:, Co:] = x[:, 1:Co + 1]
+        bad = R.glu_restate32(xs)["y"]
+        ref, b = R.glu(x)["y"], R.glu_bounds(x)["y"]
+    else:
+        s = 1.0 / (1.0 + torch.exp(-x[:, Co:]))
+        bad = torch.cat([gy * s, gy * x[:, :Co] * s], 1)
+        ref, b = R.glu(x, gy)["gx"], R.glu_bounds(x, gy)["gx"]
+    assert R.worst(bad, ref, b)[0] > 1.0
+
+
+def test_glu_bf16_store_is_judged_per_element():
+    x, gy = R.glu_data(2, 4, 130, x16=True)
+    ref, b32 = R.glu(x, gy)["gx"], R.glu_bounds(x, gy)["gx"]
+    f32 = R.glu_restate32(x, gy)["gx"]
+    tol = R.bf16_store_bound(ref, b32)
+    assert R.worst(R.bf16_rne(f32), ref, tol)[0] <= 1.0
+    trunc = (f32.contiguous().view(torch.int32) & -65536).view(torch.float32)
+    assert R.worst(trunc, ref, tol)[0] > 1.0
+
+
+def test_glu_case_table_reaches_every_form():
+    reached = set()
+    for entry in R.GLU_ENTRIES:
+        for c in R.GLU_ROW_CASES + R.GLU_CAP_CASES[1:]:
+            f = R.forms_glu(entry, *c)
+            assert f is not None and any(s.endswith(":rows") for s in f), (entry, c)
+            reached |= f
+            if entry != "bwd_bf16":                            # one element past the 16-byte boundary: the flat kernel
+                for i in range(2 if entry == "fwd" else 3):
+                    offs = tuple(int(j == i) for j in range(3))
+                    assert R.forms_glu(entry, *c, offs) == {f"glu_{entry}_kernel:flat"} | ({"flat:grid_capped"} if c[0] * c[1] // 2 * c[2] > R.GLU_GRID_CAP else set())
+                    reached |= R.forms_glu(entry, *c, offs)
+            else:                                              # 8-byte x / gx: two bf16 elements still run, one does not; gy needs 16
+                assert R.forms_glu(entry, *c, (4, 4, 4)) == f
+                for offs in ((1, 0, 0), (2, 0, 0), (0, 1, 0), (0, 0, 1), (0, 0, 2)):
+                    assert R.forms_glu(entry, *c, offs) is None, (c, offs)
+        for c in R.GLU_FLAT_CASES + R.GLU_CAP_CASES[:1]:
+            f = R.forms_glu(entry, *c)
+            if entry == "bwd_bf16":
+                assert f is None
+            else:
+                assert f is not None and f"glu_{entry}_kernel:flat" in f
+                reached |= f
+    assert reached == {"glu_fwd_kernel:flat", "glu_bwd_kernel:flat", "glu_fwd_rows_kernel<f32>:rows", "glu_bwd_rows_kernel<f32>:rows",
+                       "glu_bwd_rows_kernel<bf16>:rows", "flat:grid_capped", "rows:ragged_chunk", "rows:several_chunks", "rows:idle_wave"}
+    # by hand: (2, 4, 130) has L = 260, two chunks per sample, the second holds one vector
+    assert R.forms_glu("fwd", 2, 4, 130) == {"glu_fwd_rows_kernel<f32>:rows", "rows:ragged_chunk", "rows:several_chunks"}
+    # (5, 6, 256): 5 x 3 = 15 items, the fourth wave of the last workgroup has none; (2, 4, 130): 4 items, one full workgroup
+    assert "rows:idle_wave" in R.forms_glu("bwd", 5, 6, 256) and "rows:idle_wave" not in R.forms_glu("bwd", 2, 4, 130)
+    assert R.forms_glu("fwd", 2, 3, 4) is None and R.forms_glu("fwd", 0, 2, 4) is None
+
+
+POOL_TABLE = R.POOL_CASES + (R.POOL_CAP_FWD, R.POOL_CAP_BWD)
+
+
+def test_pool_reference_against_float64_autograd():
+    for (NC, H, W, kh, kw) in R.POOL_CASES:
+        x, gy = R.pool_data(NC, H, W, kh, kw)
+        xr = x.double().clone().requires_grad_(True)
+        y = F.avg_pool2d(xr[None], (kh, kw))[0]
+        y.backward(gy.double())
+        assert _rel(R.pool_fwd(x, kh, kw)[0], y.detach()) <= 1e-12
+        gx, bound = R.pool_bwd(gy, H, W, kh, kw)
+        assert _rel(gx, xr.grad) <= 1e-12
+        assert bool((bound[:, (H // kh) * kh:] == 0).all()) and bool((bound[:, :, (W // kw) * kw:] == 0).all())
+
+
+def test_pool_restatement_is_inside_the_derived_bound():
+    """the fp32 sum in the kernel's order times fl(1 / (kh kw)): inside the counted bound at every case (the largest ratio is printed);
+    bit for bit the reference where kh kw is a power of two"""
+    worst = {"fwd": 0.0, "bwd": 0.0}
+    for (NC, H, W, kh, kw) in POOL_TABLE:
+        x, gy = R.pool_data(NC, H, W, kh, kw)
+        y32, g32 = R.pool_restate32(x, gy, kh, kw)
+        ref, b = R.pool_fwd(x, kh, kw)
+        q = R.worst(y32, ref, b)[0]
+        worst["fwd"] = max(worst["fwd"], q)
+        n = kh * kw
+        gref = gy.double() / n
+        if n & (n - 1) == 0:
+            assert torch.equal(g32, gref.float())
+        else:
+            worst["bwd"] = max(worst["bwd"], R.worst(g32, gref, 2 * 2.0 ** -24 * gref.abs() + 2.0 ** -149)[0])
+    print("\npooling, CPU restatement, largest error / bound:", {k: round(v, 3) for k, v in worst.items()})
+    assert worst["fwd"] <= 1.0 and worst["bwd"] <= 1.0
+
+
+def test_pool_bound_rejects_planted_faults():
+    NC, H, W, kh, kw = 2, 7, 9, 3, 2
+    x, gy = R.pool_data(NC, H, W, kh, kw)
+    ref, b = R.pool_fwd(x, kh, kw)
+    y32, _ = R.pool_restate32(x, gy, kh, kw)
+    assert R.worst(y32 * kw, ref, b)[0] > 1.0                  # inv = 1 / kh
+    wrong = F.avg_pool2d(x[None], (kw, kh))[0]                 # oh = h / kw: the window transposed
+    assert wrong.shape != ref.shape or R.worst(wrong, ref, b)[0] > 1.0
+
+
+def test_pool_case_table_reaches_every_form():
+    fw, bw = set(), set()
+    for c in POOL_TABLE:
+        fw |= R.forms_pool(False, *c)
+        bw |= R.forms_pool(True, *c)
+    assert "grid_capped" in R.forms_pool(False, *R.POOL_CAP_FWD) and "grid_capped" in R.forms_pool(True, *R.POOL_CAP_BWD)
+    assert fw == {"avgpool2_fwd_kernel", "grid_capped", "row_remainder", "column_remainder", "inv_rounded"}
+    assert bw == {"avgpool2_bwd_kernel", "grid_capped", "row_remainder", "column_remainder", "inv_rounded"}
+    assert all(R.forms_pool(b, *c) is None for c in R.POOL_REFUSED for b in (False, True))
+    assert "grid_capped" not in set().union(*(R.forms_pool(True, *c) for c in R.POOL_CASES))

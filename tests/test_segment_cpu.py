@@ -136,3 +136,68 @@ def test_label_timeline_runs():
     assert "0.00 s" in lines[0] and "2.00 s" in lines[0] and lines[0].endswith("R")
     assert "2.00 s" in lines[1] and "2.50 s" in lines[1] and lines[1].endswith("X, P")
     assert "4.00 s" in lines[2] and lines[2].endswith("none")
+
+
+# ---- the kernel-side case table of tests/test_gpu_segment_kernel.py -------------------------------------------------
+def test_merge_bound_holds_for_the_fp32_restatement_of_the_kernel_order():
+    """the per-element bound against float32 numpy, the sum in the kernel's order (products rounded: no FMA), over the whole table; the
+    largest error / bound is printed"""
+    worst = 0.0
+    for (B, C, T, L, overlap, lead, trail) in ref.CASES:
+        y = ref.merge_input(B, C, T, L, overlap, lead, trail)
+        want = ref.merge(y, T, L, overlap, lead, trail)
+        bound = ref.merge_bound(y, T, L, overlap, lead, trail)
+        assert bound.shape == want.shape and (bound > 0).all()
+        q = float((np.abs(ref.merge_restate32(y, T, L, overlap, lead, trail).astype(np.float64) - want) / bound).max())
+        assert q <= 1.0, ((B, C, T, L, overlap, lead, trail), q)
+        worst = max(worst, q)
+    print("\nsegment merge, CPU restatement, largest error / bound:", round(worst, 3))
+
+
+@pytest.mark.parametrize("fault,case", [("weights_min_j", ref.CASES[1]), ("tail_after_last", ref.CASES[1]), ("tail_twice", ref.CASES[0])])
+def test_merge_bound_rejects_planted_faults_the_global_bound_accepts(fault, case):
+    """clip i scaled by 1, 1e3, 1e-3: a weight off by one, the tail clip taken one sample late, a clip counted twice are outside the
+    per-element bound; tests/test_gpu_segment.py's global (max_cover + 3) half-ulps of max |y| is what they are compared with"""
+    B, C, T, L, overlap, lead, trail = case
+    y = ref.merge_input(B, C, T, L, overlap, lead, trail)
+    want, bound = ref.merge(y, T, L, overlap, lead, trail), ref.merge_bound(y, T, L, overlap, lead, trail)
+    bad = ref.merge_restate32(y, T, L, overlap, lead, trail, mutate=fault).astype(np.float64)
+    err = np.abs(bad - want)
+    assert not (err <= bound).all()
+    cnt, _ = ref.cover(T, L, overlap, lead, trail)
+    quiet = np.abs(want) < 1e-2 * np.abs(y).max()              # where a loud clip has faded out: the global bound is blind there
+    assert quiet.any()
+    glob = (cnt.max() + 3) * 2.0 ** -24 * np.abs(y).max()
+    assert (bound[quiet] < glob).all()
+
+
+def test_grouped_layout_round_trip():
+    B, S, C, n = 2, 3, 3, 5
+    a = np.arange(B * C * S * n, dtype=np.float32).reshape(B * C * S, n)
+    g = ref.group(a, B, S, C)
+    assert np.array_equal(ref.ungroup(g, B, S, C), a)
+    # clip (b = 1, segment 2, channel 0) sits at row (1 * S + 2) * C + 0 and came from row (1 * C + 0) * S + 2
+    assert np.array_equal(g[(1 * S + 2) * C + 0], a[(1 * C + 0) * S + 2])
+
+
+def test_kernel_case_table_reaches_both_forms_and_every_chunk_edge():
+    seen = {"split": set(), "merge": set()}
+    steer = {"split": set(), "merge": set()}
+    for (B, C, T, L, overlap, lead, trail) in ref.CASES:
+        assert T <= 4096
+        for kind, args in (("split", (T, L, overlap)), ("merge", (T, L, overlap, lead, trail))):
+            f = ref.forms(kind, *args)
+            seen[kind].add(f)
+            steer[kind] |= ref.steering(kind, *args)
+            if f == "vec":                                     # a base one sample past the boundary: dword
+                assert ref.forms(kind, *args, in_off=1) == "dword" and ref.forms(kind, *args, out_off=1) == "dword"
+    assert seen == {"split": {"vec", "dword"}, "merge": {"vec", "dword"}}
+    assert steer["split"] == {"chunks=1", "chunks>1", "ragged_chunk", "exact_chunk", "zero_fill", "tail_on_grid", "tail_off_grid"}
+    assert steer["merge"] == {"chunks=1", "chunks>1", "ragged_chunk", "exact_chunk", "tail_on_grid", "tail_off_grid"}
+    assert {252, 256, 260} <= {c[3] for c in ref.CASES}
+    assert max(int(ref.cover(*c[2:])[0].max()) for c in ref.CASES) == 4
+    assert {c[1] for c in ref.CASES} == {1, 2, 3}
+    # by hand: lengths multiples of 4 and the hop not -> dword; L' = 491 -> merge dword while split stays vec
+    assert ref.forms("split", 1000, 256, 62) == "dword" and ref.forms("merge", 1280, 512, 128, 21, 0) == "dword"
+    assert ref.forms("split", 1280, 512, 128) == "vec"
+    assert ref.forms("merge", 1000, 64, 16, 9, 8) is None and ref.forms("merge", 10, 64, 16, 10, 0) is None
