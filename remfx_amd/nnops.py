@@ -39,6 +39,8 @@ class _GroupNormFn(torch.autograd.Function):
         if not x16:
             ops._req(x, "x")
         x = x.contiguous()
+        gamma, beta = gamma.contiguous(), beta.contiguous()          # read (and their gradients written) as dense vectors
+        scale = scale.contiguous() if scale is not None else None
         N, Cc = x.shape[0], x.shape[1]
         S = x.numel() // (N * Cc)
         oshape = list(x.shape)
@@ -47,6 +49,10 @@ class _GroupNormFn(torch.autograd.Function):
         y = torch.empty(oshape, device=x.device, dtype=torch.float32)
         mean = torch.empty(N * groups, device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
+        if sums is not None:
+            if not (sums.is_cuda and sums.dtype == torch.float64):
+                raise ValueError(f"group_norm: sums are fp64 on the GPU (got {sums.dtype}, {sums.device})")
+            sums = sums.contiguous()                   # read as dense (N * groups [, slots], 2)
         given = (sums.shape[1] if sums.dim() == 3 else 1) if sums is not None else 0     # number of partial-sum slots
         if sums is None:
             # the statistics kernel stores one pair per (group, chunk) into its own slot: no zero fill, no atomics
@@ -54,6 +60,7 @@ class _GroupNormFn(torch.autograd.Function):
             sums = torch.empty(N * groups * 2 * max(chunks, 1), device=x.device, dtype=torch.float64)
             given = -1
         if res is not None:
+            ops._req(res, "res")
             res = res.contiguous()
         launch("rfx_groupnorm_fwd_x16" if x16 else "rfx_groupnorm_fwd", x, gamma, beta, N, Cc, S, groups, eps, mode,
                res, scale, sums, given, mean, rstd, y)
@@ -65,6 +72,7 @@ class _GroupNormFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, gamma, beta, mean, rstd, scale = ctx.saved_tensors
         N, Cc, S, groups, mode = ctx.cfg
+        ops._req(gy, "gy")
         gy = gy.contiguous()
         dx = torch.empty_like(x)
         # parameter gradients: straight into the flat gradient buffer when a GradSink is armed and this is the parameter's first
@@ -79,9 +87,11 @@ class _GroupNormFn(torch.autograd.Function):
         with sw or ops.NO_SINK:
             launch("rfx_groupnorm_bwd_x16" if x.dtype == torch.bfloat16 else "rfx_groupnorm_bwd", x, gamma, beta, mean, rstd, gy,
                    N, Cc, S, groups, mode, scale, gsum, dx, dgamma, dbeta, dscale)
+        need = ctx.needs_input_grad                   # one launch forms them all: what was not asked for is dropped here
+        dx, dres = dx if need[0] else None, gy if (mode == 3 and need[6]) else None
         if sw is not None:
-            return dx, None, None, None, None, None, (gy if mode == 3 else None), None, None
-        return dx, dgamma, dbeta, None, None, None, (gy if mode == 3 else None), dscale, None
+            return dx, None, None, None, None, None, dres, None, None
+        return dx, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, dres, dscale if need[7] else None, None
 
 
 def group_norm(x, groups, weight, bias, eps=1e-5, mode="none", res=None, scale=None, sums=None):
@@ -98,6 +108,7 @@ class _BatchNormFn(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, relu):
         ops._req(x, "x")
         x = x.contiguous()
+        gamma, beta = gamma.contiguous(), beta.contiguous()          # read (and their gradients written) as dense vectors
         N, Cc = x.shape[0], x.shape[1]
         S = x.numel() // (N * Cc)
         y = torch.empty_like(x)
@@ -127,13 +138,14 @@ class _BatchNormFn(torch.autograd.Function):
         x, gamma, beta, mean, rstd = ctx.saved_tensors
         N, Cc, S, mode, training = ctx.cfg
         if not training:
-            raise RuntimeError("batch_norm backward in eval mode is not on the reference's path")
+            raise ValueError("batch_norm backward in eval mode is not on the reference's path")
         gy = gy.contiguous()
         dx = torch.empty_like(x)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         work = torch.empty(query("rfx_norm_bwd_work_floats", N, Cc, S, 0), device=x.device, dtype=torch.float32)
         launch("rfx_batchnorm_bwd", x, gamma, beta, mean, rstd, gy, N, Cc, S, mode, work, dx, dgamma, dbeta)
-        return dx, dgamma, dbeta, None, None, None, None, None, None
+        need = ctx.needs_input_grad                   # one launch forms all three
+        return dx if need[0] else None, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None, None, None
 
 
 def batch_norm(x, bn, training, relu=False):
@@ -176,6 +188,8 @@ class _GluFn(torch.autograd.Function):
         ops._req(x, "x")
         x = x.contiguous()
         N, Cc = x.shape[0], x.shape[1]
+        if Cc % 2:
+            raise ValueError(f"glu: the channel axis halves, got {Cc} channels")
         S = x.numel() // (N * Cc)
         shp = list(x.shape)
         shp[1] = Cc // 2
@@ -205,7 +219,10 @@ class _AddFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, alpha):
-        ops._req(x, "x")
+        ops._req(x, "x"); ops._req(y, "y")
+        if y.dim() != x.dim() or x.dim() not in (3, 4):
+            raise ValueError(f"add: x and y of the same rank, 3 or 4 (got {x.dim()} and {y.dim()}): a y of lower rank is not "
+                             "broadcast as torch would, give it its singleton axes")
         x = x.contiguous()
         x4 = x if x.dim() == 4 else x.unsqueeze(2)
         y4 = y if y.dim() == 4 else y.unsqueeze(2)
@@ -233,7 +250,7 @@ class _AddFn(torch.autograd.Function):
                 gy = g4.sum_to_size(yshape) * alpha
             if ydim == 3:
                 gy = gy.squeeze(2)
-        return g, gy, None
+        return g if ctx.needs_input_grad[0] else None, gy, None
 
 
 def add(x, y, alpha=1.0):
@@ -251,6 +268,8 @@ class _DConvLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps, grad_on=True):
         ops._req(x, "x")
+        x = x.contiguous()                            # the kernels take dense tensors by pointer, the parameters included
+        w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale = (p.contiguous() for p in (w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale))
         N, Cc, T = x.shape
         H = Cc // 4
         out = torch.empty_like(x)
@@ -277,7 +296,13 @@ class _DConvLayerFn(torch.autograd.Function):
     def backward(ctx, gy):
         dil, eps, fused_bwd = ctx.cfg
         if fused_bwd:
-            return _DConvLayerFn._backward_fused(ctx, gy, dil, eps)
+            grads = _DConvLayerFn._backward_fused(ctx, gy, dil, eps)
+        else:
+            grads = _DConvLayerFn._backward_layers(ctx, gy, dil)
+        return tuple(g if n else None for g, n in zip(grads, ctx.needs_input_grad))      # either form computes them all
+
+    @staticmethod
+    def _backward_layers(ctx, gy, dil):
         x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, h16, z16, a_out, stats = ctx.saved_tensors
         N, Cc, T = x.shape
         H = Cc // 4
@@ -368,9 +393,13 @@ class _MulFn(torch.autograd.Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         g = g.contiguous()
-        ga, gb = torch.empty_like(a), torch.empty_like(b)
-        launch("rfx_mul", g, b, ga, a.numel())
-        launch("rfx_mul", g, a, gb, a.numel())
+        ga = gb = None
+        if ctx.needs_input_grad[0]:
+            ga = torch.empty_like(a)
+            launch("rfx_mul", g, b, ga, a.numel())
+        if ctx.needs_input_grad[1]:
+            gb = torch.empty_like(b)
+            launch("rfx_mul", g, a, gb, a.numel())
         return ga, gb
 
 
@@ -393,6 +422,7 @@ def row_standardize(x, eps):
 class _RowAffineFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a, b):
+        ops._req(x, "x"); ops._req(a, "a"); ops._req(b, "b")
         x = x.contiguous()
         R = x.shape[0]
         y = torch.empty_like(x)
@@ -499,7 +529,7 @@ class _RowAffineAddFn(torch.autograd.Function):
             gx = torch.empty(ctx.xshape, device=g.device, dtype=torch.float32)
             # the rows of a group are contiguous: one row of group * L samples per coefficient
             launch("rfx_row_affine", gc, a, None, gx, Q, gc.numel() // Q)
-        return gx, None, None, g, None
+        return gx, None, None, g if ctx.needs_input_grad[3] else None, None
 
 
 def row_affine_add(x, a, b, y, group=1):
@@ -560,7 +590,8 @@ class _LocalStateFn(torch.autograd.Function):
         else:
             w = ctx.saved_tensors[4]
             launch("rfx_localstate_bwd", q, k, cont, qd, w, g, B, heads, ch, T, ndecay, dq, dk, dc, dqd)
-        return dq, dk, dc, dqd, None, None
+        need = ctx.needs_input_grad                   # one launch forms all four
+        return dq if need[0] else None, dk if need[1] else None, dc if need[2] else None, dqd if need[3] else None, None, None
 
 
 def local_state_attention(q, k, content, query_decay, heads, ndecay):
@@ -607,9 +638,11 @@ class _BlstmUnframeFn(torch.autograd.Function):
     def backward(ctx, g):
         B, Cc, T, nfr, width, stride, has_skip = ctx.cfg
         g = g.contiguous()
-        dh = torch.empty((1, Cc, width * B * nfr), device=g.device, dtype=torch.float32)
-        launch("rfx_blstm_frames", g, None, dh, B, Cc, T, nfr, width, stride, 3)
-        return dh, (g if has_skip else None), None, None, None, None, None
+        dh = None
+        if ctx.needs_input_grad[0]:
+            dh = torch.empty((1, Cc, width * B * nfr), device=g.device, dtype=torch.float32)
+            launch("rfx_blstm_frames", g, None, dh, B, Cc, T, nfr, width, stride, 3)
+        return dh, (g if has_skip and ctx.needs_input_grad[1] else None), None, None, None, None, None
 
 
 def blstm_frame(x, nfr, width, stride):

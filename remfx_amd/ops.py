@@ -324,6 +324,21 @@ def _req(t, name="tensor"):
                          "there is no CPU fallback")
 
 
+def _distinct(x):
+    """x itself where its elements are distinct in memory, a contiguous copy otherwise.  The nodes that allocate dx with x's own
+    strides (the gather-GEMM reads and writes any strides) call this on the way in: for an expanded x (stride 0 over the batch: one
+    clip for every sample) every sample's gradient would land on the same words, and autograd's expand backward would then sum N
+    copies of the last writer instead of the N gradients."""
+    if x.is_contiguous():
+        return x
+    ext = 1
+    for s, n in sorted((s, n) for n, s in zip(x.shape, x.stride()) if n > 1):
+        if s < ext:
+            return x.contiguous()
+        ext = s * n
+    return x
+
+
 # ---- plan cache (tables live on the device next to the tensors) -------------------
 class DevPlan:
     def __init__(self, plan, device):
@@ -443,7 +458,8 @@ def weights_changed():
 
 
 def _derived(src, derive):
-    return derive(src) if derive is not None else src.contiguous()
+    """the dense tensor rfx_pack_a gathers from (a derive() of an expanded weight is still a view with a zero stride)"""
+    return (derive(src) if derive is not None else src).contiguous()
 
 
 def pack_cached(dp, src, derive=None, tag=0):
@@ -483,6 +499,8 @@ def clear_pack_cache():
 def gemm_fwd(dp, apack, x, out, bias=None, act=None, act_param=None, res=None, act2=None,
              dp2=None, apack2=None, in2=None, bwd=False, gparam=None, stat_sums=None, glu_out=None):
     e = Epilogue()
+    if bias is not None and not bias.is_contiguous():
+        bias = bias.contiguous()                           # read as a dense vector; alive until the launch below is queued
     e.bias = bias.data_ptr() if bias is not None else None
     e.act = ACT[act]
     e.act_param = act_param.data_ptr() if act_param is not None else None
@@ -696,12 +714,13 @@ def _conv2d_backward(ctx, g, res=None):
     if ctx.needs_input_grad[0]:
         dx = conv2d_dgrad(g, w, tuple(x.shape), tuple(x.stride()), stride, padding, dilation, res=res)
     if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-        dw, db = conv2d_wgrad(x, g, tuple(w.shape), stride, padding, dilation, has_bias, w, ctx.bias)
-    return dx, dw, db
+        dw, db = conv2d_wgrad(x, g, tuple(w.shape), stride, padding, dilation, has_bias, w, ctx.bias)    # one GEMM forms both
+    return dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
 
 
 def _conv2d_node_forward(ctx, x, w, bias, stride, padding, dilation, stat_sums, out_bf16):
     """conv2d_forward as an autograd node's forward: saves what _conv2d_backward reads."""
+    x = _distinct(x)                                      # dx takes the saved x's strides
     ctx.save_for_backward(x, w)
     ctx.bias = bias                                       # identity only (GradSink lookup); never read
     ctx.cfg = (stride, padding, dilation, bias is not None)
@@ -743,6 +762,7 @@ class ConvGlu2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, stride, padding, dilation):
         _req(x, "x"); _req(w, "weight")
+        x = _distinct(x)                                  # dx takes the saved x's strides
         N, Cin, IA, IB = x.shape
         C2, _, KA, KB = w.shape
         Ch = C2 // 2
@@ -836,6 +856,7 @@ class ConvT2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, stride, dilation, crop_lo, out_len):
+        x = _distinct(x)                                  # dx takes the saved x's strides
         ctx.save_for_backward(x, w)
         ctx.bias = bias                                   # identity only (GradSink lookup)
         ctx.cfg = (stride, dilation, crop_lo, out_len, bias is not None)
@@ -907,9 +928,11 @@ def _rows16(x, gy, out, act):
 
 
 def _act_bwd(ctx, gy):
-    """(gx, contiguous gy) of a node that saved its contiguous fp32 x and set ctx.act."""
+    """(gx or None where x asked for none, contiguous gy) of a node that saved its contiguous fp32 x and set ctx.act."""
     (x,) = ctx.saved_tensors
     gy = gy.contiguous()
+    if not ctx.needs_input_grad[0]:
+        return None, gy
     gx = torch.empty_like(x)
     launch("rfx_act_bwd", x, gy, gx, x.numel(), ACT[ctx.act])
     return gx, gy
@@ -961,7 +984,8 @@ class ActAddFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        return _act_bwd(ctx, gy) + (None,)
+        gx, gy = _act_bwd(ctx, gy)
+        return gx, gy if ctx.needs_input_grad[1] else None, None
 
 
 def activation_add(x, res, act):
@@ -985,6 +1009,7 @@ class ActToFn(torch.autograd.Function):
         x16 = x.dtype == torch.bfloat16         # a conv output stored in 16 bits (bf16 mode): fp32 result, 16-bit gradient
         if not x16:
             _req(x)
+        x = _distinct(x)                                  # gx takes the saved x's strides
         xs = _row_strides(x)
         D = x.shape
         y = torch.empty([D[p] for p in perm] + [D[3]], device=x.device, dtype=torch.float32)

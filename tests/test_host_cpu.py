@@ -605,3 +605,34 @@ def test_lstm_workspace_bytes():
         assert L.rfx_lstm_ws_bytes(H) == 256 + clusters * 64 + clusters * 2 * nwc * nwc * 4096, H
     for H in (0, -32, 16, 33, 544, 1024):
         assert L.rfx_lstm_ws_bytes(H) == -1, H
+
+
+def test_every_autograd_node_is_pinned():
+    """tests/node_census.py: its keys are the torch.autograd.Function subclasses under remfx_amd/ (found with ast), every value is an
+    existing tests/test_gpu_*.py.  For test_gpu_nodes.py the case table of tests/node_ref.py must hold a case of the class.  For the
+    other modules the check is only that the file mentions the class or the name VIA records (often just the module under test): that
+    keeps the map from pointing at a file that never touches the code, it does not prove the backward is judged there -- the map was
+    filled by reading"""
+    import ast
+    from tests import node_census as N
+    found = set()
+    pkg = os.path.join(ROOT, "remfx_amd")
+    for f in sorted(os.listdir(pkg)):
+        if not f.endswith(".py"):
+            continue
+        for n in ast.walk(ast.parse(open(os.path.join(pkg, f)).read())):
+            if isinstance(n, ast.ClassDef) and any(ast.unparse(b) in ("torch.autograd.Function", "autograd.Function", "Function") for b in n.bases):
+                found.add(f"{f[:-3]}.{n.name}")
+    assert found == set(N.PINNED_BY), found ^ set(N.PINNED_BY)
+    here = os.path.join(ROOT, "tests")
+    from tests import node_ref
+    tabled = {c.node for c in node_ref.case_table() + node_ref.dconv_cases()}
+    for node, module in N.PINNED_BY.items():
+        assert re.fullmatch(r"test_gpu_\w+\.py", module) and os.path.exists(os.path.join(here, module)), (node, module)
+        cls = node.split(".")[1]
+        if module == N.NODES:
+            assert node.split(".")[0] in ("ops", "nnops") and cls in tabled, (node, "has no case in tests/node_ref.py")
+        else:
+            text = open(os.path.join(here, module)).read()
+            assert cls in text or (node in N.VIA and N.VIA[node] in text), (node, "is not named by", module)
+    assert set(N.VIA) <= set(N.PINNED_BY)
