@@ -14,6 +14,13 @@
  *   - return value: 0 on success, negative on bad arguments (-1) or a failed
  *     launch (-2 - hipError).  No exceptions cross the ABI.
  *   - tensors are fp32 unless stated; strides are in ELEMENTS.
+ *   - scratch (a buffer the caller never reads for a result: ws, work, partial, hop_ws, env_ws, slotted sums) is sized by the
+ *     library: every entry point rfx_X that takes one has a host-only query int64_t rfx_X_ws(<geometry arguments of rfx_X, same
+ *     order and types>) -- rfx_X_ws_<param>(...) per buffer where there are several -- that returns the number of ELEMENTS of the
+ *     parameter's declared type (stated beside each query), or -1 (0 where noted) for geometry the launcher refuses.  Query and
+ *     launcher run the same host function for the grid, so the kernels, which store into slot blockIdx.x unconditionally, cannot
+ *     outgrow a buffer sized this way.  Older queries of the same kind carry their unit in the name (_ws_floats, _ws_bytes,
+ *     _work_floats); entry points that share a geometry share a query.  No scratch needs initialising unless stated.
  */
 #ifndef REMFX_HIP_H
 #define REMFX_HIP_H
@@ -312,7 +319,8 @@ int rfx_act_rows16(const void* x, int64_t xs0, int64_t xs1, int64_t xs2, const f
 int rfx_mul(const float* a, const float* b, float* y, int64_t n, void* stream);
 /* nn.PReLU over [N][C][L] contiguous with a per-channel slope (C = 1: the single-parameter form of asteroid DPTNet's
  * `first_out`, reference remfx/models.py:327-344; per-channel: remfx/tcn.py:46).  Forward; backward: gx, and gslope[C] WRITTEN (one fp64
- * slot per (channel, sample) in `ws`, N * C doubles, added in sample order). */
+ * slot per (channel, sample) in `ws`, rfx_prelu_bwd_ws(N, C, L) doubles, added in sample order). */
+int64_t rfx_prelu_bwd_ws(int64_t N, int64_t C, int64_t L);
 int rfx_prelu_fwd(const float* x, const float* slope, float* y, int64_t N, int64_t C, int64_t L, void* stream);
 int rfx_prelu_bwd(const float* x, const float* gy, const float* slope, float* gx, double* ws, float* gslope,
                   int64_t N, int64_t C, int64_t L, void* stream);
@@ -328,10 +336,10 @@ int rfx_channel_sum(const float* x, int32_t N, int32_t C, int32_t A, int32_t B, 
 int rfx_add_bcast(const float* x, const float* y, float* out, int64_t N, int32_t C, int32_t A, int32_t B,
                   int64_t yn, int64_t yc, int64_t ya, int64_t yb, float alpha, void* stream);
 /* per-row mean / unbiased std of x[R][L] and out = x*a[r] + b[r] (b may be NULL): HDemucs input and spectrogram standardisation /
- * de-standardisation (x.mean/std over dims 1..).  sums: fp64 workspace of 2 * R * rfx_row_moments_slots(L) values, no initialisation
+ * de-standardisation (x.mean/std over dims 1..).  sums: fp64 workspace of rfx_row_moments_ws(R, L) doubles, no initialisation
  * needed (one slot per workgroup, added in slot order: bit-reproducible, no atomics).  coef_a / coef_b (both or neither): the
  * standardisation as one affine map, a = 1 / (eps + std), b = -mean * a. */
-int rfx_row_moments_slots(int64_t L);
+int64_t rfx_row_moments_ws(int32_t R, int64_t L);
 int rfx_row_moments(const float* x, int32_t R, int64_t L, double* sums, float* mean, float* stdv, float eps, float* coef_a,
                     float* coef_b, void* stream);
 int rfx_row_affine(const float* x, const float* a, const float* b, float* out, int32_t R, int64_t L, void* stream);
@@ -368,9 +376,10 @@ int rfx_span_mask(float* x, int32_t R, int32_t F, int32_t T, const int32_t* f0, 
 int rfx_blstm_frames(const float* src, const float* skip, float* dst, int32_t B, int32_t C, int32_t T, int32_t nfr,
                      int32_t width, int32_t stride, int32_t mode, void* stream);
 
-/* out[0] = scale * sum |a-b| over n elements (nn.L1Loss, models.py:320: scale = 1 / n).  ws: RFX_L1_SLOTS doubles of per-workgroup
- * partials (no initialisation needed), added in slot order.  n == 0: out[0] = 0 is written (whatever the scale), no slot is. */
-#define RFX_L1_SLOTS 512
+/* out[0] = scale * sum |a-b| over n elements (nn.L1Loss, models.py:320: scale = 1 / n).  ws: rfx_l1_sum_ws(n) doubles of per-workgroup
+ * partials (no initialisation needed; the same count for every n >= 0), added in slot order.  n == 0: out[0] = 0 is written (whatever
+ * the scale), no slot is. */
+int64_t rfx_l1_sum_ws(int64_t n);
 int rfx_l1_sum(const float* a, const float* b, int64_t n, double* ws, float scale, float* out, void* stream);
 
 /* ---- LocalState attention (torchaudio HDemucs `_LocalState` inside the DConv blocks, reached from models.py:319) ----
@@ -412,8 +421,8 @@ int rfx_localstate_gen_bwd(const float* q, const float* k, const float* cont, co
  * (each clip draws its own).  y may alias x (the same pointer: in place) for distortion, chorus, compressor, reverb, scale, limiter, eq,
  * widener and phaser, with the same bits as out of place; rfx_fx_delay and rfx_fx_sox_reverb refuse x == y, rfx_fx_normalize_rows
  * refuses it with a row table.  Every entry point returns -1, with nothing launched or written, for a null pointer, B outside
- * 1 ... 65535, T < 1 or a parameter outside what its comment states.  rfx_fx_compressor: env_ws is B * T floats and holds the
- * envelope afterwards.  rfx_fx_chorus: sample_rate from 4000 to 80600 Hz (a 50 ms delay and a block fit the 4096-sample ring).
+ * 1 ... 65535, T < 1 or a parameter outside what its comment states.  rfx_fx_compressor: env_ws is rfx_fx_compressor_ws(B, T) floats
+ * (a (B, T) image) and holds the envelope afterwards.  rfx_fx_chorus: sample_rate from 4000 to 80600 Hz (a 50 ms delay and a block fit the 4096-sample ring).
  * rfx_fx_reverb: 12544 <= sample_rate <= 143526 (every ring at least one 64-sample block long, the twelve rings within 160 KB of
  * LDS); -1 outside.  Algorithms: csrc/fx.hip; oracle/ref_effects.py.  Every form of every kernel is pinned per element to the fp64
  * statements of tests/fx_ref.py. */
@@ -422,6 +431,7 @@ int rfx_fx_delay(const float* x, float* y, int32_t B, int64_t T, const int32_t* 
                  const float* mix, void* stream);
 int rfx_fx_chorus(const float* x, float* y, int32_t B, int64_t T, float sample_rate, const float* rate_hz, const float* depth,
                   const float* centre_delay_ms, const float* feedback, const float* mix, void* stream);
+int64_t rfx_fx_compressor_ws(int32_t B, int64_t T);
 int rfx_fx_compressor(const float* x, float* y, float* env_ws /* (B, T) workspace */, int32_t B, int64_t T,
                       const float* threshold_lin, const float* ratio, const float* c_attack, const float* c_release, void* stream);
 int rfx_fx_reverb(const float* x, float* y, int32_t B, int64_t T, int32_t sample_rate, const float* damp, const float* feedback,
@@ -430,12 +440,14 @@ int rfx_fx_reverb(const float* x, float* y, int32_t B, int64_t T, int32_t sample
  * relative gates) and the LoudnessNormalize gain 10^(clamp(target - L, -120, 40) / 20) per clip.  coef: 28 HOST doubles = the two
  * normalised biquads b1[3] a1[3] b2[3] a2[3] and the 4 x 4 zero-input state transition of `chunk` samples (row-major);
  * chunk * 64 >= T; hop_len = samples per 100 ms; nblk gating blocks over nhop >= nblk + 3 hops; inv_block = 1 / (0.4 * rate);
- * hop_ws: B * nhop doubles.  Outputs lufs[B], gain[B]; apply the gain with rfx_fx_scale. */
+ * hop_ws: rfx_fx_loudness_ws(...) doubles (B * nhop).  Outputs lufs[B], gain[B]; apply the gain with rfx_fx_scale. */
+int64_t rfx_fx_loudness_ws(int32_t B, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk);
 int rfx_fx_loudness(const float* x, int32_t B, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
                     double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs, float* gain, void* stream);
 int rfx_fx_scale(const float* x, float* y, int32_t B, int64_t T, const float* gain, void* stream);
 /* The same measurement for B clips of C channels, x: (B, C, T): pyloudnorm's joint multichannel loudness (block power = sum of the
- * channels' mean squares).  hop_ws: B * C * nhop doubles; lufs[B], gain[B]. */
+ * channels' mean squares).  hop_ws: rfx_fx_loudness_joint_ws(...) doubles (B * C * nhop); lufs[B], gain[B]. */
+int64_t rfx_fx_loudness_joint_ws(int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk);
 int rfx_fx_loudness_joint(const float* x, int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
                           double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs, float* gain,
                           void* stream);
@@ -450,13 +462,14 @@ int rfx_fx_normalize_rows(const float* x, float* y, const int32_t* rows, int32_t
                           int32_t nhop, int32_t nblk, double inv_block, const double* coef, float target_lufs, void* ws, void* stream);
 /* The rest of remfx/effects.py: RandomPedalboardLimiter (:468-494), RandomParametricEQ (:37-214), RandomStereoWidener (:217-252),
  * RandomVolumeAutomation (:255-294), RandomPedalboardPhaser (:418-465).  Parameters per row unless stated.
- * limiter: ws = 2 * B * T floats (afterwards: stage 2's envelope, then stage 1's output); params = 9 x B floats on the device, rows thr1 ratio1 c_attack1 c_release1 (stage 1),
+ * limiter: ws = rfx_fx_limiter_ws(B, T) floats, two (B, T) images (afterwards: stage 2's envelope, then stage 1's output); params = 9 x B floats on the device, rows thr1 ratio1 c_attack1 c_release1 (stage 1),
  *          thr2 ratio2 c_attack2 c_release2 (stage 2, linear thresholds and ballistics coefficients as for rfx_fx_compressor), make-up.
  * eq: nsec = 2..8 biquads; coef on the device, per row nsec x {b0 b1 b2 a1 a2} (a0 = 1) then the (2 nsec)^2 zero-input state
  *     transition of `chunk` samples, row-major; chunk * 64 >= T.
  * widener: B (2, T) clips, x: (B, 2, T); g_mid = 2 (1 - width), g_side = 2 width per clip.
  * volume: IN PLACE; S segments per row: seg_end (cumulative end sample, non-decreasing), dB at the segment's start and end; S <= 64.
  * phaser: ws = rfx_fx_phaser_ws_floats(B, T) floats. */
+int64_t rfx_fx_limiter_ws(int32_t B, int64_t T);
 int rfx_fx_limiter(const float* x, float* y, float* ws, int32_t B, int64_t T, const float* params, void* stream);
 int rfx_fx_eq(const float* x, float* y, int32_t B, int64_t T, int32_t nsec, int32_t chunk, const double* coef, void* stream);
 int rfx_fx_widener(const float* x, float* y, int32_t B, int64_t T, const float* g_mid, const float* g_side, void* stream);
@@ -495,10 +508,10 @@ int rfx_dconv_layer_fwd(const float* x, float* out, int32_t N, int32_t C, int32_
 /* Backward of the same layer in ONE launch (round 4): recomputes the forward from x, returns gx = dL/dx, the operands of the two
  * weight-gradient GEMMs -- dz (N, 2C, T) bf16 = gradient of the 1x1 convolution's output, a_out (N, H, T) fp32 = its input,
  * dh (N, H, T) bf16 = gradient of the 3-tap convolution's output (rfx_gemm_wgrad: dW2 = dz a^T, dW1 = dh * x) -- and `partial`:
- * rfx_dconv_layer_bwd_rows(N) rows of 5C + 2H floats [dscale C | dgn2w 2C | dgn2b 2C | dgn1w H | dgn1b H] whose column sums are the
+ * rfx_dconv_layer_bwd_ws(N, C, T, dil) floats = rows of 5C + 2H floats [dscale C | dgn2w 2C | dgn2b 2C | dgn1w H | dgn1b H] whose column sums are the
  * LayerScale / GroupNorm gradients (one row per workgroup; the caller adds them up).  Replaces the autograd backward of torchaudio
  * `_DConv` reached from remfx/models.py:319. */
-int rfx_dconv_layer_bwd_rows(int32_t N);
+int64_t rfx_dconv_layer_bwd_ws(int32_t N, int32_t C, int32_t T, int32_t dil);
 int rfx_dconv_layer_bwd(const float* x, const float* g, float* gx, int32_t N, int32_t C, int32_t T, int32_t dil, const float* w1,
                         const float* b1, const float* gn1w, const float* gn1b, const float* w2, const float* b2, const float* gn2w,
                         const float* gn2b, const float* scale, float eps, void* dz_bf16, float* a_out, void* dh_bf16, float* partial,
@@ -534,13 +547,15 @@ int rfx_groupnorm_fwd(const float* x, const float* gamma, const float* beta, int
                       double* sums /* N*G*2 fp64 workspace; sums_given != 0: already holds {sum, sumsq} per
                                       (n, g) -- e.g. from rfx_epilogue.stat_sums -- and the statistics pass is skipped;
                                       sums_given = k > 1: the buffer is [N*G][k][2] partial sums (rfx_epilogue.stat_slots);
-                                      sums_given = -1: see rfx_groupnorm_stat_chunks */,
+                                      sums_given = -1: see rfx_groupnorm_stat_chunks / rfx_groupnorm_fwd_ws */,
                       int32_t sums_given, float* mean, float* rstd, float* y, void* stream);
 /* Chunks the statistics kernel of rfx_groupnorm_fwd / _x16 cuts one group into.  sums_given = -1 in those entry points: no statistics
- * are given and `sums` is a workspace of N * G * chunks pairs of doubles that the kernel fills with plain stores, one pair per
- * (group, chunk), summed in chunk order -- no zero fill, no atomics (a fill followed by fp64 atomics lost contributions whenever a
- * second stream kept the machine busy).  sums_given = 0 keeps the N * G pair buffer + atomics form. */
+ * are given and `sums` is a workspace of rfx_groupnorm_fwd_ws(N, C, S, G) doubles (N * G * chunks pairs) that the kernel fills with plain
+ * stores, one pair per (group, chunk), summed in chunk order -- no zero fill, no atomics (a fill followed by fp64 atomics lost
+ * contributions whenever a second stream kept the machine busy).  sums_given = 0 keeps the N * G pair buffer + atomics
+ * form.  The chunk count itself is what a producing GEMM spreads its statistics over (rfx_epilogue.stat_slots). */
 int rfx_groupnorm_stat_chunks(int32_t C, int32_t S, int32_t G);
+int64_t rfx_groupnorm_fwd_ws(int32_t N, int32_t C, int32_t S, int32_t G);   /* doubles; rfx_groupnorm_fwd and _x16, sums_given = -1 */
 /* Floats of `work` the three backward entry points below need (G = 0: rfx_batchnorm_bwd): N*C*2 + N*(C/2) + 2 max(N*G, C) and, for
  * rows longer than one 4096-sample chunk, one slot per (sample, channel, chunk) partial -- plain stores added in chunk order (no zero
  * fill, no atomics: DESIGN.md 4.11). */
@@ -563,9 +578,9 @@ int rfx_groupnorm_bwd_x16(const void* x, const float* gamma, const float* beta, 
 /* BatchNorm2d (+ReLU, mode 4) over (N, S) per channel -- classifier.py:271-272 (ConvBlock).
  * use_given_stats != 0: eval mode, mean = running_mean, rstd = 1/sqrt(running_var + eps) are inputs;
  * otherwise batch statistics are computed into mean / rstd (biased variance).  sums: fp64 workspace of
- * C * rfx_batchnorm_stat_slots(N, S) PAIRS -- one per (channel, sample, 4096-value chunk), stored by the wave that owns it and added
+ * rfx_batchnorm_fwd_ws(N, C, S) doubles -- one pair per (channel, sample, 4096-value chunk), stored by the wave that owns it and added
  * in slot order (no zero fill, no atomics). */
-int rfx_batchnorm_stat_slots(int32_t N, int32_t S);
+int64_t rfx_batchnorm_fwd_ws(int32_t N, int32_t C, int32_t S);
 int rfx_batchnorm_fwd(const float* x, const float* gamma, const float* beta, int32_t N, int32_t C, int32_t S,
                       float eps, int32_t mode, int32_t use_given_stats, double* sums, float* mean, float* rstd,
                       float* y, void* stream);
@@ -592,9 +607,10 @@ int rfx_glu_bwd_bf16(const void* x, const float* gy, void* gx, int64_t N, int64_
  * Complex tensors are real tensors (N, 2C, S): channels [0,C) real parts, [C,2C) imaginary parts; a complex
  * convolution is then ONE rfx_gemm_fwd with the block weight [[Wr,-Wi],[Wi,Wr]].
  * sums (5, per channel c at c*5+q): sum xr, xi, xr^2, xr*xi, xi^2 in fp64 (ComplexBatchNorm statistics).
- * ws: fp64 workspace of 5 * C * rfx_cplx_slots(N, S) values (rfx_cplx_affine_act_bwd: 6 * C * rfx_cplx_slots) -- one slot per
- * (sample, 4096-value chunk), stored by the wave that owns it and added in slot order: no zero fill, no atomics. */
-int64_t rfx_cplx_slots(int32_t N, int64_t S);
+ * ws: fp64 workspace of rfx_cplx_moments_ws(N, C, S) / rfx_cplx_affine_act_bwd_ws(N, C, S) doubles -- 5 / 6 values per channel and
+ * (sample, 4096-value chunk) slot, stored by the wave that owns it and added in slot order: no zero fill, no atomics. */
+int64_t rfx_cplx_moments_ws(int32_t N, int32_t C, int64_t S);
+int64_t rfx_cplx_affine_act_bwd_ws(int32_t N, int32_t C, int64_t S);
 int rfx_cplx_moments(const float* x, int32_t N, int32_t C, int64_t S, double* ws, double* sums, void* stream);
 /* ComplexBatchNorm coefficients (asteroid complex_nn BatchNorm inside DCUNet, models.py:356-367) in one launch: per channel
  * coef (6, C) = Zrr, Zri, Zir, Zii, Br', Bi' with y = Z x + B', Z = W V^{-1/2} (2x2 inverse square root of the covariance + eps)
@@ -654,7 +670,7 @@ int rfx_wiener(const float* X, const float* S, float* Y, int32_t B, int32_t C, i
  * auraloss STFTLoss terms on complex spectra [R][n] (n = bins*frames, view_as_real layout):
  * sums[r] = { sum (|Y|-|X|)^2, sum |Y|^2, sum |log|X| - log|Y|| }, |.| = sqrt(max(re^2+im^2, eps)) (written, not accumulated).
  * Replaces auraloss.freq.STFTLoss.forward (models.py:299,320,362,385,107; metrics 237-255). */
-#define RFX_STFT_REDUCE_SLOTS 64      /* ws: 3 * R * RFX_STFT_REDUCE_SLOTS doubles (per-workgroup partials, no initialisation needed) */
+int64_t rfx_stft_loss_reduce_ws(int32_t R, int64_t n);   /* doubles of ws (per-workgroup partials; the same count for every n > 0) */
 int rfx_stft_loss_reduce(const float* xc, const float* yc, int32_t R, int64_t n, float eps, double* ws, float* sums,
                          void* stream);
 /* gxc = w_sc * d[sqrt(A_r)/sqrt(B_r)]/dxc + w_lm * d[sum |log|X|-log|Y||]/dxc  (A_r, B_r from sums).  gup (may be NULL): one
@@ -692,9 +708,9 @@ int rfx_l1_grad(const float* a, const float* b, int64_t n, float w, const float*
  * take any R. */
 #define RFX_LOSS_MAX_ROWS 65535
 /* per row: sums[r] = { sum x, sum t, sum x t, sum x^2, sum t^2 } in fp64 (auraloss SISDRLoss).  ws: per-workgroup partials (no
- * initialisation needed), added in slot order.  The call writes 5 * R * g doubles of it, g = min(max(ceil(L / 2048), 1),
- * RFX_SISDR_SLOTS) workgroups per row = rfx_time_sums_ws(R, L); 5 * R * RFX_SISDR_SLOTS doubles are enough for every L. */
-#define RFX_SISDR_SLOTS 128
+ * initialisation needed), added in slot order: rfx_sisdr_sums_ws(R, L) doubles, the same count for every L > 0.  The call writes the
+ * first rfx_time_sums_ws(R, L) of them (5 per row and workgroup). */
+int64_t rfx_sisdr_sums_ws(int32_t R, int64_t L);
 int rfx_sisdr_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs, int64_t t_rs,
                    double* ws, double* sums, void* stream);
 /* The scalar tail of SISDRLoss in one launch: out[0] = -mean_r 10 log10(|a t|^2 / (|x - a t|^2 + eps) + eps), a = <x,t> / (|t|^2 + eps),
@@ -790,8 +806,9 @@ int rfx_mrstft_combine_w(const double* const* sums, const int64_t* n, int32_t nr
 /* nbytes (multiple of 4) of zeros at p: optimizer.zero_grad() on the flat gradient buffer and the accumulation targets of the
  * atomics-based kernels (torch.zeros call sites of the hot path; Lightning's zero_grad behind models.py:185-191) */
 int rfx_zero(void* p, int64_t nbytes, void* stream);
-/* out[0] = sum g^2 (fp64).  ws: RFX_SUMSQ_SLOTS doubles of per-workgroup partials (no initialisation needed), added in slot order */
-#define RFX_SUMSQ_SLOTS 4096
+/* out[0] = sum g^2 (fp64).  ws: rfx_sumsq_ws(n) doubles of per-workgroup partials (no initialisation needed; the same count for every
+ * n >= 0, so an optimiser sizes it once), added in slot order */
+int64_t rfx_sumsq_ws(int64_t n);
 int rfx_sumsq(const float* g, int64_t n, double* ws, double* out, void* stream);
 /* *coef = min(1, max_norm / (sqrt(*sumsq) * pre + 1e-6)) * pre ; *norm_out = sqrt(*sumsq) * pre */
 int rfx_clip_coef(const double* sumsq, float max_norm, float pre, float* coef, float* norm_out, void* stream);
@@ -941,11 +958,18 @@ typedef struct rfx_cl_dconv_desc {
                             * (the parameters' slices of a flat gradient buffer) instead of being written to pgrad */
 } rfx_cl_dconv_desc;
 int rfx_cl_dconv_ok(int32_t C, int32_t H, int32_t T, int32_t backward);
+/* Floats of the scratch fields of d, from S, C, H, grid and TPS alone (no pointer is read); 0 = the call does not use the field.
+ * forward: d->partial (the tile sums of the statistics passes, TPS > 1).  backward: d->partial, d->tsum, d->sums. */
+int64_t rfx_cl_dconv_fwd_ws_partial(const rfx_cl_dconv_desc* d);
+int64_t rfx_cl_dconv_bwd_ws_partial(const rfx_cl_dconv_desc* d);
+int64_t rfx_cl_dconv_bwd_ws_tsum(const rfx_cl_dconv_desc* d);
+int64_t rfx_cl_dconv_bwd_ws_sums(const rfx_cl_dconv_desc* d);
 int rfx_cl_dconv_fwd(const rfx_cl_dconv_desc* d, void* stream);
 int rfx_cl_dconv_bwd(const rfx_cl_dconv_desc* d, float* pgrad, void* stream);
 
-/* out[a][c] (+)= scale * sum over (n, b) of x[n][a][b][c], deterministic (G fixed-order partials of A * C floats each in `partial`):
- * bias gradients (A = 1, rows folded into N) and the frequency-embedding gradient of Hybrid Demucs. */
+/* out[a][c] (+)= scale * sum over (n, b) of x[n][a][b][c], deterministic (G fixed-order partials of A * C floats each in `partial`,
+ * rfx_cl_rowsum_ws(N, A, B, C, G) floats): bias gradients (A = 1, rows folded into N) and the frequency-embedding gradient of Hybrid Demucs. */
+int64_t rfx_cl_rowsum_ws(int32_t N, int32_t A, int32_t B, int32_t C, int32_t G);
 int rfx_cl_rowsum(const rfx_cl_tensor* x, int32_t N, int32_t A, int32_t B, int32_t C, int32_t G, float scale, float* partial, float* out,
                   int32_t accumulate, void* stream);
 

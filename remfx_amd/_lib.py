@@ -139,6 +139,7 @@ SIGNATURES = {
     "rfx_fft_analysis": [C.POINTER(StftDesc), _P, _P, _P, _P, _P],
     "rfx_fft_synthesis_ws": [C.POINTER(StftDesc)],
     "rfx_fft_synthesis": [C.POINTER(StftDesc), _P, _P, _P, _P, _P, _P],
+    "rfx_stft_loss_reduce_ws": [_I32, _I64],
     "rfx_stft_loss_reduce": [_P, _P, _I32, _I64, C.c_float, _P, _P, _P],
     "rfx_stft_loss_grad": [_P, _P, _I32, _I64, C.c_float, _P, C.c_float, C.c_float, _P, _P, _P],
     "rfx_stft_loss_grad_m": [_P, _P, _I32, _I64, C.c_float, _P, C.c_float, C.c_float, _P, _P, _P],
@@ -146,6 +147,7 @@ SIGNATURES = {
     "rfx_stft_pair_loss": [C.POINTER(StftDesc), _P, _P, _P, C.c_float, _P, _P, _P, _P, _P],
     "rfx_fft_synthesis_lossgrad": [C.POINTER(StftDesc), _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P],
     "rfx_l1_grad": [_P, _P, _I64, C.c_float, _P, _P, _P],
+    "rfx_sisdr_sums_ws": [_I32, _I64],
     "rfx_sisdr_sums": [_P, _P, _I32, _I64, _I64, _I64, _P, _P, _P],
     "rfx_sisdr_finish": [_P, _I32, _I64, _I32, C.c_double, _P, _P],
     "rfx_time_sums_ws": [_I32, _I64],
@@ -162,12 +164,14 @@ SIGNATURES = {
                                   _P, _P, _P],
     "rfx_mrstft_combine_w": [_P, _P, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float, _P, _P],
     "rfx_zero": [_P, _I64, _P],
+    "rfx_sumsq_ws": [_I64],
     "rfx_sumsq": [_P, _I64, _P, _P, _P],
     "rfx_clip_coef": [_P, C.c_float, C.c_float, _P, _P, _P],
     "rfx_adamw_step": [_P, _P, _P, _P, _I64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I32, _P, _P],
     "rfx_groupnorm_stat_chunks": [_I32, _I32, _I32],
+    "rfx_groupnorm_fwd_ws": [_I32, _I32, _I32, _I32],
     "rfx_norm_bwd_work_floats": [_I32, _I32, _I32, _I32],
-    "rfx_batchnorm_stat_slots": [_I32, _I32],
+    "rfx_batchnorm_fwd_ws": [_I32, _I32, _I32],
     "rfx_groupnorm_fwd": [_P, _P, _P, _I32, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _P, _I32, _P, _P, _P, _P],
     "rfx_groupnorm_bwd": [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     "rfx_groupnorm_fwd_x16": [_P, _P, _P, _I32, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _P, _I32, _P, _P, _P, _P],
@@ -176,7 +180,8 @@ SIGNATURES = {
     "rfx_batchnorm_bwd": [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "rfx_avgpool2d_fwd": [_P, _P, _I64, _I32, _I32, _I32, _I32, _P],
     "rfx_avgpool2d_bwd": [_P, _P, _I64, _I32, _I32, _I32, _I32, _P],
-    "rfx_cplx_slots": [_I32, _I64],
+    "rfx_cplx_moments_ws": [_I32, _I32, _I64],
+    "rfx_cplx_affine_act_bwd_ws": [_I32, _I32, _I64],
     "rfx_cplx_moments": [_P, _I32, _I32, _I64, _P, _P, _P],
     "rfx_cplx_moments_bwd": [_P, _P, _I32, _I32, _I64, _P, _P],
     "rfx_cplx_coef_fwd": [_P, C.c_double, _P, _P, _P, _P, _P, _P, C.c_float, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P],
@@ -200,23 +205,29 @@ SIGNATURES = {
     "rfx_act_rows16": [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P],
     "rfx_mul": [_P, _P, _P, _I64, _P],
     "rfx_prelu_fwd": [_P, _P, _P, _I64, _I64, _I64, _P],
+    "rfx_prelu_bwd_ws": [_I64, _I64, _I64],
     "rfx_prelu_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "rfx_l1_sum_ws": [_I64],
     "rfx_l1_sum": [_P, _P, _I64, _P, C.c_float, _P, _P],
     "rfx_add_bcast": [_P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I64, _I64, _I64, C.c_float, _P],
     "rfx_localstate_fwd": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
     "rfx_localstate_bwd": [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "rfx_dconv_layer_ok": [_I32, _I32, _I32],
-    "rfx_dconv_layer_bwd_rows": [_I32],
+    "rfx_dconv_layer_bwd_ws": [_I32, _I32, _I32, _I32],
     "rfx_dconv_layer_bwd": [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P],
     "rfx_dconv_layer_fwd": [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P],
     "rfx_fx_distortion": [_P, _P, _I32, _I64, _P, _P],
     "rfx_fx_delay": [_P, _P, _I32, _I64, _P, _P, _P, _P],
     "rfx_fx_chorus": [_P, _P, _I32, _I64, C.c_float, _P, _P, _P, _P, _P, _P],
+    "rfx_fx_compressor_ws": [_I32, _I64],
     "rfx_fx_compressor": [_P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P],
     "rfx_fx_reverb": [_P, _P, _I32, _I64, _I32, _P, _P, _P, _P, _P],
+    "rfx_fx_loudness_ws": [_I32, _I64, _I32, _I32, _I32, _I32],
     "rfx_fx_loudness": [_P, _I32, _I64, _I32, _I32, _I32, _I32, C.c_double, _P, C.c_float, _P, _P, _P, _P],
     "rfx_fx_scale": [_P, _P, _I32, _I64, _P, _P],
+    "rfx_fx_loudness_joint_ws": [_I32, _I32, _I64, _I32, _I32, _I32, _I32],
     "rfx_fx_loudness_joint": [_P, _I32, _I32, _I64, _I32, _I32, _I32, _I32, C.c_double, _P, C.c_float, _P, _P, _P, _P],
+    "rfx_fx_limiter_ws": [_I32, _I64],
     "rfx_fx_limiter": [_P, _P, _P, _I32, _I64, _P, _P],
     "rfx_fx_eq": [_P, _P, _I32, _I64, _I32, _I32, _P, _P],
     "rfx_fx_widener": [_P, _P, _I32, _I64, _P, _P, _P],
@@ -237,7 +248,7 @@ SIGNATURES = {
     "rfx_blstm_frames": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "rfx_span_mask": [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "rfx_dropout": [_P, _P, _I64, C.c_float, C.c_uint64, _P],
-    "rfx_row_moments_slots": [_I64],
+    "rfx_row_moments_ws": [_I32, _I64],
     "rfx_row_moments": [_P, _I32, _I64, _P, _P, _P, C.c_float, _P, _P, _P],
     "rfx_row_affine": [_P, _P, _P, _P, _I32, _I64, _P],
     "rfx_row_affine_add": [_P, _P, _P, _P, _P, _I32, _I32, _I64, _P],
@@ -263,6 +274,7 @@ SIGNATURES = {
     "rfx_cl_wgrad_reduce": [_P, _P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P, _I32, _P],
     "rfx_cl_from_cm": [_P, _I32, _I64, _I64, _I64, _I32, _I32, _I32, _I32, C.POINTER(ClTensor), C.POINTER(ClTensor), C.POINTER(ClTensor),
                        _I32, _P],
+    "rfx_cl_rowsum_ws": [_I32, _I32, _I32, _I32, _I32],
     "rfx_cl_rowsum": [C.POINTER(ClTensor), _I32, _I32, _I32, _I32, _I32, C.c_float, _P, _P, _I32, _P],
     "rfx_cl_to_cm": [C.POINTER(ClTensor), _I32, _I32, _I32, _I32, _P, _I32, _I64, _I64, _I64, _P, _P],
     "rfx_cl_dgelu": [_P, _P, _P, _I64, _P],
@@ -271,6 +283,10 @@ SIGNATURES = {
     "rfx_cl_im2col_fm": [_P, _P, _P, _I32, _I32, _I32, _P, _P],
     "rfx_fm_cm_affine": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P],
     "rfx_cl_dconv_ok": [_I32, _I32, _I32, _I32],
+    "rfx_cl_dconv_fwd_ws_partial": [_P],
+    "rfx_cl_dconv_bwd_ws_partial": [_P],
+    "rfx_cl_dconv_bwd_ws_tsum": [_P],
+    "rfx_cl_dconv_bwd_ws_sums": [_P],
     "rfx_cl_dconv_fwd": [_P, _P],
     "rfx_cl_dconv_bwd": [_P, _P, _P],
     "rfx_segment_split": [_P, _P, _I32, _I64, _I32, _I32, _I32, _P],
@@ -282,8 +298,8 @@ SIGNATURES = {
     "rfx_sum_diff_adj": [_P, _P, _P, _I32, _I64, _P],
 }
 
-_RET64 = {"rfx_cl_wgrad_ws_floats", "rfx_cplx_slots", "rfx_norm_bwd_work_floats", "rfx_stft_pair_loss_ws", "rfx_stft_scaled_loss_ws", "rfx_channel_sum_ws", "rfx_fft_synthesis_ws",
-          "rfx_fx_phaser_ws_floats", "rfx_fx_sox_reverb_ws_floats", "rfx_fx_normalize_ws_bytes", "rfx_time_sums_ws", "rfx_logcosh_ws", "rfx_wiener_ws_floats"}
+# the queries that return int64_t: every workspace size but the LSTM's (int)
+_RET64 = {n for n in SIGNATURES if n.endswith("_ws") or "_ws_" in n or n == "rfx_norm_bwd_work_floats"} - {"rfx_lstm_ws_bytes"}
 _lib = None
 
 

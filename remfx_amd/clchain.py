@@ -84,7 +84,7 @@ def rowsum(x, A, Cc, out, scale=1.0, accumulate=False):
             raise ValueError("rowsum: folding rows needs a contiguous tensor")
         N, ct.ns = N * XA, ct.as_
     G = max(1, min(N, -(-2048 // A)))
-    partial = torch.empty((G, A, Cc), device=x.device, dtype=torch.float32)
+    partial = ops.scratch("rfx_cl_rowsum_ws", N, A, B, Cc, G, device=x.device, dtype=torch.float32)
     ops.launch("rfx_cl_rowsum", C.byref(ct), N, A, B, Cc, G, float(scale), partial, out, int(accumulate))
     return out
 

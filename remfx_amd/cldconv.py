@@ -6,6 +6,7 @@ version), the launch descriptors, and the autograd node.  The two weight-gradien
 the dz / dh tensors the backward kernel leaves (deterministic, GradSink-aware through clchain._wgrad).
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -114,6 +115,21 @@ def _empty(name, shape, dtype, device):
     return torch.empty(shape, device=device, dtype=dtype)
 
 
+@functools.lru_cache(maxsize=None)
+def _scratch_size(ws_query, S, Cc, H, grid, TPS):
+    """The library's answer for one scratch field: a function of these five numbers alone, asked once per geometry (a training
+    step makes the same three dozen calls every time)."""
+    d = ClDconvDesc()
+    d.S, d.C, d.H, d.grid, d.TPS = S, Cc, H, grid, TPS
+    return ops.scratch_size(ws_query, C.byref(d))
+
+
+def _scratch(alloc, name, ws_query, d, device):
+    """The fp32 scratch field `name` of descriptor d (S, C, H, grid, TPS set), sized by the library; None where the call uses none."""
+    n = _scratch_size(ws_query, d.S, d.C, d.H, d.grid, d.TPS)
+    return alloc(name, (n,), torch.float32, device) if n else None
+
+
 def layer_forward(x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps, train, alloc=_empty):
     """One fused layer on x (Bn, A, 256 k, C) channels-last bf16: y, and what the backward pass reads -- a, hpre (Bn, A, 256 k, HP) bf16
     and stats (Bn * A, 4) fp32 (mean1, rstd1, mean2, rstd2); a / hpre are None without `train`, stats too where a sample is one tile.
@@ -136,8 +152,8 @@ def layer_forward(x, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, dil, eps, train,
     if train or TPS > 1:
         stats = alloc("stats", (Bn * A, 4), torch.float32, dev)
         d.stats = stats.data_ptr()
-    if TPS > 1:
-        part = alloc("part", (S, 2), torch.float32, dev)
+    if TPS > 1:                                     # the statistics passes leave their tile sums in d.partial
+        part = _scratch(alloc, "part", "rfx_cl_dconv_fwd_ws_partial", d, dev)
         d.partial = part.data_ptr()
     if train:
         a = alloc("a", (Bn, A, Tt, HP), torch.bfloat16, dev)
@@ -163,20 +179,20 @@ def layer_backward(gy, x, a, hpre, stats, w1, b1, g1w, g1b, w2, b2, g2w, g2b, sc
     dz = alloc("dz", (Bn, A, Tt, 2 * Cc), torch.bfloat16, dev)
     dh = alloc("dh", (Bn, A, Tt, HP), torch.bfloat16, dev)
     npg = 5 * Cc + 2 * H
-    partial = alloc("partial", (min(GRID, S), npg), torch.float32, dev)
     # the five small gradients go straight into the parameters' slices of the flat gradient buffer when a GradSink is armed
     # (autograd would add each returned tensor into .grad with a launch of its own)
     sw = ops.sink_write(scale, g2w, g2b, g1w, g1b)
     pg = None if sw is not None else alloc("pg", (npg,), torch.float32, dev)
     d = _desc(Cc, H, dil, eps, S, b1, g1w, g1b, b2, g2w, g2b, scale)
     d.TPS = TPS
+    partial = _scratch(alloc, "partial", "rfx_cl_dconv_bwd_ws_partial", d, dev)     # one row of npg sums per workgroup
     d.gy, d.y, d.a, d.hpre, d.stats = gy.data_ptr(), dx.data_ptr(), a.data_ptr(), hpre.data_ptr(), stats.data_ptr()
     d.dz, d.dh, d.partial = dz.data_ptr(), dh.data_ptr(), partial.data_ptr()
     d.w2p = clchain.packed(tb["w2p"], w2).data_ptr()
     d.w2dp = clchain.packed(tb["w2dp"], w2).data_ptr()
     if passes:
-        tsum = alloc("tsum", (S, 2), torch.float32, dev)
-        sums = alloc("sums", (Bn * A, 4), torch.float32, dev)
+        tsum = _scratch(alloc, "tsum", "rfx_cl_dconv_bwd_ws_tsum", d, dev)
+        sums = _scratch(alloc, "sums", "rfx_cl_dconv_bwd_ws_sums", d, dev)
         d.tsum, d.sums = tsum.data_ptr(), sums.data_ptr()
     else:
         d.w1dp = clchain.packed(tb["w1dp"], w1).data_ptr()

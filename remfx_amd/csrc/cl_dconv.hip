@@ -67,7 +67,13 @@ struct CldCfg {
   static constexpr int B_A = CLD_T * RS, B_HI = B_A + CLD_T * RSH, B_DZ = B_HI + CLD_T * RSH, B_DH = B_DZ + CLD_T * RSZ,
                        B_W2 = B_DH + (CLD_T + 2 * CLD_HALO) * RSH, B_W2D = B_W2 + KH * NT2 * 1024, B_W1D = B_W2D + (2 * C / 16) * 1024,
                        B_RED = B_W1D + 3 * KH * NTV * 1024, B_LDS = B_RED + 8 * 64 * 4 * 0 + 512;
+  // 16-byte global stores ONE wave issues for its 32 rows of an output image (64 lanes x 16 bytes = 1 KiB each): y / dx [.][C], dz
+  // [.][2 C], dh [.][HP].  The store loops of the three prefetching kernels run to these bounds and their counted waits
+  // (cld_wait_vm<..>, which leave exactly these stores in flight behind an untracked LDS-DMA prefetch) are sums of the same names:
+  // a store loop cannot change without its wait.
+  static constexpr int ST_X = 32 * RS / 1024, ST_Z = 32 * RSZ / 1024, ST_H = 32 * RSH / 1024;
   static_assert(C % 16 == 0 && H * 4 == C && HP <= 32, "");
+  static_assert(ST_X == KC && ST_Z == 2 * KC && ST_H == KH, "");
 };
 
 // cooperative copy of `bytes` (a multiple of 1024) from global to LDS, linear
@@ -163,7 +169,8 @@ __global__ __launch_bounds__(512, 2) void cl_dconv_fwd_kernel(const ClDconvK g) 
   // two x images: the next tile's rows arrive by untracked LDS-DMA while this one is worked on (section 4.13 of DESIGN.md: with the
   // builtin the compiler drains the DMA at the first LDS read it cannot prove disjoint); all in-loop barriers are raw, __syncthreads()
   // would drain it too
-  constexpr int NVM = (PH == 0 || PH == 3) ? KC : 0;          // this wave's stores that are certain to follow a prefetch (the y rows)
+  constexpr int NVM = (PH == 0 || PH == 3) ? Cfg::ST_X : 0;   // this wave's stores that are certain to follow a prefetch (the y rows)
+  static_assert(NVM <= 16, "cld_wait_vm counts up to 16");
   unsigned char* ximg = cld_smem;
   float* red = reinterpret_cast<float*>(cld_smem + Cfg::F_RED);
   const bool train = d.a != nullptr;
@@ -391,10 +398,12 @@ __global__ __launch_bounds__(512, 2) void cl_dconv_fwd_kernel(const ClDconvK g) 
       unsigned char* yo = reinterpret_cast<unsigned char*>(d.y) + (int64_t)s * (CLD_T * RS) + p0 * RS + lane * 16;
       const unsigned char* yi = ximg + (CLD_HALO + p0) * RS + lane * 16;
 #pragma unroll
-      for (int i = 0; i < KC; ++i) *reinterpret_cast<uint4*>(yo + i * 1024) = *reinterpret_cast<const uint4*>(yi + i * 1024);
+      for (int i = 0; i < Cfg::ST_X; ++i) *reinterpret_cast<uint4*>(yo + i * 1024) = *reinterpret_cast<const uint4*>(yi + i * 1024);
     }
-    // the next sample's DMA overwrites this wave's rows: its own LDS reads above are done (program order + the waits), the
-    // other waves' halo reads of them happened before the first statistics barrier of this sample
+    // the two images alternate: the DMA issued at the top of the next iteration (the sample after the next) overwrites this wave's
+    // rows of THIS image.  Its own LDS reads of them above are done (program order + this wait); the other waves' halo reads of
+    // them happened before the first statistics barrier of this sample.  The ST_X stores just issued are what cld_wait_vm<NVM>
+    // leaves in flight there.
     CL_LGKM0();
   }
 }
@@ -744,7 +753,8 @@ __global__ __launch_bounds__(512, 1) void cl_dconv_bwd8_kernel(const ClDconvK g)
 #pragma unroll
     for (int i = 0; i < KH; ++i) cld_glds16_quiet(rs, img + r0 * RSH + i * 1024, hb + i * 1024);
   };
-  constexpr int NSTORE = 3 * KC + KH;                             // 16-byte global stores per wave and sample
+  constexpr int NSTORE = Cfg::ST_X + Cfg::ST_Z + Cfg::ST_H;       // 16-byte global stores per wave and sample: dx, dz, dh
+  static_assert(NSTORE <= 16, "cld_wait_vm counts up to 16");
   float4 st_next = make_float4(0.f, 0.f, 0.f, 0.f);
   if ((int)blockIdx.x < d.S) {
     fetch_g(blockIdx.x, cld_smem);
@@ -953,13 +963,13 @@ __global__ __launch_bounds__(512, 1) void cl_dconv_bwd8_kernel(const ClDconvK g)
       // (LDS reads the compiler cannot see: it would put `s_waitcnt vmcnt(0)` -- the next sample's DMA pieces -- in front of them)
       unsigned char* o = reinterpret_cast<unsigned char*>(d.y) + (int64_t)s * (CLD_T * RS) + r0 * RS + lane * 16;
 #pragma unroll
-      for (int i = 0; i < KC; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = cld_lds_read16(gimg + r0 * RS + i * 1024 + lane * 16);
+      for (int i = 0; i < Cfg::ST_X; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = cld_lds_read16(gimg + r0 * RS + i * 1024 + lane * 16);
       o = reinterpret_cast<unsigned char*>(d.dz) + (int64_t)s * (CLD_T * RSZ) + r0 * RSZ + lane * 16;
 #pragma unroll
-      for (int i = 0; i < 2 * KC; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = cld_lds_read16(zimg + r0 * RSZ + i * 1024 + lane * 16);
+      for (int i = 0; i < Cfg::ST_Z; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = cld_lds_read16(zimg + r0 * RSZ + i * 1024 + lane * 16);
       o = reinterpret_cast<unsigned char*>(d.dh) + (int64_t)s * (CLD_T * RSH) + r0 * RSH + lane * 16;
 #pragma unroll
-      for (int i = 0; i < KH; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = cld_lds_read16(dhimg + (CLD_HALO + r0) * RSH + i * 1024 + lane * 16);
+      for (int i = 0; i < Cfg::ST_H; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = cld_lds_read16(dhimg + (CLD_HALO + r0) * RSH + i * 1024 + lane * 16);
     }
     CL_LGKM0();
     // the sample after the next lands in the rows of this gy image that this wave alone read last (its own output rows)
@@ -1102,7 +1112,8 @@ __global__ __launch_bounds__(256, 1) void cl_dconv_bwdp_kernel(const ClDconvK g)
   CL_VMCNT(0);
   __syncthreads();
   // global stores of one sub-tile, this wave: the newest operations in its queue when the next sub-tile starts
-  constexpr int NSTORE = 2 * KC + (PASS == 2 ? KH : 0);
+  constexpr int NSTORE = Cfg::ST_Z + (PASS == 2 ? Cfg::ST_H : 0);      // dz, and dh in pass 2
+  static_assert(NSTORE <= 16, "cld_wait_vm counts up to 16");
   unsigned parity = 0;                                             // the block sums of consecutive tiles alternate between two scratch rows
 
   for (int s = blockIdx.x; s < d.S; s += gridDim.x) {
@@ -1246,11 +1257,11 @@ __global__ __launch_bounds__(256, 1) void cl_dconv_bwdp_kernel(const ClDconvK g)
       {
         unsigned char* o = reinterpret_cast<unsigned char*>(d.dz) + (int64_t)s * (CLD_T * RSZ) + p0 * RSZ + lane * 16;
 #pragma unroll
-        for (int i = 0; i < 2 * KC; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = *reinterpret_cast<const uint4*>(zsub + i * 1024 + lane * 16);
+        for (int i = 0; i < Cfg::ST_Z; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = *reinterpret_cast<const uint4*>(zsub + i * 1024 + lane * 16);
         if (PASS == 2) {
           o = reinterpret_cast<unsigned char*>(d.dh) + (int64_t)s * (CLD_T * RSH) + p0 * RSH + lane * 16;
 #pragma unroll
-          for (int i = 0; i < KH; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = *reinterpret_cast<const uint4*>(dhsub + i * 1024 + lane * 16);
+          for (int i = 0; i < Cfg::ST_H; ++i) *reinterpret_cast<uint4*>(o + i * 1024) = *reinterpret_cast<const uint4*>(dhsub + i * 1024 + lane * 16);
         }
       }
       CL_LGKM0();
@@ -1367,6 +1378,9 @@ __global__ __launch_bounds__(256) void cl_dconv_stats_kernel(const float* __rest
   }
 }
 
+// workgroups of every sample-loop kernel below: each strides over the S tiles and owns row blockIdx.x of `partial` (backward)
+static int cld_grid(const rfx_cl_dconv_desc& d) { return d.S < d.grid ? d.S : d.grid; }
+
 template <int C, int H, int PH>
 static int cld_launch_fwd(const rfx_cl_dconv_desc& d, hipStream_t st) {
   using Cfg = CldCfg<C, H>;
@@ -1380,7 +1394,7 @@ static int cld_launch_fwd(const rfx_cl_dconv_desc& d, hipStream_t st) {
   }
   ClDconvK k;
   k.d = d;
-  hipLaunchKernelGGL((cl_dconv_fwd_kernel<C, H, PH>), dim3(d.S < d.grid ? d.S : d.grid), dim3(512), lds, st, k);
+  hipLaunchKernelGGL((cl_dconv_fwd_kernel<C, H, PH>), dim3(cld_grid(d)), dim3(512), lds, st, k);
   RFX_CHECK_LAUNCH();
   return 0;
 }
@@ -1422,12 +1436,12 @@ static int cld_launch(const rfx_cl_dconv_desc& d, bool bwd, hipStream_t st) {
           return -3;
         attr8 = true;
       }
-      hipLaunchKernelGGL((cl_dconv_bwd8_kernel<C, H>), dim3(d.S < d.grid ? d.S : d.grid), dim3(512), lds8, st, k);
+      hipLaunchKernelGGL((cl_dconv_bwd8_kernel<C, H>), dim3(cld_grid(d)), dim3(512), lds8, st, k);
       RFX_CHECK_LAUNCH();
       return 0;
     }
   }
-  hipLaunchKernelGGL((cl_dconv_bwd_kernel<C, H>), dim3(d.S < d.grid ? d.S : d.grid), dim3(256), Cfg::B_LDS, st, k);
+  hipLaunchKernelGGL((cl_dconv_bwd_kernel<C, H>), dim3(cld_grid(d)), dim3(256), Cfg::B_LDS, st, k);
   RFX_CHECK_LAUNCH();
   return 0;
 }
@@ -1442,12 +1456,37 @@ extern "C" int rfx_cl_dconv_ok(int32_t C, int32_t H, int32_t T, int32_t backward
   return C == 48 || C == 96;
 }
 
+// What the scratch sizes depend on: S, C, H, grid, TPS -- no pointer is read.
+static bool cld_geometry_ok(const rfx_cl_dconv_desc* d, int backward) {
+  return d && d->S > 0 && d->grid > 0 && rfx_cl_dconv_ok(d->C, d->H, CLD_T, backward) && d->TPS >= 1 && d->S % d->TPS == 0;
+}
+// backward in passes (several tiles per sample, or images too large for the one-pass kernel's LDS) or in one launch
+static bool cld_bwd_in_passes(const rfx_cl_dconv_desc& d) { return d.TPS > 1 || d.C != 48; }
+
+// floats of d->partial the forward writes: the tile sums [S][2] of its statistics passes (TPS > 1), nothing otherwise
+extern "C" int64_t rfx_cl_dconv_fwd_ws_partial(const rfx_cl_dconv_desc* d) {
+  if (!cld_geometry_ok(d, 0)) return -1;
+  return d->TPS > 1 ? (int64_t)2 * d->S : 0;
+}
+// floats of d->partial ([workgroups][5 C + 2 H]), d->tsum ([S][2]) and d->sums ([S / TPS][4]; both only in passes) of the backward
+extern "C" int64_t rfx_cl_dconv_bwd_ws_partial(const rfx_cl_dconv_desc* d) {
+  if (!cld_geometry_ok(d, 1)) return -1;
+  return (int64_t)cld_grid(*d) * (5 * d->C + 2 * d->H);
+}
+extern "C" int64_t rfx_cl_dconv_bwd_ws_tsum(const rfx_cl_dconv_desc* d) {
+  if (!cld_geometry_ok(d, 1)) return -1;
+  return cld_bwd_in_passes(*d) ? (int64_t)2 * d->S : 0;
+}
+extern "C" int64_t rfx_cl_dconv_bwd_ws_sums(const rfx_cl_dconv_desc* d) {
+  if (!cld_geometry_ok(d, 1)) return -1;
+  return cld_bwd_in_passes(*d) ? (int64_t)4 * (d->S / d->TPS) : 0;
+}
+
 extern "C" int rfx_cl_dconv_fwd(const rfx_cl_dconv_desc* dp, void* stream) {
   if (!dp || !dp->x || !dp->y || !dp->w1p) return -1;
   rfx_cl_dconv_desc d = *dp;
   d.x_or_gy_ok = 1;
-  if (!cld_common_ok(&d) || !rfx_cl_dconv_ok(d.C, d.H, CLD_T, 0)) return -1;
-  if (d.TPS < 1 || d.S % d.TPS) return -1;
+  if (!cld_common_ok(&d) || !cld_geometry_ok(&d, 0)) return -1;
   if ((d.a == nullptr) != (d.hpre == nullptr)) return -1;
   if (d.TPS == 1 ? (d.a == nullptr) != (d.stats == nullptr) : (!d.stats || !d.partial)) return -1;
   if (d.C == 48) return cld_launch<48, 12>(d, false, (hipStream_t)stream);
@@ -1467,7 +1506,7 @@ static int cld_launch_bwdp(const rfx_cl_dconv_desc& d, hipStream_t st) {
   }
   ClDconvK k;
   k.d = d;
-  hipLaunchKernelGGL((cl_dconv_bwdp_kernel<C, H, PASS>), dim3(d.S < d.grid ? d.S : d.grid), dim3(256), lds, st, k);
+  hipLaunchKernelGGL((cl_dconv_bwdp_kernel<C, H, PASS>), dim3(cld_grid(d)), dim3(256), lds, st, k);
   RFX_CHECK_LAUNCH();
   return 0;
 }
@@ -1500,9 +1539,9 @@ extern "C" int rfx_cl_dconv_bwd(const rfx_cl_dconv_desc* dp, float* pgrad, void*
   if (!direct && !pgrad) return -1;
   rfx_cl_dconv_desc d = *dp;
   d.x_or_gy_ok = 1;
-  if (!cld_common_ok(&d) || !rfx_cl_dconv_ok(d.C, d.H, CLD_T, 1) || d.TPS < 1 || d.S % d.TPS) return -1;
+  if (!cld_common_ok(&d) || !cld_geometry_ok(&d, 1)) return -1;
   int rc;
-  if (d.TPS > 1 || d.C != 48) {                       // passes: the caller computes dx (y unused)
+  if (cld_bwd_in_passes(d)) {                         // passes: the caller computes dx (y unused)
     if (!d.tsum || !d.sums) return -1;
     rc = d.C == 48 ? cld_backward_passes<48, 12>(d, (hipStream_t)stream) : cld_backward_passes<96, 24>(d, (hipStream_t)stream);
   } else {
@@ -1510,7 +1549,7 @@ extern "C" int rfx_cl_dconv_bwd(const rfx_cl_dconv_desc* dp, float* pgrad, void*
     rc = cld_launch<48, 12>(d, true, (hipStream_t)stream);
   }
   if (rc) return rc;
-  const int n = 5 * d.C + 2 * d.H, G = d.S < d.grid ? d.S : d.grid;
+  const int n = 5 * d.C + 2 * d.H, G = cld_grid(d);
   CldPgDst dst;
   for (int q = 0; q < 5; ++q) dst.p[q] = d.pg_dst[q];
   hipLaunchKernelGGL(cl_dconv_pgrad_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, d.partial, n, G, pgrad, dst, d.C, d.H);

@@ -194,10 +194,14 @@ __global__ __launch_bounds__(256) void cl_rowsum_final_kernel(const float* __res
   if (l == 0) out[i] = accumulate ? out[i] + s : s;
 }
 
+// floats of `partial`: G fixed-order partials of A * C floats, one per grid row of cl_rowsum_partial_kernel
+extern "C" int64_t rfx_cl_rowsum_ws(int32_t N, int32_t A, int32_t B, int32_t C, int32_t G) {
+  if (N <= 0 || A <= 0 || B <= 0 || C <= 0 || C % 8 || C > 256 || G < 1) return -1;
+  return (int64_t)G * A * C;
+}
 extern "C" int rfx_cl_rowsum(const rfx_cl_tensor* x, int32_t N, int32_t A, int32_t B, int32_t C, int32_t G, float scale, float* partial,
                              float* out, int32_t accumulate, void* stream) {
-  if (!x || !x->p || !partial || !out || N <= 0 || A <= 0 || B <= 0 || C <= 0 || C % 8 || C > 256 || G < 1 || x->bs % 8 || x->c0 % 8)
-    return -1;
+  if (!x || !x->p || !partial || !out || rfx_cl_rowsum_ws(N, A, B, C, G) < 0 || x->bs % 8 || x->c0 % 8) return -1;
   hipLaunchKernelGGL(cl_rowsum_partial_kernel, dim3((unsigned)A, (unsigned)G), dim3(256), 0, (hipStream_t)stream, *x, N, A, B, C, G, partial);
   const int64_t n = (int64_t)A * C;
   hipLaunchKernelGGL(cl_rowsum_final_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, partial, n, G, scale, out,

@@ -206,20 +206,29 @@ static int cx_grid(int64_t total) {
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-// slots per channel of the two reductions below: one per (sample, 4096-value chunk)
-extern "C" int64_t rfx_cplx_slots(int32_t N, int64_t S) {
-  if (N <= 0 || S <= 0) return -1;
-  return (int64_t)N * ((S + CX_CHUNK - 1) / CX_CHUNK);
+// slots per channel of the two reductions below: one per (sample, 4096-value chunk); -1: geometry both launchers refuse
+static int64_t cx_slots(int32_t N, int32_t C, int64_t S) {
+  if (N <= 0 || C <= 0 || S <= 0) return -1;
+  const int64_t slots = (int64_t)N * ((S + CX_CHUNK - 1) / CX_CHUNK);
+  return slots > 0x7fffffff ? -1 : slots;
+}
+constexpr int CX_MOMENTS = 5, CX_COEFS = 6;       // values per (channel, slot) of rfx_cplx_moments / rfx_cplx_affine_act_bwd
+extern "C" int64_t rfx_cplx_moments_ws(int32_t N, int32_t C, int64_t S) {
+  const int64_t slots = cx_slots(N, C, S);
+  return slots < 0 ? -1 : CX_MOMENTS * C * slots;
+}
+extern "C" int64_t rfx_cplx_affine_act_bwd_ws(int32_t N, int32_t C, int64_t S) {
+  const int64_t slots = cx_slots(N, C, S);
+  return slots < 0 ? -1 : CX_COEFS * C * slots;
 }
 extern "C" int rfx_cplx_moments(const float* x, int32_t N, int32_t C, int64_t S, double* ws, double* sums, void* stream) {
-  if (!x || !ws || !sums || N <= 0 || C <= 0 || S <= 0) return -1;
+  if (!x || !ws || !sums || cx_slots(N, C, S) < 0) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int nchunks = (int)((S + CX_CHUNK - 1) / CX_CHUNK);
+  const int nchunks = (int)(cx_slots(N, C, S) / N);
   const int64_t items = (int64_t)N * C * nchunks;
-  if ((int64_t)N * nchunks > 0x7fffffff) return -1;
   hipLaunchKernelGGL(cplx_moments_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, x, N, C, S, nchunks, ws);
   RFX_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rfx_slot_sum_kernel<double>, RFX_SLOT_SUM_GRID(5 * C), 0, s, ws, C, N * nchunks, 5, sums);
+  hipLaunchKernelGGL(rfx_slot_sum_kernel<double>, RFX_SLOT_SUM_GRID(CX_MOMENTS * C), 0, s, ws, C, N * nchunks, CX_MOMENTS, sums);
   RFX_CHECK_LAUNCH();
   return 0;
 }
@@ -247,15 +256,14 @@ extern "C" int rfx_cplx_affine_act_fwd(const float* x, const float* coef, int32_
 extern "C" int rfx_cplx_affine_act_bwd(const float* x, const float* coef, const float* gy, int64_t gy_ns,
                                        int64_t gy_im_off, int32_t N, int32_t C, int64_t S, float slope, float* gx,
                                        double* ws, float* gcoef, void* stream) {
-  if (!x || !coef || !gy || !gx || !ws || !gcoef || N <= 0 || C <= 0 || S <= 0) return -1;
+  if (!x || !coef || !gy || !gx || !ws || !gcoef || cx_slots(N, C, S) < 0) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int nchunks = (int)((S + CX_CHUNK - 1) / CX_CHUNK);
+  const int nchunks = (int)(cx_slots(N, C, S) / N);
   const int64_t items = (int64_t)N * C * nchunks;
-  if ((int64_t)N * nchunks > 0x7fffffff) return -1;
   hipLaunchKernelGGL(cplx_affine_act_bwd_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, x, coef, gy, gy_ns,
                      gy_im_off, N, C, S, nchunks, slope, gx, ws);
   RFX_CHECK_LAUNCH();
-  hipLaunchKernelGGL(rfx_slot_sum_kernel<float>, RFX_SLOT_SUM_GRID(6 * C), 0, s, ws, 6 * C, N * nchunks, 1, gcoef);
+  hipLaunchKernelGGL(rfx_slot_sum_kernel<float>, RFX_SLOT_SUM_GRID(CX_COEFS * C), 0, s, ws, CX_COEFS * C, N * nchunks, 1, gcoef);
   RFX_CHECK_LAUNCH();
   return 0;
 }

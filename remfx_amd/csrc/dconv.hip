@@ -660,9 +660,17 @@ static int dconv_launch_bwd(const DconvArgs& a, int grid, hipStream_t s) {
   return 0;
 }
 
-// partial: rfx_dconv_layer_bwd_rows(N) rows of 5C + 2H floats [dscale C | dgn2w 2C | dgn2b 2C | dgn1w H | dgn1b H]; the caller sums the rows
+// partial: one row per workgroup of 5C + 2H floats [dscale C | dgn2w 2C | dgn2b 2C | dgn1w H | dgn1b H]; the caller sums the rows
 extern "C" int rfx_dconv_layer_ok(int32_t C, int32_t T, int32_t dil);
-extern "C" int rfx_dconv_layer_bwd_rows(int32_t N) { const int pairs = (N + 1) / 2; return pairs < 256 ? pairs : 256; }
+constexpr int DC_BWD_MAX_GRID = 256;
+static int dconv_bwd_grid(int32_t N) {                                // a workgroup takes sample pairs
+  const int pairs = (N + 1) / 2;
+  return pairs < DC_BWD_MAX_GRID ? pairs : DC_BWD_MAX_GRID;
+}
+extern "C" int64_t rfx_dconv_layer_bwd_ws(int32_t N, int32_t C, int32_t T, int32_t dil) {
+  if (N <= 0 || !rfx_dconv_layer_ok(C, T, dil)) return -1;
+  return (int64_t)dconv_bwd_grid(N) * DcLdsBwd<48>::ROWS;
+}
 extern "C" int rfx_dconv_layer_bwd(const float* x, const float* g, float* gx, int32_t N, int32_t C, int32_t T, int32_t dil,
                                    const float* w1, const float* b1, const float* gn1w, const float* gn1b, const float* w2,
                                    const float* b2, const float* gn2w, const float* gn2b, const float* scale, float eps,
@@ -673,7 +681,7 @@ extern "C" int rfx_dconv_layer_bwd(const float* x, const float* g, float* gx, in
   a.dz = (uint16_t*)dz_bf16; a.a_out = a_out; a.dh = (uint16_t*)dh_bf16; a.partial = partial;
   if (!(x && g && gx && w1 && b1 && gn1w && gn1b && w2 && b2 && gn2w && gn2b && scale && dz_bf16 && a_out && dh_bf16 && partial && N > 0) ||
       !rfx_dconv_layer_ok(C, T, dil)) return -1;
-  return dconv_launch_bwd<48>(a, rfx_dconv_layer_bwd_rows(N), (hipStream_t)stream);
+  return dconv_launch_bwd<48>(a, dconv_bwd_grid(N), (hipStream_t)stream);
 }
 
 extern "C" int rfx_dconv_layer_ok(int32_t C, int32_t T, int32_t dil) { return T == DC_T && C == 48 && (dil == 1 || dil == 2); }

@@ -315,27 +315,40 @@ __global__ void prelu_fwd_kernel(const float* __restrict__ x, const float* __res
     yr[i] = v >= 0.f ? v : s * v;
   }
 }
+// one workgroup per (sample, channel) row; the backward stores one fp64 slot per workgroup.  -1: geometry both launchers refuse
+static int64_t prelu_grid(int64_t N, int64_t C, int64_t L) {
+  return (N <= 0 || C <= 0 || L <= 0 || N * C > 0x7fffffffLL) ? -1 : N * C;
+}
 extern "C" int rfx_prelu_fwd(const float* x, const float* slope, float* y, int64_t N, int64_t C, int64_t L, void* stream) {
-  if (!x || !slope || !y || N <= 0 || C <= 0 || L <= 0 || N * C > 0x7fffffffLL) return -1;
-  hipLaunchKernelGGL(prelu_fwd_kernel, dim3((unsigned)(N * C)), dim3(256), 0, (hipStream_t)stream, x, slope, y, C, L);
+  const int64_t grid = prelu_grid(N, C, L);
+  if (!x || !slope || !y || grid < 0) return -1;
+  hipLaunchKernelGGL(prelu_fwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, slope, y, C, L);
   RFX_CHECK_LAUNCH();
   return 0;
 }
+extern "C" int64_t rfx_prelu_bwd_ws(int64_t N, int64_t C, int64_t L) { return prelu_grid(N, C, L); }
 extern "C" int rfx_prelu_bwd(const float* x, const float* gy, const float* slope, float* gx,
-                             double* ws /* N * C doubles */, float* gslope, int64_t N, int64_t C, int64_t L, void* stream) {
-  if (!x || !gy || !slope || !gx || !ws || !gslope || N <= 0 || C <= 0 || L <= 0 || N * C > 0x7fffffff) return -1;
-  hipLaunchKernelGGL(prelu_bwd_kernel, dim3((unsigned)(N * C)), dim3(256), 0, (hipStream_t)stream, x, gy,
+                             double* ws /* rfx_prelu_bwd_ws doubles */, float* gslope, int64_t N, int64_t C, int64_t L, void* stream) {
+  const int64_t grid = prelu_grid(N, C, L);
+  if (!x || !gy || !slope || !gx || !ws || !gslope || grid < 0) return -1;
+  hipLaunchKernelGGL(prelu_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, gy,
                      slope, gx, ws, N, C, L);
   RFX_CHECK_LAUNCH();
   hipLaunchKernelGGL(rfx_slot_sum_kernel<float>, RFX_SLOT_SUM_GRID((int)C), 0, (hipStream_t)stream, ws, (int)C, (int)N, 1, gslope);
   RFX_CHECK_LAUNCH();
   return 0;
 }
-// out[0] = scale * sum |a - b|; ws: RFX_L1_SLOTS doubles (per-workgroup partials, no initialisation needed)
+// out[0] = scale * sum |a - b|; ws: rfx_l1_sum_ws(n) doubles (per-workgroup partials, no initialisation needed)
+constexpr int L1_MAX_SLOTS = 512;
+static int l1_slots(int64_t n) {                                        // n == 0: out[0] = 0 and no slot, as rfx_sumsq
+  const int g = n > 0 ? grid_for(n) : 0;
+  return g > L1_MAX_SLOTS ? L1_MAX_SLOTS : g;                           // <= L1_MAX_SLOTS = rfx_l1_sum_ws, by this clamp
+}
+// the bound of l1_slots, not l1_slots(n): one buffer serves every n
+extern "C" int64_t rfx_l1_sum_ws(int64_t n) { return n < 0 ? -1 : L1_MAX_SLOTS; }
 extern "C" int rfx_l1_sum(const float* a, const float* b, int64_t n, double* ws, float scale, float* out, void* stream) {
   if (!a || !b || !out || !ws || n < 0) return -1;
-  int g = n > 0 ? grid_for(n) : 0;                                      // n == 0: out[0] = 0 and no slot, as rfx_sumsq
-  g = g > RFX_L1_SLOTS ? RFX_L1_SLOTS : g;
+  const int g = l1_slots(n);
   if (g) {
     hipLaunchKernelGGL(l1_sum_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, a, b, n, ws);
     RFX_CHECK_LAUNCH();
@@ -528,15 +541,19 @@ extern "C" int rfx_blstm_frames(const float* src, const float* skip, float* dst,
   RFX_CHECK_LAUNCH();
   return 0;
 }
-extern "C" int rfx_row_moments_slots(int64_t L) {
+constexpr int ROW_MOMENTS_MAX_SLOTS = 256;
+static int row_moments_slots(int64_t L) {                               // workgroups per row, one slot each
   const int64_t gx = (L + 16383) / 16384;
-  return (int)(gx < 1 ? 1 : (gx > 256 ? 256 : gx));
+  return (int)(gx < 1 ? 1 : (gx > ROW_MOMENTS_MAX_SLOTS ? ROW_MOMENTS_MAX_SLOTS : gx));
+}
+extern "C" int64_t rfx_row_moments_ws(int32_t R, int64_t L) {
+  return (R <= 0 || L <= 1) ? -1 : (int64_t)2 * R * row_moments_slots(L);
 }
 extern "C" int rfx_row_moments(const float* x, int32_t R, int64_t L, double* sums, float* mean, float* stdv, float eps, float* coef_a,
                                float* coef_b, void* stream) {
   if (!x || !sums || !mean || !stdv || R <= 0 || L <= 1 || (!coef_a) != (!coef_b)) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int gx = rfx_row_moments_slots(L);
+  const int gx = row_moments_slots(L);
   hipLaunchKernelGGL(row_moments_kernel, dim3(gx, R), dim3(256), 0, s, x, L, sums);
   RFX_CHECK_LAUNCH();
   hipLaunchKernelGGL(row_moments_finalize_kernel, dim3((R + 3) / 4), dim3(256), 0, s, sums, R, gx, (double)L, mean, stdv, eps, coef_a,

@@ -703,7 +703,10 @@ static dim3 fx_grid(int64_t T, int B, int per_block) {
   if (gx < 1) gx = 1;
   return dim3((unsigned)gx, (unsigned)B);
 }
-static bool fx_ok(const void* x, const void* y, int B, int64_t T) { return x && y && B > 0 && B <= 65535 && T > 0; }
+static bool fx_geometry_ok(int B, int64_t T) { return B > 0 && B <= 65535 && T > 0; }
+static bool fx_ok(const void* x, const void* y, int B, int64_t T) { return x && y && fx_geometry_ok(B, T); }
+// floats of one (B, T) envelope image: env_ws of the compressor; the limiter's ws holds two (stage 2's envelope, stage 1's output)
+static int64_t fx_env_floats(int B, int64_t T) { return (int64_t)B * T; }
 
 extern "C" int rfx_fx_distortion(const float* x, float* y, int32_t B, int64_t T, const float* gain, void* stream) {
   if (!fx_ok(x, y, B, T) || !gain) return -1;
@@ -732,6 +735,7 @@ extern "C" int rfx_fx_chorus(const float* x, float* y, int32_t B, int64_t T, flo
   RFX_CHECK_LAUNCH();
   return 0;
 }
+extern "C" int64_t rfx_fx_compressor_ws(int32_t B, int64_t T) { return fx_geometry_ok(B, T) ? fx_env_floats(B, T) : -1; }
 extern "C" int rfx_fx_compressor(const float* x, float* y, float* env_ws, int32_t B, int64_t T, const float* threshold_lin,
                                  const float* ratio, const float* c_attack, const float* c_release, void* stream) {
   if (!fx_ok(x, y, B, T) || !env_ws || !threshold_lin || !ratio || !c_attack || !c_release) return -1;
@@ -784,18 +788,30 @@ extern "C" int rfx_fx_sox_reverb(const float* x, float* y, float* ws, int32_t B,
   RFX_CHECK_LAUNCH();
   return 0;
 }
+// doubles of hop_ws: nhop hop sums per row of the K-weighting pass; -1: geometry the launcher refuses
+static int64_t fx_hop_doubles(int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk) {
+  if (B <= 0 || C <= 0 || (int64_t)B * C > 65535 || T <= 0 || chunk <= 0 || hop_len <= 0 || nhop < 4 || nblk < 1 || nblk + 3 > nhop ||
+      (int64_t)chunk * 64 < T) return -1;
+  return (int64_t)B * C * nhop;
+}
+extern "C" int64_t rfx_fx_loudness_ws(int32_t B, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk) {
+  return fx_hop_doubles(B, 1, T, chunk, hop_len, nhop, nblk);
+}
+extern "C" int64_t rfx_fx_loudness_joint_ws(int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk) {
+  return fx_hop_doubles(B, C, T, chunk, hop_len, nhop, nblk);
+}
 // B clips of C channels: the K-weighting runs over all B * C rows, the gate sums each clip's C rows of hop sums
 static int fx_loudness(const float* x, int32_t B, int32_t C, int64_t T, int32_t chunk, int32_t hop_len, int32_t nhop, int32_t nblk,
                        double inv_block, const double* coef, float target_lufs, double* hop_ws, float* lufs, float* gain,
                        void* stream) {
-  if (!x || !coef || !hop_ws || !lufs || !gain || B <= 0 || C <= 0 || (int64_t)B * C > 65535 || T <= 0 || chunk <= 0 ||
-      hop_len <= 0 || nhop < 4 || nblk < 1 || nblk + 3 > nhop || (int64_t)chunk * 64 < T) return -1;
+  const int64_t hop_doubles = fx_hop_doubles(B, C, T, chunk, hop_len, nhop, nblk);
+  if (!x || !coef || !hop_ws || !lufs || !gain || hop_doubles < 0) return -1;
   FxLoudArgs a{};
   a.x = x; a.hop = hop_ws; a.T = T; a.chunk = chunk; a.nhop = nhop; a.hop_len = hop_len; a.hop_of = nullptr;
   for (int i = 0; i < 3; ++i) { a.b1[i] = coef[i]; a.a1[i] = coef[3 + i]; a.b2[i] = coef[6 + i]; a.a2[i] = coef[9 + i]; }
   for (int i = 0; i < 16; ++i) a.M[i] = coef[12 + i];
   const int rows = B * C;
-  if (hipMemsetAsync(hop_ws, 0, sizeof(double) * (size_t)rows * nhop, (hipStream_t)stream) != hipSuccess) return -3;
+  if (hipMemsetAsync(hop_ws, 0, sizeof(double) * (size_t)hop_doubles, (hipStream_t)stream) != hipSuccess) return -3;
   hipLaunchKernelGGL(fx_kweight_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(fx_loud_gate_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, hop_ws, B, C, nhop, nblk, inv_block,
                      target_lufs, lufs, gain);
@@ -812,12 +828,13 @@ extern "C" int rfx_fx_loudness_joint(const float* x, int32_t B, int32_t C, int64
                                      float* gain, void* stream) {
   return fx_loudness(x, B, C, T, chunk, hop_len, nhop, nblk, inv_block, coef, target_lufs, hop_ws, lufs, gain, stream);
 }
+extern "C" int64_t rfx_fx_limiter_ws(int32_t B, int64_t T) { return fx_geometry_ok(B, T) ? 2 * fx_env_floats(B, T) : -1; }
 extern "C" int rfx_fx_limiter(const float* x, float* y, float* ws, int32_t B, int64_t T, const float* params, void* stream) {
   if (!fx_ok(x, y, B, T) || !ws || !params) return -1;
   const float* p[9];
   for (int i = 0; i < 9; ++i) p[i] = params + (size_t)i * B;   // thr1 ratio1 ca1 cr1 thr2 ratio2 ca2 cr2 makeup
   float* env = ws;
-  float* y1 = ws + (size_t)B * T;
+  float* y1 = ws + fx_env_floats(B, T);
   const hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(fx_comp_env_kernel, dim3((B + 63) / 64), dim3(64), 0, s, x, env, B, T, p[2], p[3]);
   hipLaunchKernelGGL(fx_comp_gain_kernel, fx_grid(T, B, 256), dim3(256), 0, s, x, env, y1, T, p[0], p[1]);

@@ -324,15 +324,27 @@ static int grid_x(int64_t n) {
   return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
 }
 // reductions: fewer, longer workgroups per row (each ends in one slot store)
+constexpr int STFT_REDUCE_MAX_SLOTS = 64;
 static int grid_red(int64_t n) {
   const int64_t b = (n + 16383) / 16384;
-  return (int)(b < 1 ? 1 : (b > 64 ? 64 : b));
+  return (int)(b < 1 ? 1 : (b > STFT_REDUCE_MAX_SLOTS ? STFT_REDUCE_MAX_SLOTS : b));   // <= the cap rfx_stft_loss_reduce_ws answers, by this clamp
 }
+// workgroups per row of the five-sum kernels (rfx_sisdr_sums, rfx_time_sums, rfx_logcosh_rows), one slot each
+constexpr int TIME_SUMS_MAX_SLOTS = 128;
+static int time_sums_grid(int64_t L) {
+  const int g = grid_x(L);
+  return g > TIME_SUMS_MAX_SLOTS ? TIME_SUMS_MAX_SLOTS : g;              // <= the cap rfx_sisdr_sums_ws answers, by this clamp
+}
+static bool loss_rows_ok(int32_t R, int64_t n) { return R > 0 && R <= RFX_LOSS_MAX_ROWS && n > 0; }
 
+// the bound of grid_red per row and sum, not grid_red(n): enough for every n
+extern "C" int64_t rfx_stft_loss_reduce_ws(int32_t R, int64_t n) {
+  return loss_rows_ok(R, n) ? (int64_t)3 * R * STFT_REDUCE_MAX_SLOTS : -1;
+}
 extern "C" int rfx_stft_loss_reduce(const float* xc, const float* yc, int32_t R, int64_t n, float eps, double* ws,
                                     float* sums, void* stream) {
-  if (!xc || !yc || !sums || !ws || R <= 0 || R > RFX_LOSS_MAX_ROWS || n <= 0) return -1;
-  const int g = grid_red(n);                                                 // <= RFX_STFT_REDUCE_SLOTS
+  if (!xc || !yc || !sums || !ws || !loss_rows_ok(R, n)) return -1;
+  const int g = grid_red(n);
   hipLaunchKernelGGL(stft_loss_reduce_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)xc, (const float2*)yc, n, eps, ws);
   RFX_CHECK_LAUNCH();
@@ -362,11 +374,14 @@ extern "C" int rfx_l1_grad(const float* a, const float* b, int64_t n, float w, c
   RFX_CHECK_LAUNCH();
   return 0;
 }
+// the bound of time_sums_grid per row and sum, not time_sums_grid(L) (that is rfx_time_sums_ws): enough for every L
+extern "C" int64_t rfx_sisdr_sums_ws(int32_t R, int64_t L) {
+  return loss_rows_ok(R, L) ? (int64_t)5 * R * TIME_SUMS_MAX_SLOTS : -1;
+}
 extern "C" int rfx_sisdr_sums(const float* x, const float* t, int32_t R, int64_t L, int64_t x_rs,
                               int64_t t_rs, double* ws, double* sums, void* stream) {
-  if (!x || !t || !sums || !ws || R <= 0 || R > RFX_LOSS_MAX_ROWS || L <= 0) return -1;
-  int g = grid_x(L);
-  g = g > RFX_SISDR_SLOTS ? RFX_SISDR_SLOTS : g;
+  if (!x || !t || !sums || !ws || !loss_rows_ok(R, L)) return -1;
+  const int g = time_sums_grid(L);
   hipLaunchKernelGGL(sisdr_sums_kernel, dim3(g, R), dim3(256), 0, (hipStream_t)stream, x, t, L, x_rs, t_rs, ws);
   RFX_CHECK_LAUNCH();
   hipLaunchKernelGGL(rfx_slot_sum_kernel<double>, RFX_SLOT_SUM_GRID(5 * R), 0, (hipStream_t)stream, ws, R, g, 5, sums);
@@ -711,10 +726,6 @@ __global__ __launch_bounds__(256) void logcosh_grad_kernel(const float* __restri
   }
 }
 
-static int time_sums_grid(int64_t L) {
-  int g = grid_x(L);
-  return g > RFX_SISDR_SLOTS ? RFX_SISDR_SLOTS : g;
-}
 // streaming passes over [R][n units]: ~4096 workgroups in all, at least 1024 units each before another workgroup is worth its launch
 static int time_stream_grid(int64_t units, int R) {
   int64_t want = (units + 1023) / 1024, cap = 4096 / R;

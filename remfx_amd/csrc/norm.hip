@@ -566,6 +566,9 @@ static int gn_grid(int64_t total) {
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
+// 4096-value chunks gn_stats_kernel cuts a run of L values into; its slotted form stores one pair of doubles per chunk
+static int gn_stat_chunks(int64_t L) { return (int)((L + GN_CHUNK - 1) / GN_CHUNK); }
+
 static int norm_fwd(int x16, int bn, int use_given_stats, int sums_given_in, const float* x, const float* gamma, const float* beta, int32_t N, int32_t C,
                                  int32_t S, int32_t G, float eps, int32_t mode, const float* res,
                                  const float* scale, double* sums /* N*G*2 workspace */, float* mean,
@@ -589,12 +592,12 @@ static int norm_fwd(int x16, int bn, int use_given_stats, int sums_given_in, con
     // S = 128 -- with 196608 waves of 128 values and 768 same-address fp64 atomics per group: 0.06 of HBM in the r02c profile.)
     GnArgs st = a;
     if (!bn) { st.C = G; st.S = (C / G) * S; }
-    const int nchunks = (st.S + GN_CHUNK - 1) / GN_CHUNK;
+    const int nchunks = gn_stat_chunks(st.S);
     const int64_t nitems = (int64_t)N * st.C * nchunks;
     int slots = sums_given > 1 ? sums_given : 1;
     if (!sums_given) {
       if (sums_given == 0 && (sums_slotted || bn)) {
-        // `sums` holds N * G * nchunks pairs (rfx_groupnorm_stat_chunks; BatchNorm: C * N * nchunks, rfx_batchnorm_stat_slots): every
+        // `sums` holds N * G * nchunks pairs (rfx_groupnorm_fwd_ws; BatchNorm: C * N * nchunks, rfx_batchnorm_fwd_ws): every
         // (group, chunk) wave stores its own
         if (x16) hipLaunchKernelGGL((gn_stats_kernel<rfx_bf16s, true>), dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, s, st, sums, nchunks);
         else hipLaunchKernelGGL((gn_stats_kernel<float, true>), dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, s, st, sums, nchunks);
@@ -1212,13 +1215,17 @@ extern "C" int64_t rfx_norm_bwd_work_floats(int32_t N, int32_t C, int32_t S, int
   if (nchunks > 1) n += (int64_t)N * C * 2 * nchunks + (int64_t)N * (C / 2) * nchunks;
   return n;
 }
-// fp64 PAIRS of `sums` rfx_batchnorm_fwd needs per channel when it computes the batch statistics: one slot per (sample, chunk)
-extern "C" int rfx_batchnorm_stat_slots(int32_t N, int32_t S) {
-  if (N <= 0 || S <= 0) return -1;
-  return N * ((S + GN_CHUNK - 1) / GN_CHUNK);
+// doubles of `sums` rfx_batchnorm_fwd needs when it computes the batch statistics: one pair per (channel, sample, chunk)
+extern "C" int64_t rfx_batchnorm_fwd_ws(int32_t N, int32_t C, int32_t S) {
+  if (N <= 0 || C <= 0 || S <= 0) return -1;
+  return (int64_t)2 * C * N * gn_stat_chunks(S);
 }
 extern "C" int rfx_groupnorm_stat_chunks(int32_t C, int32_t S, int32_t G) {
   if (C <= 0 || S <= 0 || G <= 0 || C % G) return -1;
-  const int64_t L = (int64_t)(C / G) * S;
-  return (int)((L + GN_CHUNK - 1) / GN_CHUNK);
+  return gn_stat_chunks((int64_t)(C / G) * S);
+}
+// doubles of `sums` in the slotted form (sums_given = -1) of rfx_groupnorm_fwd / _x16: one pair per (sample, group, chunk)
+extern "C" int64_t rfx_groupnorm_fwd_ws(int32_t N, int32_t C, int32_t S, int32_t G) {
+  const int chunks = rfx_groupnorm_stat_chunks(C, S, G);
+  return (N <= 0 || chunks < 0) ? -1 : (int64_t)2 * N * G * chunks;
 }

@@ -60,9 +60,16 @@ __global__ void clip_coef_kernel(const double* __restrict__ sumsq, float max_nor
   *coef = (c < 1.f ? c : 1.f) * pre;
 }
 
-static int gridn(int64_t n) {
+constexpr int ADAMW_MAX_GRID = 4096;
+static int adamw_grid(int64_t n) {
   const int64_t b = (n + 1023) / 1024;
-  return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+  return (int)(b < 1 ? 1 : (b > ADAMW_MAX_GRID ? ADAMW_MAX_GRID : b));
+}
+// workgroups of sumsq_kernel = slots of its workspace: its own rule, so that retuning the AdamW grid cannot resize it
+constexpr int SUMSQ_MAX_SLOTS = 4096;
+static int sumsq_slots(int64_t n) {
+  const int64_t b = (n + 1023) / 1024;
+  return n > 0 ? (int)(b > SUMSQ_MAX_SLOTS ? SUMSQ_MAX_SLOTS : b) : 0;   // <= SUMSQ_MAX_SLOTS = rfx_sumsq_ws, by this clamp
 }
 
 extern "C" int rfx_zero(void* p, int64_t nbytes, void* stream) {
@@ -75,10 +82,12 @@ extern "C" int rfx_zero(void* p, int64_t nbytes, void* stream) {
   RFX_CHECK_LAUNCH();
   return 0;
 }
-// out[0] = sum g^2 (fp64); ws: RFX_SUMSQ_SLOTS doubles of per-workgroup partials (no initialisation needed), added in slot order
+// out[0] = sum g^2 (fp64); ws: rfx_sumsq_ws(n) doubles of per-workgroup partials (no initialisation needed), added in slot order.
+// The query answers the bound of sumsq_slots, not sumsq_slots(n): the optimiser allocates once for a buffer of any length.
+extern "C" int64_t rfx_sumsq_ws(int64_t n) { return n < 0 ? -1 : SUMSQ_MAX_SLOTS; }
 extern "C" int rfx_sumsq(const float* g, int64_t n, double* ws, double* out, void* stream) {
   if (!g || !out || !ws || n < 0) return -1;
-  const int gr = n > 0 ? gridn(n) : 0;                                 // <= RFX_SUMSQ_SLOTS
+  const int gr = sumsq_slots(n);
   if (gr) {
     hipLaunchKernelGGL(sumsq_kernel, dim3(gr), dim3(256), 0, (hipStream_t)stream, g, n, ws);
     RFX_CHECK_LAUNCH();
@@ -99,7 +108,7 @@ extern "C" int rfx_adamw_step(float* p, const float* g, float* m, float* v, int6
   if (!p || !g || !m || !v || n < 0 || step < 1) return -1;
   if (n == 0) return 0;
   const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(gridn(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1, b2,
+  hipLaunchKernelGGL(adamw_kernel, dim3(adamw_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, b1, b2,
                      eps, wd, bc1, bc2, gscale);
   RFX_CHECK_LAUNCH();
   return 0;

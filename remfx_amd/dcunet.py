@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import launch, query
+from .ops import launch
 
 ENCODERS = ((1, 45, (7, 1), (1, 1)), (45, 45, (1, 7), (1, 1)), (45, 90, (7, 5), (2, 2)), (90, 90, (7, 5), (2, 1)),
             (90, 90, (5, 3), (2, 2)), (90, 90, (5, 3), (2, 1)), (90, 90, (5, 3), (2, 2)), (90, 90, (5, 3), (2, 1)),
@@ -152,7 +152,7 @@ class _CplxNormActFn(torch.autograd.Function):
         coefc = torch.empty((6, Cc), device=y.device, dtype=torch.float32)
         if norm.training:
             sums = torch.empty(Cc * 5, device=y.device, dtype=torch.float64)
-            ws = torch.empty(5 * Cc * query("rfx_cplx_slots", N, S), device=y.device, dtype=torch.float64)
+            ws = ops.scratch("rfx_cplx_moments_ws", N, Cc, S, device=y.device, dtype=torch.float64)
             launch("rfx_cplx_moments", y, N, Cc, S, ws, sums)
             inv = 1.0 / float(N * S)
             launch("rfx_cplx_coef_fwd", sums, inv, None, *pw, norm.eps, Cc, coefc, None,
@@ -181,7 +181,7 @@ class _CplxNormActFn(torch.autograd.Function):
             g = g.contiguous()
         gx = torch.empty_like(y)
         gcoef = torch.empty((6, Cc), device=y.device, dtype=torch.float32)
-        ws = torch.empty(6 * Cc * query("rfx_cplx_slots", N, S), device=y.device, dtype=torch.float64)
+        ws = ops.scratch("rfx_cplx_affine_act_bwd_ws", N, Cc, S, device=y.device, dtype=torch.float64)
         launch("rfx_cplx_affine_act_bwd", y, coefc, g, g.stride(0), Cc, N, Cc, S, LEAKY, gx, ws, gcoef)
         sums, inv, stats_in = ctx.stat
         gw = torch.empty((5, Cc), device=y.device, dtype=torch.float32)

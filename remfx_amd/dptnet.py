@@ -90,7 +90,7 @@ class _PReLUFn(torch.autograd.Function):
         x, slope = ctx.saved_tensors
         N, C, L = ctx.cfg
         gx, gs = torch.empty_like(x), torch.empty_like(slope)
-        ws = torch.empty(N * C, device=x.device, dtype=torch.float64)
+        ws = ops.scratch("rfx_prelu_bwd_ws", N, C, L, device=x.device, dtype=torch.float64)
         launch("rfx_prelu_bwd", x, g.contiguous(), slope, gx, ws, gs, N, C, L)
         return gx, gs
 

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from .ops import launch, query
+from .ops import launch, query, scratch
 
 
 def loguniform(low=0, high=1):                         # effects.py:25-26
@@ -274,8 +274,10 @@ class RandomPedalboardCompressor(_RandomEffect):
         ratio = _col(params, "ratio", dev)
         ca = _col(params, lambda p: _ballistics_cte(p["attack_ms"], self.sample_rate), dev)
         cr = _col(params, lambda p: _ballistics_cte(p["release_ms"], self.sample_rate), dev)
-        y, ws = torch.empty_like(clips), torch.empty_like(clips)
-        launch("rfx_fx_compressor", clips, y, ws, clips.shape[0], clips.shape[1], thr, ratio, ca, cr)
+        N, T = clips.shape
+        y = torch.empty_like(clips)
+        ws = scratch("rfx_fx_compressor_ws", N, T, device=dev, dtype=torch.float32)
+        launch("rfx_fx_compressor", clips, y, ws, N, T, thr, ratio, ca, cr)
         return y
 
 
@@ -343,8 +345,8 @@ class LoudnessNormalize(torch.nn.Module):
     def measure(self, clips):
         """(N, T) device clips -> (lufs (N,), gain (N,)) device tensors."""
         N, T = clips.shape
-        nhop, plan = self._plan(T)
-        hop_ws = torch.empty((N, nhop), device=clips.device, dtype=torch.float64)
+        _, plan = self._plan(T)
+        hop_ws = scratch("rfx_fx_loudness_ws", N, T, *plan[:4], device=clips.device, dtype=torch.float64)
         lufs = torch.empty(N, device=clips.device, dtype=torch.float32)
         gain = torch.empty_like(lufs)
         launch("rfx_fx_loudness", clips, N, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
@@ -353,8 +355,8 @@ class LoudnessNormalize(torch.nn.Module):
     def measure_joint(self, clips):
         """(B, C, T) device clips -> (lufs (B,), gain (B,)): every clip's C channels measured together."""
         B, Ch, T = clips.shape
-        nhop, plan = self._plan(T)
-        hop_ws = torch.empty((B * Ch, nhop), device=clips.device, dtype=torch.float64)
+        _, plan = self._plan(T)
+        hop_ws = scratch("rfx_fx_loudness_joint_ws", B, Ch, T, *plan[:4], device=clips.device, dtype=torch.float64)
         lufs = torch.empty(B, device=clips.device, dtype=torch.float32)
         gain = torch.empty_like(lufs)
         launch("rfx_fx_loudness_joint", clips, B, Ch, T, *plan, float(self.target_lufs_db), hop_ws, lufs, gain)
@@ -615,7 +617,7 @@ class RandomPedalboardLimiter(_RandomEffect):
                         _ballistics_cte(s["release_ms"], self.sample_rate)]
             cols.append(col + [makeup])
         prm = _vec(np.asarray(cols).T.copy(), clips.device)
-        ws = torch.empty((2, N, T), device=clips.device, dtype=torch.float32)
+        ws = scratch("rfx_fx_limiter_ws", N, T, device=clips.device, dtype=torch.float32)
         y = torch.empty_like(clips)
         launch("rfx_fx_limiter", clips, y, ws, N, T, prm)
         return y

@@ -53,7 +53,7 @@ import torch
 import torch.nn as nn
 
 from . import stft
-from .ops import _req, launch, query, zeros
+from .ops import _req, launch, query, scratch, zeros
 
 FFT_SIZES = (1024, 2048, 512)
 HOP_SIZES = (120, 240, 50)
@@ -288,7 +288,7 @@ class _MRSTFTFn(torch.autograd.Function):
                 sums = _MEMO.get(skey) if _MEMO is not None else None   # metric(output, target) repeats the loss's row sums
                 if sums is None:
                     sums = torch.empty((R, 3), device=x.device, dtype=torch.float32)
-                    ws = torch.empty(3 * R * 64, device=x.device, dtype=torch.float64)        # RFX_STFT_REDUCE_SLOTS per row
+                    ws = scratch("rfx_stft_loss_reduce_ws", R, n, device=x.device, dtype=torch.float64)      # per-workgroup partials
                     launch("rfx_stft_loss_reduce", X, Y, R, n, eps, ws, sums)
                     if _MEMO is not None and ("spec", X.data_ptr()) in _MEMO and ("spec", Y.data_ptr()) in _MEMO:
                         _MEMO[skey] = sums                               # both spectra are held by the memo: pointers stay valid
@@ -430,7 +430,7 @@ class _L1Fn(torch.autograd.Function):
         _req(a, "input"); _req(b, "target")
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty((), device=a.device, dtype=torch.float32)
-        ws = torch.empty(512, device=a.device, dtype=torch.float64)                 # RFX_L1_SLOTS per-workgroup partials
+        ws = scratch("rfx_l1_sum_ws", a.numel(), device=a.device, dtype=torch.float64)      # per-workgroup partials
         launch("rfx_l1_sum", a, b, a.numel(), ws, 1.0 / a.numel(), out)
         ctx.save_for_backward(a, b)
         return out
@@ -571,7 +571,7 @@ class SISDRLoss(_TimeLoss):
             t = t.contiguous()
         R = x.shape[0]
         s = torch.empty((R, 5), device=x.device, dtype=torch.float64)
-        ws = torch.empty(5 * R * 128, device=x.device, dtype=torch.float64)          # RFX_SISDR_SLOTS per-workgroup partials per row
+        ws = scratch("rfx_sisdr_sums_ws", R, L, device=x.device, dtype=torch.float64)       # per-workgroup partials per row
         launch("rfx_sisdr_sums", x, t, R, L, x.stride(0), t.stride(0), ws, s)
         out = torch.empty((), device=x.device, dtype=torch.float32)      # the scalar tail in one launch (fp64 inside)
         launch("rfx_sisdr_finish", s, R, L, 1 if self.zero_mean else 0, float(self.eps), out)

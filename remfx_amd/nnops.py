@@ -56,8 +56,7 @@ class _GroupNormFn(torch.autograd.Function):
         given = (sums.shape[1] if sums.dim() == 3 else 1) if sums is not None else 0     # number of partial-sum slots
         if sums is None:
             # the statistics kernel stores one pair per (group, chunk) into its own slot: no zero fill, no atomics
-            chunks = query("rfx_groupnorm_stat_chunks", Cc, S, groups)
-            sums = torch.empty(N * groups * 2 * max(chunks, 1), device=x.device, dtype=torch.float64)
+            sums = ops.scratch("rfx_groupnorm_fwd_ws", N, Cc, S, groups, device=x.device, dtype=torch.float64)
             given = -1
         if res is not None:
             ops._req(res, "res")
@@ -116,7 +115,7 @@ class _BatchNormFn(torch.autograd.Function):
         if training:
             mean = torch.empty(Cc, device=x.device, dtype=torch.float32)
             rstd = torch.empty_like(mean)
-            sums = torch.empty(Cc * 2 * query("rfx_batchnorm_stat_slots", N, S), device=x.device, dtype=torch.float64)
+            sums = ops.scratch("rfx_batchnorm_fwd_ws", N, Cc, S, device=x.device, dtype=torch.float64)
             given = 0
         else:
             mean = running_mean.contiguous()
@@ -341,9 +340,9 @@ class _DConvLayerFn(torch.autograd.Function):
         dz = torch.empty((N, 2 * Cc, T), device=x.device, dtype=torch.bfloat16)
         a_out = torch.empty((N, H, T), device=x.device, dtype=torch.float32)
         dh = torch.empty((N, H, T), device=x.device, dtype=torch.bfloat16)
-        partial = torch.empty((query("rfx_dconv_layer_bwd_rows", N), 5 * Cc + 2 * H), device=x.device, dtype=torch.float32)
+        partial = ops.scratch("rfx_dconv_layer_bwd_ws", N, Cc, T, dil, device=x.device, dtype=torch.float32)
         launch("rfx_dconv_layer_bwd", x, gy, dx, N, Cc, T, dil, w1, b1, g1w, g1b, w2, b2, g2w, g2b, scale, eps, dz, a_out, dh, partial)
-        ps = partial.sum(0)
+        ps = partial.view(-1, 5 * Cc + 2 * H).sum(0)       # one row per workgroup: dscale | dgn2w | dgn2b | dgn1w | dgn1b
         dscale, dg2w, dg2b = ps[:Cc], ps[Cc:3 * Cc], ps[3 * Cc:5 * Cc]
         dg1w, dg1b = ps[5 * Cc:5 * Cc + H], ps[5 * Cc + H:]
         # weight / bias gradients of the two convolutions on the existing wgrad kernels (side stream + in place when a GradSink is armed)
@@ -447,7 +446,7 @@ def row_moments(x, eps):
     x = x.contiguous()
     R = x.shape[0]
     L = x.numel() // R
-    sums = torch.empty(2 * R * query("rfx_row_moments_slots", L), device=x.device, dtype=torch.float64)    # one slot per workgroup
+    sums = ops.scratch("rfx_row_moments_ws", R, L, device=x.device, dtype=torch.float64)      # one slot per workgroup
     mean = torch.empty(R, device=x.device, dtype=torch.float32)
     std, a, b = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
     launch("rfx_row_moments", x, R, L, sums, mean, std, float(eps), a, b)     # a = 1 / (eps + std), b = -mean a: the finalize kernel

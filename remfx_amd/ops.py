@@ -294,6 +294,21 @@ def query(name, *args):
     return int(getattr(_lib.lib(), name)(*_native(args)))
 
 
+def scratch_size(ws_query, *geometry):
+    """Elements of a caller-owned scratch buffer: what the library's own query for it (`rfx_X_ws`, or `rfx_X_ws_<field>` where
+    rfx_X has several; include/remfx_hip.h, conventions) answers for the geometry rfx_X will be launched with.  Raises where the
+    launcher would refuse that geometry: no size is worked out on this side of the ABI."""
+    n = query(ws_query, *geometry)
+    if n < 0:
+        raise RuntimeError(f"{ws_query}{geometry} = {n}: the launcher refuses this geometry")
+    return n
+
+
+def scratch(ws_query, *geometry, device, dtype):
+    """That buffer: uninitialised, scratch_size(ws_query, *geometry) elements of `dtype` (the type the header states beside the query)."""
+    return torch.empty(scratch_size(ws_query, *geometry), device=device, dtype=dtype)
+
+
 # Spelling an ABI call by hand -- `lib.rfx_x(_ptr(a), n, _stream())`, no helper in between -- is what the per-element kernel tests
 # and the probes under scripts/ do on purpose: they call the entry point under test directly and judge its return code
 # themselves.  These two spell its pointer and stream arguments; nothing in the package calls them (launch is the way in), and

@@ -90,7 +90,7 @@ class FlatAdamW:
         self.step_count = 0
         dev = flat.data.device
         self._sumsq = torch.zeros(1, device=dev, dtype=torch.float64)
-        self._sumsq_ws = torch.empty(4096, device=dev, dtype=torch.float64)        # RFX_SUMSQ_SLOTS per-workgroup partials
+        self._sumsq_ws = ops.scratch("rfx_sumsq_ws", flat.numel, device=dev, dtype=torch.float64)    # per-workgroup partials
         self._coef = torch.ones(1, device=dev, dtype=torch.float32)
         self.last_grad_norm = torch.zeros(1, device=dev, dtype=torch.float32)
         self.param_groups = [{"lr": lr}]                 # scheduler-facing, as torch optimisers

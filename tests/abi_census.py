@@ -43,6 +43,7 @@ PINNED_BY = {
     "rfx_cl_im2col_s4": "test_gpu_clast_kernel.py",
     "rfx_cl_pack": "test_gpu_clast_kernel.py",
     "rfx_cl_rowsum": "test_gpu_clast_kernel.py",
+    "rfx_cl_rowsum_ws": "test_gpu_clast_kernel.py",
     "rfx_cl_to_cm": "test_gpu_clast_kernel.py",
     "rfx_cl_wgrad": "test_gpu_clast_kernel.py",
     "rfx_cl_wgrad_reduce": "test_gpu_clast_kernel.py",
@@ -50,22 +51,27 @@ PINNED_BY = {
     "rfx_cl_wgrad_ws_floats": "test_gpu_clast_kernel.py",
     # test_gpu_cldconv_kernel.py
     "rfx_cl_dconv_bwd": "test_gpu_cldconv_kernel.py",
+    "rfx_cl_dconv_bwd_ws_partial": "test_gpu_cldconv_kernel.py",
+    "rfx_cl_dconv_bwd_ws_sums": "test_gpu_cldconv_kernel.py",
+    "rfx_cl_dconv_bwd_ws_tsum": "test_gpu_cldconv_kernel.py",
     "rfx_cl_dconv_fwd": "test_gpu_cldconv_kernel.py",
+    "rfx_cl_dconv_fwd_ws_partial": "test_gpu_cldconv_kernel.py",
     # test_gpu_cplx_kernel.py
     "rfx_bound_mask_bwd": "test_gpu_cplx_kernel.py",
     "rfx_bound_mask_fwd": "test_gpu_cplx_kernel.py",
     "rfx_cplx_affine_act_bwd": "test_gpu_cplx_kernel.py",
+    "rfx_cplx_affine_act_bwd_ws": "test_gpu_cplx_kernel.py",
     "rfx_cplx_affine_act_fwd": "test_gpu_cplx_kernel.py",
     "rfx_cplx_coef_bwd": "test_gpu_cplx_kernel.py",
     "rfx_cplx_coef_fwd": "test_gpu_cplx_kernel.py",
     "rfx_cplx_moments": "test_gpu_cplx_kernel.py",
     "rfx_cplx_moments_bwd": "test_gpu_cplx_kernel.py",
-    "rfx_cplx_slots": "test_gpu_cplx_kernel.py",
+    "rfx_cplx_moments_ws": "test_gpu_cplx_kernel.py",
     "rfx_phase_mask_bwd": "test_gpu_cplx_kernel.py",
     "rfx_phase_mask_fwd": "test_gpu_cplx_kernel.py",
     # test_gpu_dconv_kernel.py
     "rfx_dconv_layer_bwd": "test_gpu_dconv_kernel.py",
-    "rfx_dconv_layer_bwd_rows": "test_gpu_dconv_kernel.py",
+    "rfx_dconv_layer_bwd_ws": "test_gpu_dconv_kernel.py",
     "rfx_dconv_layer_fwd": "test_gpu_dconv_kernel.py",
     "rfx_dconv_layer_ok": "test_gpu_dconv_kernel.py",
     # test_gpu_elem_kernel.py
@@ -82,13 +88,15 @@ PINNED_BY = {
     "rfx_fm_cm_affine_g": "test_gpu_elem_kernel.py",
     "rfx_l1_grad": "test_gpu_elem_kernel.py",
     "rfx_l1_sum": "test_gpu_elem_kernel.py",
+    "rfx_l1_sum_ws": "test_gpu_elem_kernel.py",
     "rfx_mul": "test_gpu_elem_kernel.py",
     "rfx_prelu_bwd": "test_gpu_elem_kernel.py",
+    "rfx_prelu_bwd_ws": "test_gpu_elem_kernel.py",
     "rfx_prelu_fwd": "test_gpu_elem_kernel.py",
     "rfx_row_affine": "test_gpu_elem_kernel.py",
     "rfx_row_affine_add": "test_gpu_elem_kernel.py",
     "rfx_row_moments": "test_gpu_elem_kernel.py",
-    "rfx_row_moments_slots": "test_gpu_elem_kernel.py",
+    "rfx_row_moments_ws": "test_gpu_elem_kernel.py",
     "rfx_span_mask": "test_gpu_elem_kernel.py",
     "rfx_zero": "test_gpu_elem_kernel.py",
     # test_gpu_fft_kernel.py
@@ -99,6 +107,7 @@ PINNED_BY = {
     "rfx_stft_loss_grad": "test_gpu_fft_kernel.py",
     "rfx_stft_loss_grad_m": "test_gpu_fft_kernel.py",
     "rfx_stft_loss_reduce": "test_gpu_fft_kernel.py",
+    "rfx_stft_loss_reduce_ws": "test_gpu_fft_kernel.py",
     "rfx_stft_pair_loss": "test_gpu_fft_kernel.py",
     "rfx_stft_pair_loss_ws": "test_gpu_fft_kernel.py",
     # test_gpu_fir.py
@@ -108,12 +117,16 @@ PINNED_BY = {
     # test_gpu_fx_kernel.py
     "rfx_fx_chorus": "test_gpu_fx_kernel.py",
     "rfx_fx_compressor": "test_gpu_fx_kernel.py",
+    "rfx_fx_compressor_ws": "test_gpu_fx_kernel.py",
     "rfx_fx_delay": "test_gpu_fx_kernel.py",
     "rfx_fx_distortion": "test_gpu_fx_kernel.py",
     "rfx_fx_eq": "test_gpu_fx_kernel.py",
     "rfx_fx_limiter": "test_gpu_fx_kernel.py",
+    "rfx_fx_limiter_ws": "test_gpu_fx_kernel.py",
     "rfx_fx_loudness": "test_gpu_fx_kernel.py",
     "rfx_fx_loudness_joint": "test_gpu_fx_kernel.py",
+    "rfx_fx_loudness_joint_ws": "test_gpu_fx_kernel.py",
+    "rfx_fx_loudness_ws": "test_gpu_fx_kernel.py",
     "rfx_fx_normalize_rows": "test_gpu_fx_kernel.py",
     "rfx_fx_normalize_ws_bytes": "test_gpu_fx_kernel.py",
     "rfx_fx_phaser": "test_gpu_fx_kernel.py",
@@ -144,6 +157,7 @@ PINNED_BY = {
     "rfx_mrstft_combine_w": "test_gpu_loss_kernel.py",
     "rfx_sisdr_finish": "test_gpu_loss_kernel.py",
     "rfx_sisdr_sums": "test_gpu_loss_kernel.py",
+    "rfx_sisdr_sums_ws": "test_gpu_loss_kernel.py",
     "rfx_stft_scaled_loss": "test_gpu_loss_kernel.py",
     "rfx_stft_scaled_loss_grad": "test_gpu_loss_kernel.py",
     "rfx_stft_scaled_loss_ws": "test_gpu_loss_kernel.py",
@@ -168,18 +182,20 @@ PINNED_BY = {
     "rfx_avgpool2d_fwd": "test_gpu_norm_kernel.py",
     "rfx_batchnorm_bwd": "test_gpu_norm_kernel.py",
     "rfx_batchnorm_fwd": "test_gpu_norm_kernel.py",
-    "rfx_batchnorm_stat_slots": "test_gpu_norm_kernel.py",
+    "rfx_batchnorm_fwd_ws": "test_gpu_norm_kernel.py",
     "rfx_glu_bwd": "test_gpu_norm_kernel.py",
     "rfx_glu_bwd_bf16": "test_gpu_norm_kernel.py",
     "rfx_glu_fwd": "test_gpu_norm_kernel.py",
     "rfx_groupnorm_bwd": "test_gpu_norm_kernel.py",
     "rfx_groupnorm_bwd_x16": "test_gpu_norm_kernel.py",
     "rfx_groupnorm_fwd": "test_gpu_norm_kernel.py",
+    "rfx_groupnorm_fwd_ws": "test_gpu_norm_kernel.py",
     "rfx_groupnorm_fwd_x16": "test_gpu_norm_kernel.py",
     "rfx_groupnorm_stat_chunks": "test_gpu_norm_kernel.py",
     "rfx_norm_bwd_work_floats": "test_gpu_norm_kernel.py",
     # test_gpu_optim_kernel.py
     "rfx_sumsq": "test_gpu_optim_kernel.py",
+    "rfx_sumsq_ws": "test_gpu_optim_kernel.py",
     "rfx_adamw_step": "test_gpu_optim_kernel.py",
     "rfx_clip_coef": "test_gpu_optim_kernel.py",
     # test_gpu_segment_kernel.py

@@ -56,7 +56,7 @@ def nchunks(S):
 
 
 def slots(N, S):
-    """rfx_cplx_slots: one slot per (sample, 4096-value chunk) and channel"""
+    """slots per channel behind rfx_cplx_moments_ws / rfx_cplx_affine_act_bwd_ws: one per (sample, 4096-value chunk) and channel"""
     return -1 if N <= 0 or S <= 0 else N * nchunks(S)
 
 

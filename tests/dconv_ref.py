@@ -110,7 +110,7 @@ def grid_fwd(N):
 
 
 def bwd_rows(N):
-    """rfx_dconv_layer_bwd_rows: one workgroup (one row of partial) per pair of samples, 256 at the most"""
+    """rows of rfx_dconv_layer_bwd_ws: one workgroup (one row of partial) per pair of samples, 256 at the most"""
     return min((N + 1) // 2, 256)
 
 

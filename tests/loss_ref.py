@@ -42,7 +42,7 @@ REF_U = 2.0 ** -LONGDOUBLE_BITS                          # a half-ulp of the ref
 LIBM_ULP = 4.0                                           # ASSUMED for device exp / log / log10 / sqrt in fp64
 LIBM = LIBM_ULP * 2.0 * U64
 SECOND_ORDER = 1.0 + 2.0 ** -16                          # first-order counts are multiplied by this
-SLOTS = 128                                              # RFX_SISDR_SLOTS
+SLOTS = 128                                              # TIME_SUMS_MAX_SLOTS of losses.hip
 MAX_ROWS = 65535                                         # RFX_LOSS_MAX_ROWS
 KINDS = ("sisdr", "sdsdr", "snr", "esr", "dc", "logcosh")
 REDUCTIONS = ("mean", "sum", "none")

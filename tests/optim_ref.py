@@ -26,7 +26,7 @@ import math
 from tests.ref_common import EPS32, f32  # noqa: F401
 
 FP32_HALF_ULPS = 16
-SLOTS = 4096                      # RFX_SUMSQ_SLOTS
+SLOTS = 4096                      # SUMSQ_MAX_SLOTS of optim.hip
 HYPER = dict(betas=(0.95, 0.999), eps=1e-6, wd=1e-3)
 SUMSQ_N = (0, 1, 3, 4, 5, 1023, 1025, 4_194_304 + 1027)
 ADAMW_N = (1, 5, 1025, 4_194_304 + 1027)

@@ -170,7 +170,7 @@ def test_case_tables_reach_every_branch():
 
 
 def test_workspace_geometry_mirrors_the_launch_code():
-    """a few geometries worked by hand from channel_sum_geometry / rfx_row_moments_slots / grid_for"""
+    """a few geometries worked by hand from channel_sum_geometry / row_moments_slots / grid_for"""
     assert E.channel_geometry(0, 1, 1, 1, 1024, 1024, 1024, 1024, 1) == (1, 1)
     assert E.channel_geometry(0, 3, 5, 1, 16389, 5 * 16392, 16392, 16389, 1) == (48, 16)
     assert E.channel_geometry(0, 3, 683, 1, 16389, 683 * 16392, 16392, 16389, 1) == (3, 1)

@@ -195,7 +195,11 @@ def test_dgelu_dglu(C, npos):
                                            (2, 5, 5, 48, 192, True)])
 def test_rowsum(N, A, XA, C, B, acc):
     """A == 1 with the rows folded into N, A > 1 (the frequency embedding's gradient), N % G != 0 (N = 2100 on G = 2048), accumulate"""
-    from remfx_amd import clchain
+    from remfx_amd import _lib, clchain
+    Nf = N * XA if A == 1 else N                               # samples after clchain.rowsum folded the rows
+    G = max(1, min(Nf, -(-2048 // A)))                         # its split, a launch argument: `partial` is G partials of A * C floats
+    assert _lib.lib().rfx_cl_rowsum_ws(Nf, A, B, C, G) == G * A * C
+    assert _lib.lib().rfx_cl_rowsum_ws(Nf, A, B, 12, G) == -1 and _lib.lib().rfx_cl_rowsum_ws(Nf, A, B, C, 0) == -1
     x = _rand((N, XA, B, C), N + C)
     xd = x.to(torch.bfloat16).to(DEV)
     base = _rand((A, C), 3, bf16=False) * 50

@@ -52,6 +52,20 @@ class _Alloc:
         for name, b in self.bufs.items():
             b.owned() if name in outputs else b.guards_intact()
 
+    def sizes(self, *names):
+        """elements of the scratch buffers the launch path sized from the library's queries (absent: not allocated)"""
+        return {n: self.bufs[n].n for n in names if n in self.bufs}
+
+
+def _asked(case, *queries):
+    """{field: what the library's query answers for the case's S, C, H, grid, TPS}, fields the call does not use (0) left out"""
+    import ctypes
+    from remfx_amd import _lib
+    d = _lib.ClDconvDesc()
+    d.S, d.C, d.H, d.grid, d.TPS = case.nsamp * case.TPS, case.C, case.C // 4, case.g, case.TPS
+    got = {q.rsplit("_", 1)[1]: int(getattr(_lib.lib(), q)(ctypes.byref(d))) for q in queries}
+    return {k: v for k, v in got.items() if v}
+
 
 def _layout(case):
     """(Bn, A) of the (Bn, A, L, C) tensor the samples travel in"""
@@ -88,6 +102,11 @@ def run_forward(case, inp, train):
     y, a, hpre, stats = cldconv.layer_forward(cl(inp["x"]), *p, case.dil, EPS, train, alloc=al)
     torch.cuda.synchronize()
     al.check(("y", "a", "hpre", "stats"))
+    # rfx_cl_dconv_fwd_ws_partial against the restated rule: the tile sums [S][2] of the statistics passes, nothing at one tile per sample
+    S = case.nsamp * case.TPS
+    want = {"part": 2 * S} if case.TPS > 1 else {}
+    asked = {"part": v for v in _asked(case, "rfx_cl_dconv_fwd_ws_partial").values()}
+    assert al.sizes("part") == asked == want, (case.id, al.sizes("part"), asked, want)
     return y, a, hpre, stats
 
 
@@ -102,6 +121,13 @@ def run_backward(case, inp, sv):
                                  case.dil, EPS, alloc=al)
     torch.cuda.synchronize()
     al.check(("dx", "dz", "dh", "pg"))
+    # rfx_cl_dconv_bwd_ws_partial / _tsum / _sums against the restated rules: a row of 5 C + 2 H per workgroup, min(grid, S) workgroups;
+    # in passes the tile sums [S][2] and the sample means [samples][4]
+    S, want = case.nsamp * case.TPS, {"partial": min(case.g, case.nsamp * case.TPS) * (5 * case.C + 2 * H)}
+    if case.passes:
+        want.update(tsum=2 * S, sums=4 * case.nsamp)
+    asked = _asked(case, "rfx_cl_dconv_bwd_ws_partial", "rfx_cl_dconv_bwd_ws_tsum", "rfx_cl_dconv_bwd_ws_sums")
+    assert al.sizes("partial", "tsum", "sums") == asked == want, (case.id, al.sizes("partial", "tsum", "sums"), asked, want)
     return out
 
 

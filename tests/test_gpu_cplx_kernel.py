@@ -9,7 +9,7 @@ with magnitude = sum of |terms| the element was formed from and floor = the erro
 partial sums, in the same units (cplx_ref.floors_*; never measured on the kernel).  The walk of the case tables over the dispatch, the
 1e-3 cap on every bound and the 1e-4 cap on the sign band are in tests/test_cplx_ref_cpu.py; floors and findings in DESIGN.md 4.20.
 
-Buffers: every output is NaN-filled between two NaN guards of 4096 elements; `ws` has exactly the size rfx_cplx_slots implies, is
+Buffers: every output is NaN-filled between two NaN guards of 4096 elements; `ws` has exactly the size rfx_cplx_moments_ws / rfx_cplx_affine_act_bwd_ws answer, is
 NaN-filled and followed by a guard (every slot has to be written: it comes back finite).  A sliced output is a channel slice of a wider
 NaN-filled buffer whose neighbouring channels must keep their bits; a sliced gy is read from one (a read outside the slice returns NaN).
 Every case runs twice into fresh buffers: plain slot stores and ordered sums, the same bits."""
@@ -51,9 +51,10 @@ def launch_stream(case, inp, coef, cm):
     L, _ptr, _stream = api()
     N, C, S = case.N, case.C, case.S
     x, coef_d, cm_d = inp["x"].cuda(), coef.cuda().contiguous(), cm.cuda().contiguous()
-    assert L.rfx_cplx_slots(N, S) == R.slots(N, S)
+    nws, nws2 = int(L.rfx_cplx_moments_ws(N, C, S)), int(L.rfx_cplx_affine_act_bwd_ws(N, C, S))
+    assert (nws, nws2) == (R.moments_ws(N, C, S), R.affine_bwd_ws(N, C, S)) == (5 * C * R.slots(N, S), 6 * C * R.slots(N, S))
     got = {}
-    ws = Guarded(R.moments_ws(N, C, S), torch.float64, front=False, what="moments ws")
+    ws = Guarded(nws, torch.float64, front=False, what="moments ws")
     sums = Guarded(5 * C, torch.float64, what="sums")
     assert L.rfx_cplx_moments(_ptr(x), N, C, S, _ptr(ws.t), _ptr(sums.t), _stream()) == 0
     torch.cuda.synchronize()
@@ -72,7 +73,7 @@ def launch_stream(case, inp, coef, cm):
     y.owned()
     got["y"] = y.t.reshape(N, 2 * C, S).cpu()
     gx = Guarded(N * 2 * C * S, what="gx")
-    ws2 = Guarded(R.affine_bwd_ws(N, C, S), torch.float64, front=False, what="affine_act_bwd ws")
+    ws2 = Guarded(nws2, torch.float64, front=False, what="affine_act_bwd ws")
     gcoef = Guarded(6 * C, what="gcoef")
     gy_bits = gy.b.buf.clone() if case.sliced else gy.buf.clone()
     assert L.rfx_cplx_affine_act_bwd(_ptr(x), _ptr(coef_d), _ptr(gy.t), gy_ns, C, N, C, S, R.SLOPE, _ptr(gx.t), _ptr(ws2.t), _ptr(gcoef.t),

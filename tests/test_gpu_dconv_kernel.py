@@ -1,4 +1,4 @@
-"""Both kernels of remfx_amd/csrc/dconv.hip through the C ABI (rfx_dconv_layer_fwd, rfx_dconv_layer_bwd, rfx_dconv_layer_bwd_rows,
+"""Both kernels of remfx_amd/csrc/dconv.hip through the C ABI (rfx_dconv_layer_fwd, rfx_dconv_layer_bwd, rfx_dconv_layer_bwd_ws,
 rfx_dconv_layer_ok) against tests/dconv_ref.py: one fused channel-major DConv layer in fp64, rounded to bf16 where the kernels round,
 judged PER ELEMENT and in stages at
 
@@ -52,8 +52,10 @@ class Call:
         self.N, self.bwd = N, bwd
         self.ins = {k: Guarded(inp[k].numel(), F32, k, init=inp[k], off=o[F32]) for k in ("x",) + (("gy",) if bwd else ()) + PARAMS}
         if bwd:
+            nws = int(api()[0].rfx_dconv_layer_bwd_ws(N, C, T, 1))    # `partial` is as long as the library says: one row per workgroup
+            assert nws == R.bwd_rows(N) * ROWS
             shapes = {"gx": (F32, (N, C, T)), "dz": (BF16, (N, 2 * C, T)), "a_out": (F32, (N, H, T)), "dh": (BF16, (N, H, T)),
-                      "partial": (F32, (R.bwd_rows(N), ROWS))}
+                      "partial": (F32, (nws // ROWS, ROWS))}
         else:
             shapes = {"out": (F32, (N, C, T))}
             if train:
@@ -166,10 +168,15 @@ def test_backward_feeds_the_weight_gradient_calls():
     _show(case, "bwd -> wgrad", R.judge_wgrad(inp, dil, got, K))
 
 
-def test_bwd_rows():
+def test_bwd_ws():
+    """floats of `partial`: a row of 5 C + 2 H per workgroup, a workgroup per pair of samples up to 256; the same for both dilations,
+    -1 for what rfx_dconv_layer_bwd refuses"""
     lib = api()[0]
     for N in (1, 2, 3, 511, 512, 513, 100000):
-        assert lib.rfx_dconv_layer_bwd_rows(N) == min(-(-N // 2), 256) == R.bwd_rows(N), N
+        for dil in (1, 2):
+            assert lib.rfx_dconv_layer_bwd_ws(N, C, T, dil) == min(-(-N // 2), 256) * ROWS == R.bwd_rows(N) * ROWS, N
+    for bad in ((0, C, T, 1), (-1, C, T, 1), (4, 96, T, 1), (4, C, 255, 1), (4, C, T, 3)):
+        assert lib.rfx_dconv_layer_bwd_ws(*bad) == -1, bad
 
 
 def test_layer_ok():

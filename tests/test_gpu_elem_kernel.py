@@ -200,7 +200,9 @@ def test_prelu(shape):
     def run():
         X, G, S = Guarded(x.numel(), what="x", init=x), Guarded(x.numel(), what="gy", init=gy), Guarded(Cc, what="slope", init=slope)
         Y, GX, GS = Guarded(x.numel(), what="y"), Guarded(x.numel(), what="gx"), Guarded(Cc, what="gslope")
-        WS = Guarded(N * Cc, torch.float64, "ws")
+        nws = int(L.rfx_prelu_bwd_ws(N, Cc, Ln))
+        assert nws == N * Cc                                   # one slot per (sample, channel)
+        WS = Guarded(nws, torch.float64, "ws")
         assert L.rfx_prelu_fwd(X.ptr(), S.ptr(), Y.ptr(), N, Cc, Ln, stream()) == 0
         assert L.rfx_prelu_bwd(X.ptr(), G.ptr(), S.ptr(), GX.ptr(), WS.ptr(), GS.ptr(), N, Cc, Ln, stream()) == 0
         torch.cuda.synchronize()
@@ -221,7 +223,9 @@ def test_prelu(shape):
 def _l1(a, b, n, scale, w, gup):
     L, _, stream = api()
     A, B = Guarded(max(n, 1), what="a", init=a if n else None), Guarded(max(n, 1), what="b", init=b if n else None)
-    WS, OUT, GR = Guarded(E.L1_SLOTS, torch.float64, "ws"), Guarded(1, what="out"), Guarded(max(n, 1), what="g")
+    nws = int(L.rfx_l1_sum_ws(n))
+    assert nws == E.L1_SLOTS                                   # the restated cap, for every n (524289 of L1_N: one workgroup past it)
+    WS, OUT, GR = Guarded(nws, torch.float64, "ws"), Guarded(1, what="out"), Guarded(max(n, 1), what="g")
     GUP = Guarded(1, what="gup", init=torch.tensor([gup])) if gup is not None else None
     assert L.rfx_l1_sum(A.ptr(), B.ptr(), n, WS.ptr(), scale, OUT.ptr(), stream()) == 0
     rg = L.rfx_l1_grad(A.ptr(), B.ptr(), n, w, GUP.ptr() if GUP else None, GR.ptr(), stream())
@@ -379,17 +383,18 @@ def test_blstm_frames(case, mode):
 @pytest.mark.parametrize("shape", E.MOMENT_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_row_moments(shape, coef):
     """rfx_row_moments: 1, 2, 3 slots, R not a multiple of the finalize workgroup's four rows, a row at mean / std = 1e3 and a constant
-    row (std == 0 exactly, a == 1 / eps); sums is 2 R rfx_row_moments_slots(L) doubles, all written.  coef_a / coef_b are judged as
+    row (std == 0 exactly, a == 1 / eps); sums is rfx_row_moments_ws(R, L) doubles, all written.  coef_a / coef_b are judged as
     functions of the fp32 mean / std the kernel stored."""
     L, _, stream = api()
     R, Ln = shape
     x = E.moments_data(R, Ln, 91 + Ln)
-    slots = L.rfx_row_moments_slots(Ln)
-    assert slots == E.moments_slots(Ln)
+    slots = E.moments_slots(Ln)
+    nws = int(L.rfx_row_moments_ws(R, Ln))
+    assert nws == 2 * R * slots
     info = (shape, sorted(E.forms_moments(R, Ln, coef)))
 
     def run():
-        X, S = Guarded(R * Ln, what="x", init=x), Guarded(2 * R * slots, torch.float64, "sums")
+        X, S = Guarded(R * Ln, what="x", init=x), Guarded(nws, torch.float64, "sums")
         M, D, A, Bc = (Guarded(R, what=k) for k in ("mean", "std", "coef_a", "coef_b"))
         assert L.rfx_row_moments(X.ptr(), R, Ln, S.ptr(), M.ptr(), D.ptr(), E.MOMENT_EPS, A.ptr() if coef else None, Bc.ptr() if coef else None,
                                  stream()) == 0

@@ -287,14 +287,18 @@ def _pairs(Z):
     return torch.view_as_real(Z.contiguous()).contiguous()
 
 
-@pytest.mark.parametrize("n", F.CELL_N)
-@pytest.mark.parametrize("R", F.CELL_R)
+# + one row exactly one workgroup past grid_red's cap of REDUCE_SLOTS workgroups of 16384 cells
+REDUCE_CASES = [(R, n) for n in F.CELL_N for R in F.CELL_R] + [(1, F.REDUCE_SLOTS * 16384 + 1)]
+
+
+@pytest.mark.parametrize("R,n", REDUCE_CASES)
 def test_loss_reduce(R, n):
     """rfx_stft_loss_reduce on given spectra: the three row sums against fp64 within K eps32 of the terms' first-order magnitude
     (K from the measured floor of their float32 evaluation) plus gamma_8 of the fp32 partial sums of eight cells; the stored float32
     spectra are the inputs, so no cell carries an interval.  n = 1 ... one
-    more than a whole unroll-by-eight round (the clamped index at n - 1), several slots and a second grid-stride round; X = 0 and
-    |X|^2 at, just below and just above eps are among the cells."""
+    more than a whole unroll-by-eight round (the clamped index at n - 1), several slots and a second grid-stride round, and one workgroup
+    more than the capped grid has, with ws exactly as long as rfx_stft_loss_reduce_ws says; X = 0 and |X|^2 at, just below and just
+    above eps are among the cells."""
     L, _, stream = api()
     X, Y, _, _ = F.cell_inputs(R, n, 100 * R + n)
     z = torch.zeros(R, n, dtype=torch.float64)
@@ -303,7 +307,9 @@ def test_loss_reduce(R, n):
 
     def run():
         XB, YB = Guarded(2 * R * n, what="xc", init=_pairs(X)), Guarded(2 * R * n, what="yc", init=_pairs(Y))
-        WS = Guarded(3 * R * F.REDUCE_SLOTS, dtype=torch.float64, what="ws")
+        nws = int(L.rfx_stft_loss_reduce_ws(R, n))
+        assert nws == 3 * R * F.REDUCE_SLOTS                   # the restated cap per row and sum, for every n
+        WS = Guarded(nws, dtype=torch.float64, what="ws")
         SM = Guarded(3 * R, what="sums")
         rc = L.rfx_stft_loss_reduce(XB.ptr(), YB.ptr(), R, n, F.CELL_EPS, WS.ptr(), SM.ptr(), stream())
         torch.cuda.synchronize()

@@ -145,7 +145,9 @@ def _run_comp(x, thr, ratio, ca, cr, inplace=False):
     B, T = x.shape
     bufs = [Guarded.of(x, "x"), Guarded.of(thr, "thr"), Guarded.of(ratio, "ratio"), Guarded.of(ca, "c_attack"), Guarded.of(cr, "c_release")]
     Y = bufs[0] if inplace else Guarded(x.size, what="y")
-    W = Guarded(B * T, what="env_ws")                                    # exactly (B, T)
+    nws = int(L.rfx_fx_compressor_ws(B, T))
+    assert nws == B * T                                                  # exactly (B, T)
+    W = Guarded(nws, what="env_ws")
     sync(L.rfx_fx_compressor(bufs[0].ptr(), Y.ptr(), W.ptr(), B, T, *(b.ptr() for b in bufs[1:]), stream()), "rfx_fx_compressor", (B, T))
     for b in bufs[1 if inplace else 0:]:
         b.unchanged()
@@ -174,7 +176,9 @@ def _run_limit(x, p, inplace=False):
     B, T = x.shape
     Xb, P = Guarded.of(x, "x"), Guarded.of(p, "params")
     Y = Xb if inplace else Guarded(x.size, what="y")
-    W = Guarded(2 * B * T, what="ws")                                    # exactly 2 B T
+    nws = int(L.rfx_fx_limiter_ws(B, T))
+    assert nws == 2 * B * T                                              # exactly 2 B T
+    W = Guarded(nws, what="ws")
     sync(L.rfx_fx_limiter(Xb.ptr(), Y.ptr(), W.ptr(), B, T, P.ptr(), stream()), "rfx_fx_limiter", (B, T))
     P.unchanged()
     if not inplace:
@@ -365,7 +369,10 @@ def _run_loud(x, c, coef, inv, joint):
     L, _, stream = api()
     B, Cc, T = x.shape
     Xb = Guarded.of(x, "x")
-    H, Lu, Ga = Guarded(B * Cc * c["nhop"], torch.float64, "hop_ws"), Guarded(B, what="lufs"), Guarded(B, what="gain")
+    geom = (T, c["chunk"], c["hop"], c["nhop"], c["nblk"])
+    nws = int(L.rfx_fx_loudness_joint_ws(B, Cc, *geom)) if joint else int(L.rfx_fx_loudness_ws(B, *geom))
+    assert nws == B * Cc * c["nhop"]                                     # nhop hop sums per row
+    H, Lu, Ga = Guarded(nws, torch.float64, "hop_ws"), Guarded(B, what="lufs"), Guarded(B, what="gain")
     tail = (c["chunk"], c["hop"], c["nhop"], c["nblk"], inv, host(coef), X.LOUD_TARGET, H.ptr(), Lu.ptr(), Ga.ptr(), stream())
     rc = L.rfx_fx_loudness_joint(Xb.ptr(), B, Cc, T, *tail) if joint else L.rfx_fx_loudness(Xb.ptr(), B, T, *tail)
     sync(rc, "rfx_fx_loudness", (B, Cc, T))

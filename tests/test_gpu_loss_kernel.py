@@ -46,17 +46,19 @@ def _run_sums(c, entry, data=None):
     Xb, Tb = Guarded.of(xb, "x", c["ox"]), Guarded.of(tb, "t", c["ot"])
     S = Guarded(5 * R, F64, "sums")
     if entry == "rfx_sisdr_sums":
-        W = Guarded(5 * R * X.time_sums_grid(L), F64, "ws")
+        n, used = int(L_.rfx_sisdr_sums_ws(R, L)), 5 * R * X.time_sums_grid(L)
+        assert n == 5 * R * X.SLOTS                            # the restated cap per row and sum, for every L
+        W = Guarded(n, F64, "ws")
         rc = L_.rfx_sisdr_sums(Xb.ptr(), Tb.ptr(), R, L, xs, ts, W.ptr(), S.ptr(), stream())
     else:
-        n = int(L_.rfx_time_sums_ws(R, L))
+        n = used = int(L_.rfx_time_sums_ws(R, L))
         assert n == 5 * R * X.time_sums_grid(L)
         W = Guarded(n, F64, "ws")
         rc = L_.rfx_time_sums(Xb.ptr(), Tb.ptr(), R, L, xs, ts, *_h(_taps(c)), W.ptr(), S.ptr(), stream())
     sync(rc, entry, (R, L))
     Xb.unchanged(), Tb.unchanged()
     ws = W.np()
-    assert np.isfinite(ws).all(), (entry, "a slot of the workspace was not written")
+    assert np.isfinite(ws[:used]).all() and np.isnan(ws[used:]).all(), (entry, "slots written", used)
     return {"sums": S.np((R, 5))}
 
 
@@ -76,6 +78,19 @@ def test_time_sums(c):
     if c["taps"] is None:
         assert np.array_equal(a["sums"].view(np.uint8), b["sums"].view(np.uint8)), "rfx_time_sums without taps is not rfx_sisdr_sums"
     report("LOSS", "sums " + X.case_id(c), [("rfx_time_sums", r1), ("rfx_sisdr_sums", r2)])
+
+
+def test_sisdr_sums_one_workgroup_past_the_cap():
+    """R = 1, L = 128 x 2048 + 1: the row asks for one workgroup more than the capped grid has; ws is exactly rfx_sisdr_sums_ws doubles
+    between its guards, the slots of the 128 workgroups written and no other"""
+    L = X.SLOTS * 2048 + 1
+    assert X.grid_x(L) == X.SLOTS + 1 and X.time_sums_grid(L) == X.SLOTS
+    c = dict(next(c for c in X.TIME_CASES if c["R"] == 1 and c["kind"] == "sisdr"), L=L, taps=None, seed=1000 + 7 * L + 1)
+    data = X.time_data(c)
+    b, _ = twice(lambda: _run_sums(c, "rfx_sisdr_sums", data))
+    ref, bound = X.row_sums(data[0], data[1], None)
+    r = _judge(b["sums"], ref, bound, ctx=("rfx_sisdr_sums", "sums", "grid_capped"))
+    report("LOSS", "sums " + X.case_id(c), [("rfx_sisdr_sums", r)])
 
 
 # ---- per-row losses, the SI-SDR tail ---------------------------------------------------------------------------------------------------

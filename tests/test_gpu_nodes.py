@@ -133,12 +133,12 @@ def test_dconv_node(case, bf16_mode, launches):
 
 # ---- which entries a case launches ------------------------------------------------------------------------------------------------------
 def _literals():
-    """the string literals passed as first argument to launch / launch_rc / query in ops.py and nnops.py"""
+    """the string literals passed as first argument to launch / launch_rc / query / scratch in ops.py and nnops.py"""
     out = set()
     for f in ("ops.py", "nnops.py"):
         tree = ast.parse(open(os.path.join(ROOT, "remfx_amd", f)).read())
         for n in ast.walk(tree):
-            if isinstance(n, ast.Call) and getattr(n.func, "id", getattr(n.func, "attr", None)) in ("launch", "launch_rc", "query") and n.args:
+            if isinstance(n, ast.Call) and getattr(n.func, "id", getattr(n.func, "attr", None)) in ("launch", "launch_rc", "query", "scratch", "scratch_size") and n.args:
                 for c in ast.walk(n.args[0]):
                     if isinstance(c, ast.Constant) and isinstance(c.value, str):
                         out.add(c.value)
@@ -148,7 +148,7 @@ def _literals():
 # entries of ops.py / nnops.py that no V0 of the table reaches, and why
 UNREACHED = {
     "rfx_dconv_layer_fwd": "bf16 mode, its own shape: test_dconv_node runs the cases of node_ref.dconv_cases() under the recorder",
-    "rfx_dconv_layer_bwd": "as rfx_dconv_layer_fwd", "rfx_dconv_layer_bwd_rows": "as rfx_dconv_layer_fwd",
+    "rfx_dconv_layer_bwd": "as rfx_dconv_layer_fwd", "rfx_dconv_layer_bwd_ws": "as rfx_dconv_layer_fwd",
     "rfx_dconv_layer_ok": "asked by dconv_layer_fused_ok, the caller's routing question (test_gpu_hdemucs_route.py), not by the node",
     "rfx_unpack_add_bias": "written through the armed sink only: V5 / V6 of the conv cases, not V0",
     "rfx_gemm_fwd_variant": "behind ops.TRACE_VARIANT, the measurement hook of bench.py",
@@ -159,7 +159,7 @@ ONLY_IN = {"rfx_glu_bwd_bf16": "bf16", "rfx_localstate_mfma_ok": "bf16", "rfx_lo
 
 def test_v0_launches_what_the_table_says_and_the_tables_cover_the_wrappers(launches):
     """V0 of every case under the recorder: each case launches EXPECT's entries (forward then backward), and the union over the table is
-    every entry ops.py and nnops.py name in a launch / launch_rc / query call, but the ones UNREACHED gives a reason for.  Run in every
+    every entry ops.py and nnops.py name in a launch / launch_rc / query / scratch call, but the ones UNREACHED gives a reason for.  Run in every
     GEMM mode: the mode moves the entries of the GLU and attention nodes."""
     from remfx_amd import nnops
     m = mode()

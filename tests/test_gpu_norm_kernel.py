@@ -77,13 +77,13 @@ def launch(case, inp):
         mean_t, rstd_t = mean.t, rstd.t
         bufs += [mean, rstd]
         if bn:
-            slots = L.rfx_batchnorm_stat_slots(N, S)
-            assert slots == R.bn_stat_slots(N, S)
-            sums = Guarded(2 * C * slots, torch.float64, front=False, what="sums")
+            nsums = int(L.rfx_batchnorm_fwd_ws(N, C, S))
+            assert nsums == 2 * C * R.bn_stat_slots(N, S)
+            sums = Guarded(nsums, torch.float64, front=False, what="sums")
         elif case.given == -1:
-            chunks = L.rfx_groupnorm_stat_chunks(C, S, G)
-            assert chunks == R.stat_chunks(C, S, G)
-            sums = Guarded(2 * N * G * chunks, torch.float64, front=False, what="sums")
+            chunks, nsums = L.rfx_groupnorm_stat_chunks(C, S, G), int(L.rfx_groupnorm_fwd_ws(N, C, S, G))
+            assert chunks == R.stat_chunks(C, S, G) and nsums == 2 * N * G * chunks
+            sums = Guarded(nsums, torch.float64, front=False, what="sums")
         elif case.given == 0:
             sums = Guarded(2 * N * G, torch.float64, front=False, what="sums")
         else:                                                  # an INPUT: what a GEMM epilogue would have left, (NG, 2) or (NG, k, 2)

@@ -1,9 +1,9 @@
 """rfx_sumsq, rfx_clip_coef and rfx_adamw_step of remfx_amd/csrc/optim.hip through the C ABI on buffers this test allocates, against
 tests/optim_ref.py (fp64), per element.  The bounds and where their constants come from are in optim_ref's docstring and DESIGN.md 4.20;
 none is measured on the kernel.  n = 4 194 304 + 1027 crosses gridn's cap of 4096 workgroups (a fifth grid-stride iteration for a quarter
-of the threads) with an n % 4 tail of 3.
+of the threads) with an n % 4 tail of 3; n = 4096 x 1024 + 1 is exactly one workgroup past the cap of rfx_sumsq's own slot count.
 
-Buffers: p, g, m, v sit between NaN guards of 4096 elements; `ws` is NaN-filled, RFX_SUMSQ_SLOTS doubles plus a guard; g has to come back
+Buffers: p, g, m, v sit between NaN guards of 4096 elements; `ws` is NaN-filled, rfx_sumsq_ws(n) doubles plus a guard; g has to come back
 bit for bit.  Every case runs twice into fresh buffers: the same bits."""
 import math
 
@@ -28,7 +28,9 @@ def _sumsq(gcpu):
     L, _ptr, _stream = api()
     n = gcpu.numel()
     g = Guarded(max(n, 1), what="g", init=gcpu if n else None)
-    ws = Guarded(O.SLOTS, torch.float64, what="ws")
+    nws = int(L.rfx_sumsq_ws(n))
+    assert nws == O.SLOTS                                        # the library's size against the restated cap: the same for every n
+    ws = Guarded(nws, torch.float64, what="ws")
     out = Guarded(1, torch.float64, what="out")
     assert L.rfx_sumsq(_ptr(g.t), n, _ptr(ws.t), _ptr(out.t), _stream()) == 0
     torch.cuda.synchronize()
@@ -40,7 +42,10 @@ def _sumsq(gcpu):
     return float(out.t.cpu()), slots
 
 
-@pytest.mark.parametrize("n", O.SUMSQ_N)
+SUMSQ_N = O.SUMSQ_N + (O.SLOTS * 1024 + 1,)                     # + the first n that needs more workgroups than there are slots
+
+
+@pytest.mark.parametrize("n", SUMSQ_N)
 def test_sumsq(n):
     """the float4 body, the n % 4 tail, one / two / 4096 workgroups and the multi-slot sum; n = 0 writes 0 and no slot.
     |err| <= 4 x 2^-53 x (additions on the longest path) x sum g^2: the products of two floats are exact in fp64, every addition rounds

@@ -26,7 +26,7 @@ PRE, ASYM = (-0.85, 1.0, 0.0), (0.3, 1.0, -0.5)
 UP_SCALAR, UP_ROWS = 1.7, (1.7, -0.6, 2.3)
 
 # shape name -> (R, L) contiguous, or the cropped view base[..., 5:20000] of a (3, 1, 20011) tensor (row stride != L, start misaligned
-# by 20 bytes).  1003: L % 4 != 0;  5: shorter than any vector or halo;  70001 > RFX_SISDR_SLOTS * 256 = 32768: every workgroup wraps
+# by 20 bytes).  1003: L % 4 != 0;  5: shorter than any vector or halo;  70001 > 128 slots * 256 = 32768: every workgroup wraps
 # its grid-stride loop and there is a tail
 SHAPES = {"3x1003": (3, 1003), "1x5": (1, 5), "2x70001": (2, 70001), "crop": None}
 
@@ -252,7 +252,9 @@ def test_sums_without_taps_are_the_sisdr_sums():
         R = x.shape[0]
         assert x.stride(0) == (L if shape != "crop" else 20011)
         s = torch.empty((R, 5), device=DEV, dtype=torch.float64)
-        ws = torch.empty(5 * R * 128, device=DEV, dtype=torch.float64)
+        nws = int(_lib.lib().rfx_sisdr_sums_ws(R, L))
+        assert nws == 5 * R * 128
+        ws = torch.empty(nws, device=DEV, dtype=torch.float64)
         _lib.check(_lib.lib().rfx_sisdr_sums(_ptr(x), _ptr(y), R, L, x.stride(0), y.stride(0), _ptr(ws), _ptr(s), _stream()), "sums")
         got = _device_sums_and_coef(x, y, "sisdr", True, None)[0]
         assert np.array_equal(got, s.cpu().numpy())
@@ -277,7 +279,9 @@ def _legacy_sisdr(x, y, zero_mean=True, eps=1e-8):
     x2, y2 = x.reshape(-1, L), y.reshape(-1, L)
     R = x2.shape[0]
     s = torch.empty((R, 5), device=DEV, dtype=torch.float64)
-    ws = torch.empty(5 * R * 128, device=DEV, dtype=torch.float64)
+    nws = int(_lib.lib().rfx_sisdr_sums_ws(R, L))
+    assert nws == 5 * R * 128
+    ws = torch.empty(nws, device=DEV, dtype=torch.float64)
     _lib.check(_lib.lib().rfx_sisdr_sums(_ptr(x2), _ptr(y2), R, L, x2.stride(0), y2.stride(0), _ptr(ws), _ptr(s), _stream()), "sums")
     out = torch.empty((), device=DEV, dtype=torch.float32)
     _lib.check(_lib.lib().rfx_sisdr_finish(_ptr(s), R, L, 1 if zero_mean else 0, eps, _ptr(out), _stream()), "finish")
@@ -286,8 +290,8 @@ def _legacy_sisdr(x, y, zero_mean=True, eps=1e-8):
 
 @pytest.mark.parametrize("shape", ("3x1003", "2x70001", "crop"))
 def test_sisdr_metric_path_is_unchanged(shape, monkeypatch):
-    """SISDRLoss()(x.detach(), y): exactly the two launches rfx_sisdr_sums + rfx_sisdr_finish and their bits; the differentiable path
-    (rfx_time_sums + rfx_time_loss_rows) returns the same bits."""
+    """SISDRLoss()(x.detach(), y): exactly the two launches rfx_sisdr_sums + rfx_sisdr_finish (behind the one host-only query that
+    sizes the workspace of the first) and their bits; the differentiable path (rfx_time_sums + rfx_time_loss_rows) returns the same bits."""
     from remfx_amd import _lib, losses
     x, y = _inputs(shape)
     x, y = _view(x.to(DEV), shape), _view(y.to(DEV), shape)
@@ -312,7 +316,7 @@ def test_sisdr_metric_path_is_unchanged(shape, monkeypatch):
 
     monkeypatch.setattr(_lib, "lib", lambda: Spy())
     losses.SISDRLoss()(x.detach(), y)
-    assert calls == ["rfx_sisdr_sums", "rfx_sisdr_finish"], calls
+    assert calls == ["rfx_sisdr_sums_ws", "rfx_sisdr_sums", "rfx_sisdr_finish"], calls
 
 
 def test_same_bits_on_two_streams():

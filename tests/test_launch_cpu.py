@@ -136,3 +136,27 @@ def test_temporary_is_alive_inside_the_entry_point():
     assert seen["alive"] and torch.equal(seen["values"], base.contiguous())
     gc.collect()
     assert seen["ref"]() is None                                     # and released once the call has returned
+
+
+def test_scratch_asks_the_library_and_allocates_what_it_answers():
+    """ops.scratch: the named `_ws` query is called with the geometry it was given (tensors and descriptors by the argument rule, no
+    stream), and the buffer has exactly the answered number of elements of the stated type"""
+    d = _lib.StftDesc()
+    ref = C.byref(d)
+    for n, dtype in ((37, torch.float64), (0, torch.float32), (5, torch.float32)):
+        with seams(_Fake(rc=n)) as fake:
+            buf = ops.scratch("rfx_x_ws", 3, 7, ref, device="cpu", dtype=dtype)
+        assert fake.calls == [("rfx_x_ws", (3, 7, ref))]
+        assert buf.shape == (n,) and buf.dtype == dtype and buf.device.type == "cpu"
+    with seams(_Fake(rc=12)) as fake:
+        assert ops.scratch_size("rfx_x_ws_partial", ref) == 12
+    assert fake.calls == [("rfx_x_ws_partial", (ref,))]
+
+
+def test_scratch_raises_where_the_launcher_would_refuse():
+    for rc in (-1, -5):
+        with seams(_Fake(rc=rc)):
+            with pytest.raises(RuntimeError, match=r"rfx_x_ws\(4, -2\) = -"):
+                ops.scratch("rfx_x_ws", 4, -2, device="cpu", dtype=torch.float32)
+            with pytest.raises(RuntimeError, match="rfx_x_ws"):
+                ops.scratch_size("rfx_x_ws", 4, -2)
